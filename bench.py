@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — images/sec of BiRefNet::forward_logits (Swin-L) on N MI355X, one process per GPU.
 
-  python bench.py [--gpus N --steps K --warmup W] [--config c2|c3|c4|c5]
+  python bench.py [--gpus N --steps K --warmup W] [--config c2|c3|c4|c5] [--dump-outputs DIR] [--full]
 
 A "step" = one pass of the hot path over one batch of synthetic images already resident in HBM.  `--config` names a
 BASELINE.json configuration (default c2 = configs[1], the one `metric` is quoted on):
@@ -16,10 +16,17 @@ images.  N>1: either launched by torch.distributed.run (RANK / LOCAL_RANK / WORL
 WORLD_SIZE is unset — this process starts the N ranks itself BEFORE anything touches HIP and relays rank 0's JSON line.
 torch.distributed (RCCL) is used for the timing barrier and the max-over-ranks reduction only.
 
-The default line (config c2, no overrides) also carries `other_configs`: at N=1 the bf16 configurations c3 and c5 in both
-deform modes (`c3`, `c3_deformable`, `c5`, `c5_deformable`: own model, warm-up, timed steps bracketed by synchronize, roofline
-block, error of image 0 against the committed strided golden); at N>1 a `c4` / `c4_deformable` block (8 images per GPU bf16 on every
-rank, per-rank times + max).  SURVEY.md D1 assigns the deformable mode to configs 3-5 (the only mode with a gather).
+A plain run sets up, warms up, times the K steps and prints the line; it runs no other forward.  `--dump-outputs DIR` then
+also writes the logits of the last timed step as DIR/logits.npy (float32; DIR/logits_rank<r>.npy per rank at N>1; a fixed, seeded
+sample of them when they pass 64 MB), so that two builds can be compared output for output on identical inputs.
+
+`--full` adds everything else the line can carry: the roofline block (profiled steps after the timed region), the CPU baseline,
+the other compute modes (c2), the errors of image 0 against the committed strided golden (logits and mask), and, on the default
+line (config c2, no overrides), `other_configs`: at N=1 the bf16 configurations c3 and c5 in both deform modes (`c3`,
+`c3_deformable`, `c5`, `c5_deformable`: own model, warm-up, timed steps bracketed by synchronize, roofline block, golden errors);
+at N>1 a `c4` / `c4_deformable` block (8 images per GPU bf16 on every rank, per-rank times + max).  The options that tune these
+legs (--profile-steps, --cpu-baseline, --also, --other-configs, --mask-error) turn one on in a plain run when given explicitly.
+SURVEY.md D1 assigns the deformable mode to configs 3-5 (the only mode with a gather).
 
 Rank 0 prints ONE JSON line; see DESIGN.md §measurement for how each field is obtained.
 """
@@ -55,6 +62,7 @@ MODES = {
 GEMM_FAMILIES = ("gemm_dense", "gemm_conv_nhwc", "gemm_gather_nchw", "gemm_deform_nhwc")
 HBM_PEAK_TBS = 8.0                     # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.3 measured with a float4 copy)
 PROFILE_ROUND = ("r04", "r03", "r02")  # committed rocprofv3 evidence, newest first (profiles/README.md)
+DUMP_BYTES = 64 << 20                  # --dump-outputs: at most this much in all (a seeded sample beyond it)
 OTHER_STEPS, OTHER_WARMUP = 20, 5      # timed steps / warm-up of each `other_configs` block (0.6 - 1.2 s regions: barrier skew at N > 1 stays < 1 %)
 # BASELINE.json configs[1..4]: (images per GPU, side, compute mode, label)
 CONFIGS = {
@@ -111,16 +119,22 @@ def parse_args(argv=None):
     ap.add_argument("--compute", default="", choices=[""] + list(MODES),
                     help="arithmetic of the contraction kernels (include/birefnet_hip.h brn_dtype; overrides --config)")
     ap.add_argument("--strong", action="store_true", help="strong scaling: the config's 8-GPU global batch (images/GPU x 8) is split over the ranks")
-    ap.add_argument("--also", default=None, help="comma list of other compute modes to time briefly on rank 0 at N=1 ('' = none; default: f32_split3,f32_split2,f32,f16 for c2)")
-    ap.add_argument("--profile-steps", type=int, default=2, help="extra steps with per-launch HIP events for the roofline block")
-    ap.add_argument("--cpu-baseline", default="auto", choices=["auto", "off", "on"])
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the logits of the last timed step to DIR (see the module docstring)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the roofline, CPU baseline, other modes / configurations and golden-error legs (a plain run only times the steps)")
+    ap.add_argument("--also", default=None, help="comma list of other compute modes to time briefly on rank 0 at N=1 ('' = none; default with --full: f32_split3,f32_split2,f32,f16 for c2)")
+    ap.add_argument("--profile-steps", type=int, default=None, help="extra steps with per-launch HIP events for the roofline block (default: 2 with --full, else 0)")
+    ap.add_argument("--cpu-baseline", default="auto", choices=["auto", "off", "on"], help="auto: with --full")
     ap.add_argument("--other-configs", default="auto", choices=["auto", "off", "on"],
-                    help="time the other BASELINE configurations in the same run (auto: with the default c2 line)")
-    ap.add_argument("--mask-error", default="on", choices=["on", "off"],
-                    help="one extra forward() of image 0 after the timed region for the mask-space error (off: rocprofv3 passes count only the timed forwards)")
+                    help="time the other BASELINE configurations in the same run (auto: with --full on the default c2 line)")
+    ap.add_argument("--mask-error", default="auto", choices=["auto", "on", "off"],
+                    help="one extra forward() of image 0 after the timed region for the mask-space error (auto: with --full; off: rocprofv3 passes count only the timed forwards)")
     ap.add_argument("--cpu-baseline-size", type=int, default=0, help="image side for the CPU sample (0 = the workload's side, capped at 1024)")
     ap.add_argument("--cpu-torch-worker", type=int, default=0, help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ---- N>1 without torch.distributed.run: start the ranks from a process that has not touched HIP ---------------------------
@@ -214,6 +228,25 @@ def golden_error(y, S, deform_mode, mask=False):
     if mask:
         g = 1.0 / (1.0 + np.exp(-g))
     return float(np.abs(yn - g).max())
+
+
+def dump_outputs(y, out_dir, name, max_bytes):
+    """--dump-outputs: y (what forward_logits returned in the last timed step) as out_dir/<name>.npy in float32.  Over max_bytes,
+    a fixed sample instead: the elements at max_bytes / 4 flat indices drawn without replacement by numpy seed 0, in index order
+    (the same indices for the same shape in every run)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    flat = y.detach().float().reshape(-1)
+    k = max_bytes // 4
+    if flat.numel() > k:
+        idx = np.sort(np.random.default_rng(0).choice(flat.numel(), size=k, replace=False))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+        arr = flat.cpu().numpy()
+    else:
+        arr = flat.cpu().numpy().reshape(tuple(y.shape))
+    np.save(os.path.join(out_dir, f"{name}.npy"), arr)
+    log(f"dump: {name}.npy {arr.shape} float32 -> {out_dir}")
 
 
 def profile_model(model, x, n):
@@ -311,8 +344,12 @@ def main(argv=None):
         B, scaling = gb // world, "strong"
     custom = (B, S, compute) != (cB, cS, cmode) and not args.strong
     default_line = args.config == "c2" and not custom and not args.strong and args.deform_mode == "reference_cpu"
-    also = args.also if args.also is not None else ("f32_split3,f32_split2,f32,f16" if (args.config == "c2" and not custom) else "")
-    others_on = args.other_configs == "on" or (args.other_configs == "auto" and default_line)
+    # everything beyond the timed steps runs with --full, or when its own option asks for it explicitly
+    also = args.also if args.also is not None else ("f32_split3,f32_split2,f32,f16" if (args.full and args.config == "c2" and not custom) else "")
+    others_on = args.other_configs == "on" or (args.other_configs == "auto" and args.full and default_line)
+    profile_steps = args.profile_steps if args.profile_steps is not None else (2 if args.full else 0)
+    cpu_on = args.cpu_baseline == "on" or (args.cpu_baseline == "auto" and args.full)
+    mask_on = args.mask_error == "on" or (args.mask_error == "auto" and args.full)
 
     import numpy as np
     import torch
@@ -383,16 +420,20 @@ def main(argv=None):
     if rank == 0:
         log(f"building model ({compute}, B={B}, {S}x{S}, {args.deform_mode}); warmup {args.warmup} + {args.steps} timed steps")
     elapsed, per_rank, cfg, model, x, y = timed_workload(B, S, compute, args.deform_mode, args.steps, args.warmup)
+    if rank == 0:
+        log(f"timed region done: {elapsed / args.steps * 1e3:.3f} ms/step")
+    if args.dump_outputs:
+        dump_outputs(y, args.dump_outputs, "logits" if world == 1 else f"logits_rank{rank}", DUMP_BYTES // world)
     weights = get_weights(cfg)
     finite = bool(torch.isfinite(y).all().item())
 
     # ---- roofline of the dominant kernel family (the GEMM kernels), per-launch HIP events on the launch stream ----
     roof = None
     stage_ms = None
-    if rank == 0 and args.profile_steps > 0:
-        log(f"timed region done: {elapsed / args.steps * 1e3:.3f} ms/step; profiling {args.profile_steps} step(s)")
-        fam, stage_ms = profile_model(model, x, args.profile_steps)
-        roof = roofline_block(fam, args.profile_steps, compute, f"{args.config}{'_deformable' if args.deform_mode == 'deformable' else ''}_{compute}",
+    if rank == 0 and profile_steps > 0:
+        log(f"profiling {profile_steps} step(s)")
+        fam, stage_ms = profile_model(model, x, profile_steps)
+        roof = roofline_block(fam, profile_steps, compute, f"{args.config}{'_deformable' if args.deform_mode == 'deformable' else ''}_{compute}",
                               not custom)
     barrier()
 
@@ -402,7 +443,7 @@ def main(argv=None):
     cpu = None
     ref = None
     cs = args.cpu_baseline_size or min(S, 1024)
-    if rank == 0 and world == 1 and args.cpu_baseline != "off":
+    if rank == 0 and world == 1 and cpu_on:
         from oracle import oracle as orc
         xs = cb.synth_input(1, cs, cs, seed0=1000)
         g_img = GFLOP_PER_IMAGE.get(cs, 0.0) - (GFLOP_OFFSET_MOD_1024 * (cs / 1024) ** 2 if args.deform_mode == "reference_cpu" else 0.0)
@@ -465,9 +506,9 @@ def main(argv=None):
                 others[mode]["gpu_vs_oracle_max_abs_err"] = float(e2.max())
                 others[mode]["gpu_vs_oracle_gate_1e-3abs_or_1e-2rel"] = bool(((e2 <= 1e-3) | (e2 <= 1e-2 * np.abs(ref_np))).all())
             m2.close()
-    gold_headline = golden_error(y, S, args.deform_mode) if (rank == 0 and not custom) else None
+    gold_headline = golden_error(y, S, args.deform_mode) if (rank == 0 and not custom and args.full) else None
     # mask space: forward() = sigmoid(logits) (birefnet.rs:466-469) of image 0 against sigmoid(golden logits)
-    gold_mask_headline = golden_error(model.forward(x[:1]), S, args.deform_mode, mask=True) if (rank == 0 and not custom and args.mask_error == "on") else None
+    gold_mask_headline = golden_error(model.forward(x[:1]), S, args.deform_mode, mask=True) if (rank == 0 and not custom and mask_on) else None
     model.close()
     del model, x, y
 

@@ -185,7 +185,7 @@ def test_bench_two_ranks_reports_c4_blocks(gpu):
     self-launcher, the rendezvous, shard_range, per-rank times, and the c4 / c4_deformable blocks of the default line."""
     import json
     import subprocess
-    pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--cpu-baseline", "off"],
+    pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--cpu-baseline", "off", "--full"],
                         env=dict(os.environ, BRN_BENCH_DIST_BACKEND="gloo"), capture_output=True, text=True, timeout=900)
     assert pr.returncode == 0, pr.stderr[-2000:]
     lines = [l for l in pr.stdout.splitlines() if l.startswith("{")]
@@ -199,6 +199,39 @@ def test_bench_two_ranks_reports_c4_blocks(gpu):
         assert blk["outputs_finite"] and blk["max_abs_err_image0_vs_strided_golden"] < BF16_ABS_BOUND["bf16"]
         assert blk["deform_mode"] == ("deformable" if k.endswith("deformable") else "reference_cpu")
         assert blk["roofline"]["families"]["gemm_deform_nhwc"]["launches"] == (20 if k.endswith("deformable") else 0)
+
+
+def test_bench_plain_run_dumps_last_step_logits(gpu, tmp_path):
+    """A plain bench run (no --full) times its steps and nothing else: the --full legs are absent from the line.  --dump-outputs
+    writes the logits of the last timed step, and they are what forward_logits returns for the bench's seeded input in this process;
+    a second run with the same arguments writes the same values (the property that lets two builds be compared output for output)."""
+    import json
+    import subprocess
+    import candle_birefnet_amd as cb
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--size", "64", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)],
+                            capture_output=True, text=True, timeout=600)
+        assert pr.returncode == 0, pr.stderr[-2000:]
+        lines = [l for l in pr.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["outputs_finite"]
+        assert line["roofline"] is None and line["cpu_baseline"] is None and line["other_modes"] is None and line["other_configs"] is None
+        assert line["max_abs_err_mask_image0"] is None
+        assert sorted(os.listdir(d)) == ["logits.npy"]
+        y = np.load(d / "logits.npy")
+        assert y.dtype == np.float32 and y.shape == (1, 1, 64, 64)
+        dumps.append(y)
+    np.testing.assert_array_equal(dumps[0], dumps[1])
+    import torch
+    cfg = cb.BiRefNetConfig()
+    m = cb.BiRefNet.new(cfg, cb.VarBuilder.from_tensors(cb.synth_weights(cb.birefnet_weight_spec(cfg), seed=42)), device=0, max_batch=1,
+                        max_size=(64, 64), compute="f32_half2")
+    y = m.forward_logits(torch.from_numpy(cb.synth_input(1, 64, 64, seed0=1000)).cuda())
+    np.testing.assert_array_equal(y.cpu().numpy(), dumps[0])
+    m.close()
 
 
 def test_bf16_ragged_token_count_against_oracle(gpu):

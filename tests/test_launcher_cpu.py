@@ -59,3 +59,36 @@ def test_bench_config_table_names_every_gpu_baseline_config():
         assert f"{S}×{S}" in base[idx] and (("bf16" in base[idx]) == (mode == "bf16")) and f"configs[{idx}]" in label
     a = bench.parse_args(["--config", "c5", "--gpus", "1"])
     assert a.config == "c5" and a.batch == 0 and a.size == 0 and a.compute == ""
+
+
+def test_bench_plain_run_and_full_options():
+    """a plain run carries only the timed steps: --full is off by default, the legs it adds default to off without it, and --steps
+    is the number of timed steps (at least one)"""
+    import pytest
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None and a.profile_steps is None and a.also is None
+    assert a.cpu_baseline == "auto" and a.other_configs == "auto" and a.mask_error == "auto"
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
+def test_bench_dump_outputs_whole_and_seeded_sample(tmp_path):
+    """--dump-outputs writes the whole array as float32 under the size cap, and over it the same fixed sample in every run"""
+    import numpy as np
+    import torch
+    import bench
+    y = torch.arange(2 * 1 * 8 * 8, dtype=torch.float32).reshape(2, 1, 8, 8) * 0.5
+    bench.dump_outputs(y, str(tmp_path / "a"), "logits", 1 << 20)
+    whole = np.load(tmp_path / "a" / "logits.npy")
+    assert whole.dtype == np.float32 and whole.shape == (2, 1, 8, 8)
+    np.testing.assert_array_equal(whole, y.numpy())
+    for d in ("b", "c"):
+        bench.dump_outputs(y, str(tmp_path / d), "logits", 40 * 4)
+    s1, s2 = np.load(tmp_path / "b" / "logits.npy"), np.load(tmp_path / "c" / "logits.npy")
+    assert s1.dtype == np.float32 and s1.shape == (40,) and len(set(s1.tolist())) == 40
+    np.testing.assert_array_equal(s1, s2)
+    assert np.all(np.diff(s1) > 0) and np.isin(s1, y.numpy()).all()

@@ -15,7 +15,7 @@ for rep in range(2):
             if "=" in kv:
                 k, v = kv.split("=", 1)
                 env[k] = v
-        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--cpu-baseline", "off", "--also", "", "--steps", "10", "--warmup", "3"] + extra,
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--cpu-baseline", "off", "--also", "", "--steps", "10", "--warmup", "3"] + extra,
                            env=env, capture_output=True, text=True)
         try:
             d = json.loads(p.stdout.strip().splitlines()[-1])
