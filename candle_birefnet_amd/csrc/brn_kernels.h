@@ -60,6 +60,10 @@ struct GemmPlan { int cfg; int splitk; size_t ws_floats; };   // cfg: 0 = 128x12
 GemmPlan plan_gemm(int M, int N, int K, int planes = 0);   // planes: bf16 planes of the split modes (0 = fp32 kernels)
 // ws: plan.ws_floats floats of scratch when plan.splitk > 1.  Returns the hipError_t of the launch(es).
 hipError_t launch_gemm(const GemmParams& p, const GemmPlan& plan, float* ws, hipStream_t s);
+// the split-bf16 path of launch_gemm (kernels/gemm_split.hip; p as launch_gemm validated it): dispatch over p.planes and the plan's tile.
+// Plan configs 0 and 3..6 run on the warp-specialised 128x128 kernel, 1 and 2 on the 4-wave 128x64 / 64x64 tiles.
+inline bool gemm_split_is_ws(int cfg) { return cfg == 6 || cfg == 0 || cfg == 3 || cfg == 4 || cfg == 5; }
+hipError_t launch_gemm_split(const GemmParams& p, int cfg, hipStream_t s);
 
 // CUs the persistent grids (gemm_bf16_kernel, gemm_wstat_*) are sized for on the calling host thread: 256 unless the launch stream carries a CU mask
 int launch_cus();

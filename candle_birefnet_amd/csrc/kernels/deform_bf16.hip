@@ -21,7 +21,7 @@
 // Bound: the gather (4 x 128 bytes per pixel and K step from L1 / L2) and its VALU work, not the matrix pipe: per K step a wave
 // issues 32 MFMAs (512 matrix-pipe cycles) beside ~230 vector instructions.
 #include "../brn_kernels.h"
-#include "split_planes.h"
+#include "gemm_common.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -82,12 +82,7 @@ __global__ void __launch_bounds__(256, 2) gemm_deform_bf16_kernel(const GemmPara
 
     // XCD-aware tile order (bijective): the workgroups that share an L2 walk a contiguous run of pixel tiles (neighbouring image rows)
     const int tilesM = (p.M + DBM - 1) / DBM, tilesN = (p.N + DBN - 1) / DBN;
-    int swz;
-    {
-        const int nwg = gridDim.x, orig = blockIdx.x;
-        const int xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
-        swz = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-    }
+    const int swz = xcd_remap();
     const int tile_n = swz / tilesM, tile_m = swz - tile_n * tilesM;     // (tilesN is 1 for the ASPP modules)
     const int m0 = tile_m * DBM, n0 = tile_n * DBN;
     (void)tilesN;
@@ -267,12 +262,7 @@ __global__ void __launch_bounds__(256, 2) gemm_deform_bf16_v2_kernel(const GemmP
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int tilesM = (p.M + DBM - 1) / DBM;
-    int swz;
-    {
-        const int nwg = gridDim.x, orig = blockIdx.x;
-        const int xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
-        swz = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-    }
+    const int swz = xcd_remap();
     const int tile_n = swz / tilesM, tile_m = swz - tile_n * tilesM;
     const int m0 = tile_m * DBM, n0 = tile_n * DBN;
     const int hw = p.Hout * p.Wout;

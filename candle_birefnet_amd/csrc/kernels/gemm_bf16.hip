@@ -19,7 +19,7 @@
 //   * a wave's instructions are i = w + NW j, so a lane's (row parity, chunk) is the same for all of them: the implicit-GEMM
 //     mode tracks ONE (tap, channel) per lane per K step, by increments (no division in the loop).
 #include "../brn_kernels.h"
-#include "split_planes.h"
+#include "gemm_common.h"
 #include <type_traits>
 
 // The file is compiled twice (Makefile): as is for compute mode BRN_BF16, and with -DBRN_S16_F16=1 for BRN_F16 — the same kernels with fp16
@@ -45,9 +45,6 @@ typedef s16_t s16x8 __attribute__((ext_vector_type(8)));
 #define BRN_S16_SELF(FN) FN
 #endif
 
-typedef float f32x16_b __attribute__((ext_vector_type(16)));
-typedef float f32x4_b __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4_b __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2_b __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {      // v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32 (round to nearest even): lo in bits 0-15
@@ -77,54 +74,6 @@ __device__ __attribute__((aligned(16))) unsigned g_zero_page[64];   // 256 zero 
 
 constexpr int BBK_PAD = 64;          // W rows and the K tail are zero-padded to this (the larger of the two K steps built)
 
-__device__ __forceinline__ float gelu_erf_b(float x) {   // same fit as gemm_f32.hip (|error| < 2e-7)
-    const float s = fabsf(x) * 0.70710678118654752440f;
-    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, s, 1.0f));
-    float q = -0.29582387555232f;
-    q = fmaf(q, t, 1.4920114662361241f);
-    q = fmaf(q, t, -2.0596673810742456f);
-    q = fmaf(q, t, 2.012361787754068f);
-    q = fmaf(q, t, -0.7324354234987704f);
-    q = fmaf(q, t, 0.42581723346182204f);
-    q = fmaf(q, t, 0.15773620453694617f);
-    q = q * t * __expf(-s * s);
-    const float one_plus_erf = x < 0.f ? q : 2.0f - q;
-    return 0.5f * x * one_plus_erf;
-}
-
-// gelu_erf for a result that is rounded to bf16 right away (flavour 0; the weight-stationary kernels).  fc1's epilogue is VALU time the
-// persistent workgroup cannot hide behind MFMAs (20 % of an fc1 launch with the round-2 form: erfc by Abramowitz-Stegun 7.1.25, 3 terms =
-// 9 VALU + v_rcp + v_exp, |error| < 2.6e-5), so the form is chosen by issue slots.  Round 4:
-//     gelu(x) = relu(x) - |x| h(|x|),   h(u) = erfc(u / sqrt 2) / 2 = 2^P(u)
-// with P a degree-5 polynomial: log2 of the Gaussian tail is almost a parabola (P(u) ~ -1 - 1.15 u - 0.46 u^2 ...), which one v_exp_f32
-// undoes — ONE transcendental instead of two, 1 clamp + 5 fma + v_exp + max + fma = 12 issue slots instead of 17, and a better fit:
-// weighted least squares on [0, 8] (weights = the tolerance budget below; coefficients rounded to fp32 and the whole form re-evaluated in
-// emulated fp32 over 5e6 points of [-40, 40]): |gelu error| < 3.0e-6 absolute and < 5.2e-5 relative for |gelu| >= 1e-2 — a hundredth of
-// half a bf16 ulp (a fifth of half an fp16 ulp: the fp16 build, compute mode BRN_F16, keeps the form).  Beyond u = 8 the clamp holds h at
-// 2^-51.9: |x| h is below 1e-7 for every |x| < 1e9.
-__device__ __forceinline__ float gelu_erf_bf16out(float x) {
-    const float ax = fabsf(x);
-    float u, r;
-    asm("v_min_f32 %0, |%1|, %2" : "=v"(u) : "v"(x), "v"(8.0f));         // (plain v_min / v_max: fminf / fmaxf put a canonicalising
-    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(0.0f));           // v_max x, x in front of each; x is an MFMA / fma result, never signalling)
-    float p = -0.00040414920658804476f;
-    p = fmaf(p, u, 0.006561775226145983f);
-    p = fmaf(p, u, -0.050444595515728f);
-    p = fmaf(p, u, -0.46150773763656616f);
-    p = fmaf(p, u, -1.150171160697937f);
-    p = fmaf(p, u, -1.0000925064086914f);
-    return fmaf(-ax, __builtin_amdgcn_exp2f(p), r);
-}
-
-__device__ __forceinline__ void bf16_tile_coords(int tile, int tilesM, int tilesN, int& tm, int& tn) {
-    constexpr int GN = 8;            // N walked in groups of 8 tile columns, M fastest-but-one inside a group (L2 reuse of the W panels)
-    const int per_group = tilesM * GN;
-    const int g = tile / per_group, r = tile - g * per_group;
-    const int gw = min(GN, tilesN - g * GN);
-    tm = r / gw;
-    tn = g * GN + (r - tm * gw);
-}
-
 template <int I, int N, class F> __device__ __forceinline__ void static_for(F&& f) {
     if constexpr (I < N) { f(std::integral_constant<int, I>{}); static_for<I + 1, N>(f); }
 }
@@ -152,7 +101,6 @@ __device__ __forceinline__ void blds16(__amdgpu_buffer_rsrc_t rsrc, unsigned vof
 }
 template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
-__device__ __forceinline__ f32x4_b zero4b() { f32x4_b z = {0.f, 0.f, 0.f, 0.f}; return z; }
 __device__ __forceinline__ float bf16_bits_to_f32(unsigned short h) { return s16_lo_f32((unsigned)h); }
 
 // 8 consecutive outputs of one row: everything of the epilogue after the accumulator
@@ -169,7 +117,7 @@ __device__ __forceinline__ void store_row8(const GemmParams& p, int m, int n, fl
         float t = v[e] + bias[e];
         if (p.scale) t = t * sc[e] + sh[e];
         if (p.act == ACT_RELU) t = fmaxf(t, 0.f);
-        else if (p.act == ACT_GELU_ERF) t = gelu_erf_b(t);
+        else if (p.act == ACT_GELU_ERF) t = gelu_erf_as(t);
         v[e] = t;
     }
     if (p.R) {
@@ -180,7 +128,7 @@ __device__ __forceinline__ void store_row8(const GemmParams& p, int m, int n, fl
         } else {
             const unsigned short* rp = reinterpret_cast<const unsigned short*>(p.R) + (long)m * p.ldr + p.r_coff + n;
             if (VEC) {
-                const u32x4_b r = *reinterpret_cast<const u32x4_b*>(rp);
+                const u32x4 r = *reinterpret_cast<const u32x4*>(rp);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     v[2 * e] += s16_lo_f32(r[e]);
@@ -195,9 +143,9 @@ __device__ __forceinline__ void store_row8(const GemmParams& p, int m, int n, fl
     if (p.c_f32) {
         float* dst = p.C + (long)m * p.ldc + p.c_coff + n;
         if (VEC) {
-            f32x4_b a = {v[0], v[1], v[2], v[3]}, b = {v[4], v[5], v[6], v[7]};
-            *reinterpret_cast<f32x4_b*>(dst) = a;
-            *reinterpret_cast<f32x4_b*>(dst + 4) = b;
+            f32x4 a = {v[0], v[1], v[2], v[3]}, b = {v[4], v[5], v[6], v[7]};
+            *reinterpret_cast<f32x4*>(dst) = a;
+            *reinterpret_cast<f32x4*>(dst + 4) = b;
         } else {
 #pragma unroll
             for (int e = 0; e < 8; ++e) if (n + e < p.N) dst[e] = v[e];
@@ -244,7 +192,7 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_bf16_kernel(const GemmParams
     constexpr int LA = BM / RPI / NW, LB = BN / RPI / NW;       // load instructions per wave and stage (A, W)
     static_assert(BBK == 64 || BBK == 32, "K step");
     static_assert(BM % (RPI * NW) == 0 && BN % (RPI * NW) == 0 && TM >= 1 && TN >= 1, "tile does not divide over the waves");
-    static_assert(MODE == GEMM_DENSE || MODE == GEMM_CONV_NHWC, "register-staged loaders live in gemm_f32.hip");
+    static_assert(MODE == GEMM_DENSE || MODE == GEMM_CONV_NHWC, "register-staged loaders live in gemm_f32.hip / gemm_split.hip");
     static_assert(NSTAGE >= 2 && NSTAGE <= 4, "ring depth");
     constexpr int LPS = LA + LB;                                // vmcnt units per stage and wave
     constexpr int A_BYTES = BM * ROWB, STAGE_BYTES = (BM + BN) * ROWB;
@@ -274,9 +222,8 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_bf16_kernel(const GemmParams
     const int ntiles = tilesM * tilesN, total = ntiles * p.splitk;
     int id, id_end, id_step;
     {
-        const int xcd = blockIdx.x & 7, q = total >> 3, r = total & 7;
-        const int cs = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-        id_end = cs + q + (xcd < r ? 1 : 0);
+        const int xcd = blockIdx.x & 7, cs = xcd_run_start(xcd, total);
+        id_end = cs + (total >> 3) + (xcd < (total & 7) ? 1 : 0);
         id_step = ((int)gridDim.x - xcd + 7) >> 3;               // workgroups of this launch on the same XCD
         id = cs + ((int)blockIdx.x >> 3);
     }
@@ -324,7 +271,7 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_bf16_kernel(const GemmParams
         slice = work / ntiles;
         const int tile = work - slice * ntiles;
         int tile_m, tile_n;
-        bf16_tile_coords(tile, tilesM, tilesN, tile_m, tile_n);
+        tile_coords(tile, tilesM, tilesN, tile_m, tile_n);
         m0 = tile_m * BM; n0 = tile_n * BN;
         kt0 = slice * kts;
         const int nk = min(nk_all, kt0 + kts);
@@ -433,7 +380,7 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_bf16_kernel(const GemmParams
     }
     bool counted = false;        // the previous item's epilogue issued exactly STORES stores per wave after this item's first loads
     while (have) {
-        typename std::conditional<M16, f32x4_b, f32x16_b>::type acc[FM][FN];
+        typename std::conditional<M16, f32x4, f32x16>::type acc[FM][FN];
 #pragma unroll
         for (int i = 0; i < FM; ++i)
 #pragma unroll
@@ -585,7 +532,7 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_bf16_kernel(const GemmParams
                 constexpr bool SCALE = decltype(scale_c)::value, FULL = decltype(full_c)::value;
                 // rounds r = jb * TM + i; flavour 1 keeps ONE round of fp32 residual rows in registers: the rows of pass ps of round r + 1
                 // are requested as soon as pass ps of round r has used its registers (the K loop has no registers to spare for more)
-                f32x4_b rres[PASSES][2];
+                f32x4 rres[PASSES][2];
                 auto load_res = [&](int r, int ps) {
                     const int jb = r / TM, i = r % TM;
                     const int n = e_n0 + wn * WTN + jb * EWN + ec;
@@ -594,8 +541,8 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_bf16_kernel(const GemmParams
                     const char* rp = reinterpret_cast<const char*>(p.R) + (mb * p.ldr + p.r_coff + (n - ec)) * 4 + (long)(ps * RPP) * p.ldr * 4 +
                                      (unsigned)(er * p.ldr + ec) * 4;
                     if (!ok) rp = reinterpret_cast<const char*>(g_zero_page);
-                    rres[ps][0] = *reinterpret_cast<const f32x4_b*>(rp);
-                    rres[ps][1] = *reinterpret_cast<const f32x4_b*>(rp + 16);
+                    rres[ps][0] = *reinterpret_cast<const f32x4*>(rp);
+                    rres[ps][1] = *reinterpret_cast<const f32x4*>(rp + 16);
                 };
                 const bool has_res1 = EPI == 1 && p.R != nullptr;
                 if (has_res1) {
@@ -607,11 +554,11 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_bf16_kernel(const GemmParams
                     const int n = e_n0 + wn * WTN + jb * EWN + ec;   // this lane's 8 columns after the read-back
                     const bool nin = FULL || n < p.N;
                     const int nl = nin ? n : 0;
-                    f32x4_b bias0 = zero4b(), bias1 = zero4b(), sc0, sc1, sh0, sh1;
-                    if (EPI != 2 && p.bias) { bias0 = *reinterpret_cast<const f32x4_b*>(p.bias + nl); bias1 = *reinterpret_cast<const f32x4_b*>(p.bias + nl + 4); }
+                    f32x4 bias0 = zero4(), bias1 = zero4(), sc0, sc1, sh0, sh1;
+                    if (EPI != 2 && p.bias) { bias0 = *reinterpret_cast<const f32x4*>(p.bias + nl); bias1 = *reinterpret_cast<const f32x4*>(p.bias + nl + 4); }
                     if (EPI != 2 && SCALE) {
-                        sc0 = *reinterpret_cast<const f32x4_b*>(p.scale + nl); sc1 = *reinterpret_cast<const f32x4_b*>(p.scale + nl + 4);
-                        sh0 = *reinterpret_cast<const f32x4_b*>(p.shift + nl); sh1 = *reinterpret_cast<const f32x4_b*>(p.shift + nl + 4);
+                        sc0 = *reinterpret_cast<const f32x4*>(p.scale + nl); sc1 = *reinterpret_cast<const f32x4*>(p.scale + nl + 4);
+                        sh0 = *reinterpret_cast<const f32x4*>(p.shift + nl); sh1 = *reinterpret_cast<const f32x4*>(p.shift + nl + 4);
                     }
                     // per-lane byte offsets inside a pass (32-bit) on top of uniform row pointers
                     const unsigned coff = (unsigned)(er * p.ldc + ec) * esz, roff = (unsigned)(er * p.ldr + ec) * 2;
@@ -626,15 +573,15 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_bf16_kernel(const GemmParams
                             for (int ii = 0; ii < 2; ++ii)
 #pragma unroll
                                 for (int jj = 0; jj < EWN / 16; ++jj)
-                                    *reinterpret_cast<f32x4_b*>(wbase + ii * (16 * EWN * 4) + (((jj * 4) ^ wt) << 4)) = acc[2 * i + ii][jb * (EWN / 16) + jj];
+                                    *reinterpret_cast<f32x4*>(wbase + ii * (16 * EWN * 4) + (((jj * 4) ^ wt) << 4)) = acc[2 * i + ii][jb * (EWN / 16) + jj];
                         } else {
 #pragma unroll
                             for (int jj = 0; jj < EWN / 32; ++jj)
 #pragma unroll
                                 for (int g = 0; g < 4; ++g) {
                                     const auto& c = acc[i][jb * (EWN / 32) + jj];
-                                    const f32x4_b v = {c[4 * g], c[4 * g + 1], c[4 * g + 2], c[4 * g + 3]};
-                                    *reinterpret_cast<f32x4_b*>(wbase + (((jj * 8 + 2 * g) ^ wt) << 4)) = v;
+                                    const f32x4 v = {c[4 * g], c[4 * g + 1], c[4 * g + 2], c[4 * g + 3]};
+                                    *reinterpret_cast<f32x4*>(wbase + (((jj * 8 + 2 * g) ^ wt) << 4)) = v;
                                 }
                         }
                         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -644,8 +591,8 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_bf16_kernel(const GemmParams
                             const int row = ps * RPP + er;
                             const int sw = row & CM;
                             const char* rb = wpatch + row * (EWN * 4);
-                            const f32x4_b v0 = *reinterpret_cast<const f32x4_b*>(rb + ((((ec >> 2)) ^ sw) << 4));
-                            const f32x4_b v1 = *reinterpret_cast<const f32x4_b*>(rb + ((((ec >> 2) + 1) ^ sw) << 4));
+                            const f32x4 v0 = *reinterpret_cast<const f32x4*>(rb + ((((ec >> 2)) ^ sw) << 4));
+                            const f32x4 v1 = *reinterpret_cast<const f32x4*>(rb + ((((ec >> 2) + 1) ^ sw) << 4));
                             const bool ok = FULL || (mb + row < p.M && nin);
                             if constexpr (EPI == 2) {                // everything else: per element, correct, not fast
                                 if (ok) {
@@ -669,11 +616,11 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_bf16_kernel(const GemmParams
                                 }
                                 continue;
                             }
-                            f32x4_b a = v0 + bias0, b = v1 + bias1;
+                            f32x4 a = v0 + bias0, b = v1 + bias1;
                             if (EPI == 0 && p.bbias) {               // per-image bias (the pooled ASPP branch folded into conv1)
                                 const long m = ok ? mb + row : 0;
                                 const float* bp = p.bbias + (m / p.bbias_rows) * p.N + nl;
-                                a = a + *reinterpret_cast<const f32x4_b*>(bp); b = b + *reinterpret_cast<const f32x4_b*>(bp + 4);
+                                a = a + *reinterpret_cast<const f32x4*>(bp); b = b + *reinterpret_cast<const f32x4*>(bp + 4);
                             }
                             if (SCALE) { a = a * sc0 + sh0; b = b * sc1 + sh1; }
                             if (ACT == ACT_RELU) {
@@ -682,26 +629,26 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_bf16_kernel(const GemmParams
                             } else if (ACT == ACT_GELU_ERF) {
 #pragma unroll
                                 for (int e = 0; e < 4; ++e) {
-                                    a[e] = EPI == 0 ? gelu_erf_bf16out(a[e]) : gelu_erf_b(a[e]);
-                                    b[e] = EPI == 0 ? gelu_erf_bf16out(b[e]) : gelu_erf_b(b[e]);
+                                    a[e] = EPI == 0 ? gelu_erf_bf16out(a[e]) : gelu_erf_as(a[e]);
+                                    b[e] = EPI == 0 ? gelu_erf_bf16out(b[e]) : gelu_erf_as(b[e]);
                                 }
                             }
                             char* cp = cu + (long)(ps * RPP) * p.ldc * esz + coff;
                             if (EPI == 0) {
                                 if (p.R) {                           // bf16 residual (the decoder's lateral adds, in place)
                                     const char* rp = ru + (long)(ps * RPP) * p.ldr * 2 + roff;
-                                    const u32x4_b rr = *reinterpret_cast<const u32x4_b*>(ok ? rp : reinterpret_cast<const char*>(g_zero_page));
+                                    const u32x4 rr = *reinterpret_cast<const u32x4*>(ok ? rp : reinterpret_cast<const char*>(g_zero_page));
                                     a[0] += s16_lo_f32(rr[0]); a[1] += s16_hi_f32(rr[0]);
                                     a[2] += s16_lo_f32(rr[1]); a[3] += s16_hi_f32(rr[1]);
                                     b[0] += s16_lo_f32(rr[2]); b[1] += s16_hi_f32(rr[2]);
                                     b[2] += s16_lo_f32(rr[3]); b[3] += s16_hi_f32(rr[3]);
                                 }
-                                const u32x4_b o = {pack_bf16x2(a[0], a[1]), pack_bf16x2(a[2], a[3]), pack_bf16x2(b[0], b[1]), pack_bf16x2(b[2], b[3])};
+                                const u32x4 o = {pack_bf16x2(a[0], a[1]), pack_bf16x2(a[2], a[3]), pack_bf16x2(b[0], b[1]), pack_bf16x2(b[2], b[3])};
                                 if (!(abl & 16) || a[0] == 123.456f)  // diag bit 16: the epilogue without its stores
-                                if (ok) *reinterpret_cast<u32x4_b*>(cp) = o;
+                                if (ok) *reinterpret_cast<u32x4*>(cp) = o;
                             } else {
                                 if (has_res1) { a = a + rres[ps][0]; b = b + rres[ps][1]; }
-                                if (ok) { *reinterpret_cast<f32x4_b*>(cp) = a; *reinterpret_cast<f32x4_b*>(cp + 16) = b; }
+                                if (ok) { *reinterpret_cast<f32x4*>(cp) = a; *reinterpret_cast<f32x4*>(cp + 16) = b; }
                                 if (has_res1 && r + 1 < NJB * TM) load_res(r + 1, ps);
                             }
                         }
@@ -780,9 +727,9 @@ __global__ void __launch_bounds__(256, 2) gemm_wstat_bf16_kernel(const GemmParam
 #pragma unroll
             for (int ks = 0; ks < K32; ++ks) wfr[j][ks] = *reinterpret_cast<const s16x8*>(wf + (long)(j * K32 + ks) * 1024);
     }
-    f32x4_b bias[3];
+    f32x4 bias[3];
 #pragma unroll
-    for (int j = 0; j < 3; ++j) bias[j] = p.bias ? *reinterpret_cast<const f32x4_b*>(p.bias + n0 + 16 * j + 4 * (lane >> 4)) : zero4b();
+    for (int j = 0; j < 3; ++j) bias[j] = p.bias ? *reinterpret_cast<const f32x4*>(p.bias + n0 + 16 * j + 4 * (lane >> 4)) : zero4();
     // ---- this lane's share of an A tile: LDS-DMA instruction ii = wave + 4 j (j < NJ) of every sub-tile fills bank rows 4 ii .. 4 ii + 3 ----
     unsigned a_voff[NJ];
     int a_row[NJ];
@@ -817,11 +764,11 @@ __global__ void __launch_bounds__(256, 2) gemm_wstat_bf16_kernel(const GemmParam
         if (more) { issue(t + nw, smem + ((it + 1) & 1) * ABUF); wait_vmcnt<NJ * KS>(); }   // this tile (and the previous tile's stores) landed; the next one may be in flight
         else wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
-        f32x4_b acc[RF][3];
+        f32x4 acc[RF][3];
 #pragma unroll
         for (int i = 0; i < RF; ++i)
 #pragma unroll
-            for (int j = 0; j < 3; ++j) acc[i][j] = zero4b();
+            for (int j = 0; j < 3; ++j) acc[i][j] = zero4();
 #pragma unroll
         for (int ks = 0; ks < K32; ++ks) {
             s16x8 af[RF];
@@ -843,7 +790,7 @@ __global__ void __launch_bounds__(256, 2) gemm_wstat_bf16_kernel(const GemmParam
                 const int i = 2 * half + ii, row = 16 * ii + (lane & 15);          // row within the 32-row half
 #pragma unroll
                 for (int j = 0; j < 3; ++j) {
-                    f32x4_b v = acc[i][j] + bias[j];
+                    f32x4 v = acc[i][j] + bias[j];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         if (ACT == ACT_GELU_ERF) v[e] = gelu_erf_bf16out(v[e]);
@@ -859,9 +806,9 @@ __global__ void __launch_bounds__(256, 2) gemm_wstat_bf16_kernel(const GemmParam
 #pragma unroll
             for (int q = 0; q < 3; ++q) {                                // 32 rows x 24 chunks of 16 bytes over 256 threads
                 const int idx = tid + 256 * q, row = idx / 24, ch = idx - row * 24;
-                const u32x4_b v = *reinterpret_cast<const u32x4_b*>(buf + row * 512 + ((ch ^ (row & 31)) << 4));
+                const u32x4 v = *reinterpret_cast<const u32x4*>(buf + row * 512 + ((ch ^ (row & 31)) << 4));
                 const int m = m0 + half * 32 + row;
-                if (m < p.M) *reinterpret_cast<u32x4_b*>(Cb + (long)m * p.ldc + p.c_coff + grp * WBN + ch * 8) = v;
+                if (m < p.M) *reinterpret_cast<u32x4*>(Cb + (long)m * p.ldc + p.c_coff + grp * WBN + ch * 8) = v;
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();                               // the half (and, after the second one, the buffer) is free again
@@ -899,9 +846,9 @@ __global__ void __launch_bounds__(256, 2) gemm_wstat_ln_bf16_kernel(const GemmPa
 #pragma unroll
             for (int ks = 0; ks < K32; ++ks) wfr[j][ks] = *reinterpret_cast<const s16x8*>(wf + (long)(j * K32 + ks) * 1024);
     }
-    f32x4_b bias[3];
+    f32x4 bias[3];
 #pragma unroll
-    for (int j = 0; j < 3; ++j) bias[j] = p.bias ? *reinterpret_cast<const f32x4_b*>(p.bias + n0 + 16 * j + 4 * (lane >> 4)) : zero4b();
+    for (int j = 0; j < 3; ++j) bias[j] = p.bias ? *reinterpret_cast<const f32x4*>(p.bias + n0 + 16 * j + 4 * (lane >> 4)) : zero4();
     unsigned a_voff[2];
     int a_row[2];
 #pragma unroll
@@ -938,11 +885,11 @@ __global__ void __launch_bounds__(256, 2) gemm_wstat_ln_bf16_kernel(const GemmPa
         if (more) { issue(t + nw, smem + ((it + 1) & 1) * ABUF); wait_vmcnt<2 * KS>(); }
         else wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
-        f32x4_b acc[4][3];
+        f32x4 acc[4][3];
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int j = 0; j < 3; ++j) acc[i][j] = zero4b();
+            for (int j = 0; j < 3; ++j) acc[i][j] = zero4();
 #pragma unroll
         for (int ks = 0; ks < K32; ++ks) {
             s16x8 af[4];
@@ -959,31 +906,31 @@ __global__ void __launch_bounds__(256, 2) gemm_wstat_ln_bf16_kernel(const GemmPa
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             const int m = m0 + half * 32 + er, mc = min(m, p.M - 1);
-            f32x4_b rr[6];
+            f32x4 rr[6];
 #pragma unroll
-            for (int k = 0; k < 6; ++k) rr[k] = *reinterpret_cast<const f32x4_b*>(Rf + (long)mc * p.ldr + p.r_coff + (ec + 8 * k) * 4);
+            for (int k = 0; k < 6; ++k) rr[k] = *reinterpret_cast<const f32x4*>(Rf + (long)mc * p.ldr + p.r_coff + (ec + 8 * k) * 4);
 #pragma unroll
             for (int ii = 0; ii < 2; ++ii) {
                 const int i = 2 * half + ii, row = 16 * ii + (lane & 15);
 #pragma unroll
                 for (int j = 0; j < 3; ++j) {
                     const int ch = (wave * 48 + 16 * j + 4 * (lane >> 4)) >> 2;      // 16-byte chunk of the 768-byte row
-                    *reinterpret_cast<f32x4_b*>(buf + row * 768 + ((ch ^ (row & 7)) << 4)) = acc[i][j] + bias[j];
+                    *reinterpret_cast<f32x4*>(buf + row * 768 + ((ch ^ (row & 7)) << 4)) = acc[i][j] + bias[j];
                 }
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
-            f32x4_b xv[6];
+            f32x4 xv[6];
             float sum = 0.f;
 #pragma unroll
             for (int k = 0; k < 6; ++k) {
                 const int ch = ec + 8 * k;
-                xv[k] = *reinterpret_cast<const f32x4_b*>(buf + er * 768 + ((ch ^ (er & 7)) << 4)) + rr[k];
+                xv[k] = *reinterpret_cast<const f32x4*>(buf + er * 768 + ((ch ^ (er & 7)) << 4)) + rr[k];
                 sum += (xv[k][0] + xv[k][1]) + (xv[k][2] + xv[k][3]);
             }
             if (m < p.M) {
 #pragma unroll
-                for (int k = 0; k < 6; ++k) *reinterpret_cast<f32x4_b*>(Cf + (long)m * p.ldc + p.c_coff + (ec + 8 * k) * 4) = xv[k];
+                for (int k = 0; k < 6; ++k) *reinterpret_cast<f32x4*>(Cf + (long)m * p.ldc + p.c_coff + (ec + 8 * k) * 4) = xv[k];
             }
             sum += __shfl_xor(sum, 1); sum += __shfl_xor(sum, 2); sum += __shfl_xor(sum, 4);
             const float mean = sum / (float)WBN;
@@ -999,8 +946,8 @@ __global__ void __launch_bounds__(256, 2) gemm_wstat_ln_bf16_kernel(const GemmPa
 #pragma unroll
                 for (int k = 0; k < 6; ++k) {
                     const int c0 = (ec + 8 * k) * 4;
-                    const f32x4_b gm = *reinterpret_cast<const f32x4_b*>(gb_s + c0), bt = *reinterpret_cast<const f32x4_b*>(gb_s + WBN + c0);
-                    const f32x4_b o = xv[k] * rstd * gm + bt;
+                    const f32x4 gm = *reinterpret_cast<const f32x4*>(gb_s + c0), bt = *reinterpret_cast<const f32x4*>(gb_s + WBN + c0);
+                    const f32x4 o = xv[k] * rstd * gm + bt;
                     const u32x2_b ob = {pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3])};
                     *reinterpret_cast<u32x2_b*>(Y + (long)m * ldy + c0) = ob;
                 }
@@ -1073,11 +1020,11 @@ __global__ void __launch_bounds__(512) gemm_rowln_bf16_kernel(const GemmParams p
     if (t < t_hi) issue(t * RBM, 0, 2);                                  // K step kt lives in slot (kt + 2) % 3
     for (; t < t_hi; t += nw) {
         const int m0 = t * RBM;
-        f32x4_b acc[FM][FN];
+        f32x4 acc[FM][FN];
 #pragma unroll
         for (int i = 0; i < FM; ++i)
 #pragma unroll
-            for (int j = 0; j < FN; ++j) acc[i][j] = zero4b();
+            for (int j = 0; j < FN; ++j) acc[i][j] = zero4();
         if (nk > 1) issue(m0, 1, 0);
         for (int kt = 0; kt < nk; ++kt) {
             // this wave's pieces of step kt have landed when at most those of step kt + 1 are outstanding
@@ -1107,33 +1054,33 @@ __global__ void __launch_bounds__(512) gemm_rowln_bf16_kernel(const GemmParams p
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             const int m = m0 + half * 32 + er, mc = min(m, p.M - 1);
-            f32x4_b rr[CPL];
+            f32x4 rr[CPL];
 #pragma unroll
-            for (int k = 0; k < CPL; ++k) rr[k] = *reinterpret_cast<const f32x4_b*>(Rf + (long)mc * p.ldr + p.r_coff + (ec + 16 * k) * 4);
+            for (int k = 0; k < CPL; ++k) rr[k] = *reinterpret_cast<const f32x4*>(Rf + (long)mc * p.ldr + p.r_coff + (ec + 16 * k) * 4);
 #pragma unroll
             for (int ii = 0; ii < 2; ++ii) {
                 const int i = 2 * half + ii, row = 16 * ii + (lane & 15);
 #pragma unroll
                 for (int j = 0; j < FN; ++j) {
                     const int col = wave * WCOL + 16 * j + 4 * (lane >> 4);
-                    f32x4_b bias4 = p.bias ? *reinterpret_cast<const f32x4_b*>(p.bias + col) : zero4b();
+                    f32x4 bias4 = p.bias ? *reinterpret_cast<const f32x4*>(p.bias + col) : zero4();
                     const int ch = col >> 2;
-                    *reinterpret_cast<f32x4_b*>(smem + row * (NC * 4) + (((ch & ~15) | ((ch ^ row) & 15)) << 4)) = acc[i][j] + bias4;
+                    *reinterpret_cast<f32x4*>(smem + row * (NC * 4) + (((ch & ~15) | ((ch ^ row) & 15)) << 4)) = acc[i][j] + bias4;
                 }
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
-            f32x4_b xv[CPL];
+            f32x4 xv[CPL];
             float sum = 0.f;
 #pragma unroll
             for (int k = 0; k < CPL; ++k) {
                 const int ch = ec + 16 * k;
-                xv[k] = *reinterpret_cast<const f32x4_b*>(smem + er * (NC * 4) + (((ch & ~15) | ((ch ^ er) & 15)) << 4)) + rr[k];
+                xv[k] = *reinterpret_cast<const f32x4*>(smem + er * (NC * 4) + (((ch & ~15) | ((ch ^ er) & 15)) << 4)) + rr[k];
                 sum += (xv[k][0] + xv[k][1]) + (xv[k][2] + xv[k][3]);
             }
             if (m < p.M) {
 #pragma unroll
-                for (int k = 0; k < CPL; ++k) *reinterpret_cast<f32x4_b*>(Cf + (long)m * p.ldc + p.c_coff + (ec + 16 * k) * 4) = xv[k];
+                for (int k = 0; k < CPL; ++k) *reinterpret_cast<f32x4*>(Cf + (long)m * p.ldc + p.c_coff + (ec + 16 * k) * 4) = xv[k];
             }
             sum += __shfl_xor(sum, 1); sum += __shfl_xor(sum, 2); sum += __shfl_xor(sum, 4); sum += __shfl_xor(sum, 8);
             const float mean = sum / (float)NC;
@@ -1149,8 +1096,8 @@ __global__ void __launch_bounds__(512) gemm_rowln_bf16_kernel(const GemmParams p
 #pragma unroll
                 for (int k = 0; k < CPL; ++k) {
                     const int c0 = (ec + 16 * k) * 4;
-                    const f32x4_b gm = *reinterpret_cast<const f32x4_b*>(gamma + c0), bt = *reinterpret_cast<const f32x4_b*>(beta + c0);
-                    const f32x4_b o = xv[k] * rstd * gm + bt;
+                    const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + c0), bt = *reinterpret_cast<const f32x4*>(beta + c0);
+                    const f32x4 o = xv[k] * rstd * gm + bt;
                     const u32x2_b ob = {pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3])};
                     *reinterpret_cast<u32x2_b*>(Y + (long)m * ldy + c0) = ob;
                 }
@@ -1223,7 +1170,7 @@ __global__ void splitk_reduce_bf16_kernel(const GemmParams p) {
         if (p.bias) v += p.bias[n];
         if (p.scale) v = v * p.scale[n] + p.shift[n];
         if (p.act == ACT_RELU) v = fmaxf(v, 0.f);
-        else if (p.act == ACT_GELU_ERF) v = gelu_erf_b(v);
+        else if (p.act == ACT_GELU_ERF) v = gelu_erf_as(v);
         if (p.R) v += p.r_f32 ? p.R[(long)m * p.ldr + p.r_coff + n]
                               : bf16_bits_to_f32(reinterpret_cast<const unsigned short*>(p.R)[(long)m * p.ldr + p.r_coff + n]);
         if (p.c_f32) p.C[(long)m * p.ldc + p.c_coff + n] = v;

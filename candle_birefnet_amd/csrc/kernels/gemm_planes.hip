@@ -1,6 +1,6 @@
 // gemm_planes.hip — the split-bf16 contraction (compute modes f32_split3 / f32_split2) for operands that ALREADY exist as bf16
 // planes in HBM: A in the "P" activation layout its producer wrote (kernels/split_planes.h: LayerNorm, window attention, the fc1
-// epilogue), W in the interleaved plane layout built at load time.  Same arithmetic as gemm_split_ws_kernel (gemm_f32.hip): every
+// epilogue), W in the interleaved plane layout built at load time.  Same arithmetic as gemm_split_ws_kernel (gemm_split.hip): every
 // fp32 operand is NP bf16 planes (error-free for NP = 3), a product is the sum of the plane products down to 2^-16 of the leading
 // one (NP = 3: hh, hm, mh, hl, lh, mm; NP = 2: hh, hl, lh), smallest first, fp32 accumulation on v_mfma_f32_32x32x16_bf16.
 //
@@ -12,36 +12,17 @@
 // per CU, under the measured ~68 GB/s L2 -> LDS intake, i.e. the loop is MFMA-bound by construction.
 // Replaces candle_nn::linear of the Swin blocks (swin.rs:98-99,130-131) in the split modes; dense A only.
 #include "../brn_kernels.h"
-#include "split_planes.h"
+#include "gemm_common.h"
 
 namespace brn {
 
-typedef float f32x16_p __attribute__((ext_vector_type(16)));
-typedef float f32x4_p __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4_p __attribute__((ext_vector_type(4)));
-
 __device__ __attribute__((aligned(16))) unsigned g_zero_page_p[64];
 
-__device__ __forceinline__ float gelu_erf_p(float x) {   // same fit as gemm_f32.hip (|error| < 2e-7)
-    const float s = fabsf(x) * 0.70710678118654752440f;
-    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, s, 1.0f));
-    float q = -0.29582387555232f;
-    q = fmaf(q, t, 1.4920114662361241f);
-    q = fmaf(q, t, -2.0596673810742456f);
-    q = fmaf(q, t, 2.012361787754068f);
-    q = fmaf(q, t, -0.7324354234987704f);
-    q = fmaf(q, t, 0.42581723346182204f);
-    q = fmaf(q, t, 0.15773620453694617f);
-    q = q * t * __expf(-s * s);
-    const float one_plus_erf = x < 0.f ? q : 2.0f - q;
-    return 0.5f * x * one_plus_erf;
-}
 __device__ __forceinline__ void glds16p(const void* gsrc, void* lds_dst) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
                                      (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
 }
 template <int N> __device__ __forceinline__ void wait_vmcnt_p() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ f32x4_p zero4p() { f32x4_p z = {0.f, 0.f, 0.f, 0.f}; return z; }
 
 // EPI: 1 = fp32 C (+ bias, + fp32 residual)        3 = C in the P layout with NP planes (+ bias, + activation): fc1 -> fc2
 template <int BM, int BN, int WM, int WN, int NSTAGE, int NP, int EPI>
@@ -76,9 +57,8 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_planes_kernel(const GemmPara
     const int ntiles = tilesM * tilesN, total = ntiles * p.splitk;
     int id, id_end, id_step;
     {
-        const int xcd = blockIdx.x & 7, q = total >> 3, r = total & 7;
-        const int cs = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-        id_end = cs + q + (xcd < r ? 1 : 0);
+        const int xcd = blockIdx.x & 7, cs = xcd_run_start(xcd, total);
+        id_end = cs + (total >> 3) + (xcd < (total & 7) ? 1 : 0);
         id_step = ((int)gridDim.x - xcd + 7) >> 3;
         id = cs + ((int)blockIdx.x >> 3);
     }
@@ -111,12 +91,8 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_planes_kernel(const GemmPara
     auto setup = [&](int work) {
         slice = work / ntiles;
         const int tile = work - slice * ntiles;
-        // N walked in groups of 8 tile columns, M fastest-but-one inside a group (L2 reuse of the W panels)
-        constexpr int GN = 8;
-        const int per_group = tilesM * GN;
-        const int g = tile / per_group, r = tile - g * per_group;
-        const int gw = min(GN, tilesN - g * GN);
-        const int tile_m = r / gw, tile_n = g * GN + (r - tile_m * gw);
+        int tile_m, tile_n;
+        tile_coords(tile, tilesM, tilesN, tile_m, tile_n);
         m0 = tile_m * BM; n0 = tile_n * BN;
         kt0 = slice * kts;
         const int nk = min(nk_all, kt0 + kts);
@@ -159,7 +135,7 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_planes_kernel(const GemmPara
     }
     bool counted = false;
     while (have) {
-        f32x16_p acc[TM][TN];
+        f32x16 acc[TM][TN];
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -249,16 +225,16 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_planes_kernel(const GemmPara
 #pragma unroll
                 for (int hb = 0; hb < NB; ++hb) {
                     const long mb = rowbase + i * 32 + hb * PR;
-                    f32x4_p rres[PASSES][2];
+                    f32x4 rres[PASSES][2];
                     if (EPI == 1) {
 #pragma unroll
                         for (int ps = 0; ps < PASSES; ++ps) {
                             const long m = mb + ps * RPP + er;
-                            rres[ps][0] = zero4p(); rres[ps][1] = zero4p();
+                            rres[ps][0] = zero4(); rres[ps][1] = zero4();
                             if (!split && p.R && m < p.M && n < p.N) {
                                 const float* rp = p.R + m * p.ldr + p.r_coff + n;
-                                rres[ps][0] = *reinterpret_cast<const f32x4_p*>(rp);
-                                rres[ps][1] = *reinterpret_cast<const f32x4_p*>(rp + 4);
+                                rres[ps][0] = *reinterpret_cast<const f32x4*>(rp);
+                                rres[ps][1] = *reinterpret_cast<const f32x4*>(rp + 4);
                             }
                         }
                     }
@@ -277,21 +253,21 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_planes_kernel(const GemmPara
                         const int row = ps * RPP + er;
                         const long m = mb + row;
                         const int par = row & 1;
-                        f32x4_p v0 = *reinterpret_cast<const f32x4_p*>(patch + row * EWN + (((ec >> 2) ^ par) << 2));
-                        f32x4_p v1 = *reinterpret_cast<const f32x4_p*>(patch + row * EWN + ((((ec >> 2) + 1) ^ par) << 2));
+                        f32x4 v0 = *reinterpret_cast<const f32x4*>(patch + row * EWN + (((ec >> 2) ^ par) << 2));
+                        f32x4 v1 = *reinterpret_cast<const f32x4*>(patch + row * EWN + ((((ec >> 2) + 1) ^ par) << 2));
                         if (m >= p.M || n >= p.N) continue;
                         if (EPI == 1) {
                             if (split) {
                                 float* dst = part + m * p.N + n;
-                                *reinterpret_cast<f32x4_p*>(dst) = v0;
-                                *reinterpret_cast<f32x4_p*>(dst + 4) = v1;
+                                *reinterpret_cast<f32x4*>(dst) = v0;
+                                *reinterpret_cast<f32x4*>(dst + 4) = v1;
                                 continue;
                             }
 #pragma unroll
                             for (int e = 0; e < 4; ++e) { v0[e] += bias[e]; v1[e] += bias[4 + e]; }
                             if (act == ACT_GELU_ERF) {
 #pragma unroll
-                                for (int e = 0; e < 4; ++e) { v0[e] = gelu_erf_p(v0[e]); v1[e] = gelu_erf_p(v1[e]); }
+                                for (int e = 0; e < 4; ++e) { v0[e] = gelu_erf_as(v0[e]); v1[e] = gelu_erf_as(v1[e]); }
                             } else if (act == ACT_RELU) {
 #pragma unroll
                                 for (int e = 0; e < 4; ++e) { v0[e] = fmaxf(v0[e], 0.f); v1[e] = fmaxf(v1[e], 0.f); }
@@ -299,15 +275,15 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_planes_kernel(const GemmPara
                             v0 = v0 + rres[ps][0];
                             v1 = v1 + rres[ps][1];
                             float* dst = p.C + m * p.ldc + p.c_coff + n;
-                            *reinterpret_cast<f32x4_p*>(dst) = v0;
-                            *reinterpret_cast<f32x4_p*>(dst + 4) = v1;
+                            *reinterpret_cast<f32x4*>(dst) = v0;
+                            *reinterpret_cast<f32x4*>(dst + 4) = v1;
                         } else {
                             // P layout out: the 8 columns are one 16-byte chunk per plane of K tile (c_coff + n) / 32
 #pragma unroll
                             for (int e = 0; e < 4; ++e) { v0[e] += bias[e]; v1[e] += bias[4 + e]; }
                             if (act == ACT_GELU_ERF) {
 #pragma unroll
-                                for (int e = 0; e < 4; ++e) { v0[e] = gelu_erf_p(v0[e]); v1[e] = gelu_erf_p(v1[e]); }
+                                for (int e = 0; e < 4; ++e) { v0[e] = gelu_erf_as(v0[e]); v1[e] = gelu_erf_as(v1[e]); }
                             } else if (act == ACT_RELU) {
 #pragma unroll
                                 for (int e = 0; e < 4; ++e) { v0[e] = fmaxf(v0[e], 0.f); v1[e] = fmaxf(v1[e], 0.f); }
@@ -321,8 +297,8 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_planes_kernel(const GemmPara
                             for (int pl = 0; pl < NP; ++pl) {
                                 typedef unsigned u32x2_p __attribute__((ext_vector_type(2)));
                                 const u32x2_p lo = __builtin_bit_cast(u32x2_p, s0[pl]), hi = __builtin_bit_cast(u32x2_p, s1[pl]);
-                                u32x4_p o = {lo[0], lo[1], hi[0], hi[1]};
-                                *reinterpret_cast<u32x4_p*>(base + 64 * pl) = o;
+                                u32x4 o = {lo[0], lo[1], hi[0], hi[1]};
+                                *reinterpret_cast<u32x4*>(base + 64 * pl) = o;
                             }
                         }
                     }
@@ -343,7 +319,7 @@ __global__ void splitk_reduce_planes_kernel(const GemmParams p) {
         for (int s = 0; s < p.splitk; ++s) v += p.part[(long)s * total + idx];
         if (p.bias) v += p.bias[n];
         if (p.act == ACT_RELU) v = fmaxf(v, 0.f);
-        else if (p.act == ACT_GELU_ERF) v = gelu_erf_p(v);
+        else if (p.act == ACT_GELU_ERF) v = gelu_erf_as(v);
         if (p.R) v += p.R[(long)m * p.ldr + p.r_coff + n];
         p.C[(long)m * p.ldc + p.c_coff + n] = v;
     }

@@ -4,7 +4,7 @@
 
 namespace brn {
 
-typedef float f32x4_sp __attribute__((ext_vector_type(4)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
@@ -18,7 +18,7 @@ __device__ __forceinline__ float valu_and(float a, unsigned keep) { float r; asm
 __device__ __forceinline__ float valu_sub(float a, float b) { float r; asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ unsigned valu_cvt_pk_bf16(float a, float b) { unsigned r; asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 template <int NP, bool MASKED = true>   // MASKED = false: the caller's rows are all valid (or were zero-filled by the load): no AND
-__device__ __forceinline__ void split4(const f32x4_sp v, const unsigned keep, bf16x4 (&out)[NP]) {
+__device__ __forceinline__ void split4(const f32x4 v, const unsigned keep, bf16x4 (&out)[NP]) {
     typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
     float r[4];
 #pragma unroll
@@ -53,7 +53,7 @@ __device__ __forceinline__ void split_pair_h(const float x0, const float x1, con
     asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(lo) : "v"(t0), "v"(t1));
 }
 template <bool MASKED = true>
-__device__ __forceinline__ void split4h(const f32x4_sp v, const unsigned keep, const float s, bf16x4 (&out)[2]) {   // (bf16x4 = the 8-byte container)
+__device__ __forceinline__ void split4h(const f32x4 v, const unsigned keep, const float s, bf16x4 (&out)[2]) {   // (bf16x4 = the 8-byte container)
     typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
     float r[4];
 #pragma unroll
@@ -73,7 +73,7 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 // plane p at bytes [64 NP kt + 64 p, + 64).  NP = 2 is byte-for-byte the size of the fp32 row (ld unchanged); NP = 3 rows are
 // 1.5x as long (ld = 3K/2 floats).  `row` points at the row's first byte, `col` (a multiple of 4) is the logical column of v[0].
 template <int NP>
-__device__ __forceinline__ void store_planes(float* row, int col, const f32x4_sp v) {
+__device__ __forceinline__ void store_planes(float* row, int col, const f32x4 v) {
     bf16x4 sp[NP];
     split4<NP, false>(v, 0xffffffffu, sp);
     char* base = reinterpret_cast<char*>(row) + (col >> 5) * (64 * NP) + (col & 31) * 2;
@@ -81,14 +81,14 @@ __device__ __forceinline__ void store_planes(float* row, int col, const f32x4_sp
     for (int pl = 0; pl < NP; ++pl) *reinterpret_cast<bf16x4*>(base + 64 * pl) = sp[pl];
 }
 // the P2 layout of mode f32_half2: the same bytes, the two planes are the fp16 planes of s * v (split4h)
-__device__ __forceinline__ void store_planes_h(float* row, int col, const f32x4_sp v, const float s) {
+__device__ __forceinline__ void store_planes_h(float* row, int col, const f32x4 v, const float s) {
     bf16x4 sp[2];
     split4h<false>(v, 0xffffffffu, s, sp);
     char* base = reinterpret_cast<char*>(row) + (col >> 5) * 128 + (col & 31) * 2;
     *reinterpret_cast<bf16x4*>(base) = sp[0];
     *reinterpret_cast<bf16x4*>(base + 64) = sp[1];
 }
-__device__ __forceinline__ void store_planes_n(int np, float* row, int col, const f32x4_sp v) {
+__device__ __forceinline__ void store_planes_n(int np, float* row, int col, const f32x4 v) {
     if (np == 2) store_planes<2>(row, col, v); else store_planes<3>(row, col, v);
 }
 
