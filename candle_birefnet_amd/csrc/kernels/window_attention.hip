@@ -274,48 +274,93 @@ __device__ __forceinline__ int kswz(int key) { return (0x78 >> (2 * ((key >> 2) 
 // un-scaled exactly.  ~2^-22 relative per product instead of 2^-16.
 constexpr float ATT_H_QKV = 8.0f, ATT_H_P = 2048.0f;
 template <int NP, bool H = false>
-__global__ void __launch_bounds__(ATT_THREADS) window_attention_split_kernel(const WindowAttnParams pa, const WindowAttnParams pb, const int nblk0) {
+__global__ void __launch_bounds__(ATT_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3))) window_attention_split_kernel(const WindowAttnParams pa, const WindowAttnParams pb, const int nblk0) {
     static_assert(!H || NP == 2, "fp16 planes come in pairs");
     const bool second = (int)blockIdx.x >= nblk0;
     const WindowAttnParams& p = second ? pb : pa;
     __shared__ __attribute__((aligned(16))) __bf16 Kp[NP * NTOK * HD];
     __shared__ __attribute__((aligned(16))) __bf16 Vt[NP * HD * VT_LD];
-    __shared__ float tab_s[(2 * WS - 1) * (2 * WS - 1)];
-    __shared__ int src_s[NTOK];
+    constexpr int TABN = (2 * WS - 1) * (2 * WS - 1);
+    __shared__ float tab_s[TABN];
     __shared__ unsigned char rid_s[NTOK];
+    __shared__ __attribute__((aligned(16))) float qb_s[HD];    // the head's q bias: what a pad query is (kept out of the loop's registers)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int li = lane & 15, g = lane >> 4;
     const int head = blockIdx.y;
     const int nWw = p.Wp / WS, nW = (p.Hp / WS) * nWw;
     const int bw = second ? (int)blockIdx.x - nblk0 : (int)blockIdx.x;
     const int b = bw / nW, w = bw - b * nW;
     const int wr = w / nWw, wc = w - wr * nWw;
     const int C = p.C, C3 = 3 * C;
+    // the shift mask (swin.rs:283-296) is non-zero only in the last row / column of windows; elsewhere the old form added +0.0 to every
+    // score, which the result cannot see (a -0.0 score becomes +0.0; max and exp treat them alike)
+    const bool has_mask = p.shift > 0 && (wr == p.Hp / WS - 1 || wc == nWw - 1);
+
+    auto tok_src = [&](int t) {                                       // source row of window token t (roll + partition), -1 = pad token
+        const int ti = t / WS, tj = t - ti * WS;
+        int sh = wr * WS + ti + p.shift, sw = wc * WS + tj + p.shift;
+        if (sh >= p.Hp) sh -= p.Hp;
+        if (sw >= p.Wp) sw -= p.Wp;
+        return (sh < p.H && sw < p.W) ? (b * p.H + sh) * p.W + sw : -1;
+    };
+    // ---- every global load of the workgroup goes out FIRST, unconditionally, from clamped addresses (a pad token reads row 0 and is
+    // replaced by the qkv bias afterwards, by a select): the K / V rows of the thread's three staging items = (token pair, 4-wide d chunk),
+    // the bias chunks a pad token needs, the table words, the wave's first Q fragment.  The source rows are computed in registers: with
+    // src_s built first and the loads inside the staging loop behind a lane-dependent pointer select, hipcc waited vmcnt(0) per
+    // iteration and per query tile — six memory round trips one after the other in a workgroup that lives little longer than that. ----
+    static_assert((NTOK / 2) * 8 == 3 * ATT_THREADS && ATT_THREADS % 8 == 0 && 3 * ATT_THREADS >= TABN, "three staging items and three table words per thread");
+    const int c4 = (tid & 7) * 4;                                     // the same d chunk in all three items of a thread
+    const float* kbp = p.qkv_bias + C + head * HD + c4;
+    const f32x4 kbias = *reinterpret_cast<const f32x4*>(kbp);
+    const f32x4 vbias = *reinterpret_cast<const f32x4*>(kbp + C);
+    f32x4 kvr[3][2], vvr[3][2];
+    int ssrc[3][2];
+#pragma unroll
+    for (int it = 0; it < 3; ++it) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int src = tok_src(((tid >> 3) + it * (ATT_THREADS / 8)) * 2 + u);
+            ssrc[it][u] = src;
+            const float* kp = p.qkv + (long)max(src, 0) * C3 + C + head * HD + c4;
+            kvr[it][u] = *reinterpret_cast<const f32x4*>(kp);
+            vvr[it][u] = *reinterpret_cast<const f32x4*>(kp + C);
+        }
+    }
+    float tbw[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) tbw[j] = p.rel_table[head * TABN + min(tid + j * ATT_THREADS, TABN - 1)];
+    const float* qbp = p.qkv_bias + head * HD + g * 8;
+    const f32x4 qbias0 = *reinterpret_cast<const f32x4*>(qbp);
+    const f32x4 qbias1 = *reinterpret_cast<const f32x4*>(qbp + 4);
+    // the Q fragment of the NEXT query tile is requested while this one is multiplied (8 registers; all three up front cost occupancy)
+    int qsrc_n;
+    f32x4 qn0, qn1;
+    auto load_q = [&](int qtok) {
+        qsrc_n = tok_src(qtok);
+        const float* qp = p.qkv + (long)max(qsrc_n, 0) * C3 + head * HD + g * 8;
+        qn0 = *reinterpret_cast<const f32x4*>(qp);
+        qn1 = *reinterpret_cast<const f32x4*>(qp + 4);
+    };
+    load_q(wave * 16 + li);
 
     if (tid < NTOK) {
         const int ti = tid / WS, tj = tid - ti * WS;
         const int ph = wr * WS + ti, pw = wc * WS + tj;
-        int sh = ph + p.shift, sw = pw + p.shift;
-        if (sh >= p.Hp) sh -= p.Hp;
-        if (sw >= p.Wp) sw -= p.Wp;
-        src_s[tid] = (sh < p.H && sw < p.W) ? (b * p.H + sh) * p.W + sw : -1;
         const int fh = ph < p.Hp - WS ? 0 : (ph < p.Hp - p.shift ? 1 : 2);
         const int fw = pw < p.Wp - WS ? 0 : (pw < p.Wp - p.shift ? 1 : 2);
         rid_s[tid] = (unsigned char)(fh * 3 + fw);
     }
-    for (int i = tid; i < (2 * WS - 1) * (2 * WS - 1); i += ATT_THREADS) tab_s[i] = p.rel_table[head * ((2 * WS - 1) * (2 * WS - 1)) + i];
-    __syncthreads();
 
-    // ---- stage K (row-major, swizzled) and V (transposed), split into bf16 planes: items = (token pair, 4-wide d chunk) ----
-    for (int idx = tid; idx < (NTOK / 2) * 8; idx += ATT_THREADS) {
-        const int tp = idx >> 3, c4 = (idx & 7) * 4;
+    // ---- consume: K (row-major, swizzled) and V (transposed), split into bf16 planes; pad tokens take the qkv bias; the table ----
+#pragma unroll
+    for (int it = 0; it < 3; ++it) {
+        const int tp = (tid >> 3) + it * (ATT_THREADS / 8);
         f32x4 kv[2], vv[2];
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
-            const int t = tp * 2 + u, src = src_s[t];
-            const float* kp = src >= 0 ? p.qkv + (long)src * C3 + C + head * HD + c4 : p.qkv_bias + C + head * HD + c4;
-            kv[u] = *reinterpret_cast<const f32x4*>(kp);
-            vv[u] = *reinterpret_cast<const f32x4*>(kp + C);
+            kv[u] = ssrc[it][u] < 0 ? kbias : kvr[it][u];
+            vv[u] = ssrc[it][u] < 0 ? vbias : vvr[it][u];
         }
         if constexpr (H) {
 #pragma unroll
@@ -364,23 +409,29 @@ __global__ void __launch_bounds__(ATT_THREADS) window_attention_split_kernel(con
         }
         }
     }
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+        if (tid + j * ATT_THREADS < TABN) tab_s[tid + j * ATT_THREADS] = tbw[j];
+    if (tid < 64 && li == 0) {
+        *reinterpret_cast<f32x4*>(qb_s + g * 8) = qbias0;
+        *reinterpret_cast<f32x4*>(qb_s + g * 8 + 4) = qbias1;
+    }
     __syncthreads();
 
-    const int li = lane & 15, g = lane >> 4;
     for (int qt = wave; qt < 9; qt += 3) {
         const int qtok = qt * 16 + li;
-        const int qsrc = src_s[qtok];
+        const int qsrc = qsrc_n;
         const int qrid = rid_s[qtok];
         const int qbase = (qtok / WS + WS - 1) * (2 * WS - 1) + (qtok % WS) + WS - 1;
         // Q fragment (B operand of S^T = K Q^T): d = 8g .. 8g+7 of this lane's query, scaled (swin.rs:278), split
         bf16x8 qf[NP];
         {
-            const float* qp = qsrc >= 0 ? p.qkv + (long)qsrc * C3 + head * HD + g * 8 : p.qkv_bias + head * HD + g * 8;
-            const f32x4 q0 = *reinterpret_cast<const f32x4*>(qp);
-            const f32x4 q1 = *reinterpret_cast<const f32x4*>(qp + 4);
+            const f32x4 q0 = qsrc < 0 ? *reinterpret_cast<const f32x4*>(qb_s + g * 8) : qn0;
+            const f32x4 q1 = qsrc < 0 ? *reinterpret_cast<const f32x4*>(qb_s + g * 8 + 4) : qn1;
             float r[8];
 #pragma unroll
             for (int e = 0; e < 4; ++e) { r[e] = q0[e] * p.scale; r[4 + e] = q1[e] * p.scale; }
+            if (qt + 3 < 9) load_q(qtok + 48);
             if constexpr (H) {
                 typedef unsigned u32x4_q __attribute__((ext_vector_type(4)));
                 u32x4_q hi, lo;
@@ -430,7 +481,7 @@ __global__ void __launch_bounds__(ATT_THREADS) window_attention_split_kernel(con
             for (int r = 0; r < 4; ++r) {
                 const int key = kt * 16 + g * 4 + r;
                 float sv = H ? fmaf(st[kt][r], 1.0f / (ATT_H_QKV * ATT_H_QKV), tab_s[qbase - key - 11 * (key / WS)]) : st[kt][r] + tab_s[qbase - key - 11 * (key / WS)];
-                if (p.shift > 0) sv += ((int)rid_s[key] != qrid) ? -100.0f : 0.0f;
+                if (has_mask) sv += ((int)rid_s[key] != qrid) ? -100.0f : 0.0f;
                 st[kt][r] = sv;
                 mx = fmaxf(mx, sv);
             }
