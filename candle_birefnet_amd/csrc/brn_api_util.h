@@ -1,0 +1,107 @@
+// brn_api_util.h — what the files behind the extern "C" boundary share (brn_api.cpp, brn_image.cpp, brn_ops.cpp): the exception
+// barrier, per-call staging of caller buffers, a private arena for one graph fragment, the compute-mode table, the handles.
+#pragma once
+#include "brn_host.h"
+#include <functional>
+
+namespace brn {
+const char* last_error_cstr();
+
+// Exceptions stop here; every entry returns a status and leaves a thread-local message for brn_last_error().
+template <class F>
+static brn_status guarded(F&& f) {
+    try {
+        (void)hipGetLastError();              // an error another library (or an earlier failed call) left in this thread is not ours to report
+        f();
+        return BRN_OK;
+    } catch (const Error& e) {
+        set_last_error(e.what());
+        return e.code;
+    } catch (const std::bad_alloc&) {
+        set_last_error("host allocation failed");
+        return BRN_ERR_OOM;
+    } catch (const std::exception& e) {
+        set_last_error(e.what());
+        return BRN_ERR_INVALID_ARG;
+    }
+}
+
+// per-call staging of caller buffers: BRN_MEM_HOST buffers travel through temporary HBM allocations
+struct Staging {
+    hipStream_t s; brn_mem loc;
+    std::vector<void*> tmp;
+    struct Out { float* host; float* dev; size_t n; };
+    std::vector<Out> outs;
+    Staging(void* stream, brn_mem l) : s((hipStream_t)stream), loc(l) {}
+    float* dalloc(size_t n) {
+        void* d = nullptr;
+        hipError_t e = hipMalloc(&d, n * sizeof(float) + 16);
+        if (e != hipSuccess) fail(BRN_ERR_OOM, "hipMalloc of %zu bytes failed: %s", n * sizeof(float), hipGetErrorString(e));
+        tmp.push_back(d);
+        return (float*)d;
+    }
+    const float* in(const float* p, size_t n) {
+        if (!p) fail(BRN_ERR_INVALID_ARG, "null input pointer");
+        if (loc == BRN_MEM_DEVICE) return p;
+        float* d = dalloc(n);
+        BRN_HIP(hipMemcpyAsync(d, p, n * sizeof(float), hipMemcpyHostToDevice, s));
+        return d;
+    }
+    float* out(float* p, size_t n) {
+        if (!p) fail(BRN_ERR_INVALID_ARG, "null output pointer");
+        if (loc == BRN_MEM_DEVICE) return p;
+        float* d = dalloc(n);
+        outs.push_back({p, d, n});
+        return d;
+    }
+    void finish() {
+        for (auto& o : outs) BRN_HIP(hipMemcpyAsync(o.host, o.dev, o.n * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (loc == BRN_MEM_HOST) BRN_HIP(hipStreamSynchronize(s));
+    }
+    ~Staging() {
+        if (!tmp.empty()) (void)hipStreamSynchronize(s);
+        for (void* p : tmp) (void)hipFree(p);
+    }
+};
+
+// run a graph fragment with a private arena: plan (dry), allocate, run
+inline void with_arena(hipStream_t s, const std::function<void(Ctx&)>& fn, int bf16 = 0) {   // bf16: 0 fp32 maps, 1 bf16, 2 fp16 (Ctx::bf16)
+    Arena a;
+    a.dry = true;
+    Ctx c{&a, s, true, false, nullptr, nullptr, nullptr};
+    c.bf16 = bf16;
+    fn(c);
+    Arena real;
+    real.cap = a.peak + 256;
+    void* d = nullptr;
+    hipError_t e = hipMalloc(&d, real.cap);
+    if (e != hipSuccess) fail(BRN_ERR_OOM, "workspace hipMalloc of %zu bytes failed: %s", real.cap, hipGetErrorString(e));
+    real.base = (char*)d;
+    Ctx c2{&real, s, false, false, nullptr, nullptr, nullptr};
+    c2.bf16 = bf16;
+    try {
+        fn(c2);
+        BRN_HIP(hipStreamSynchronize(s));
+    } catch (...) {
+        (void)hipStreamSynchronize(s);
+        (void)hipFree(d);
+        throw;
+    }
+    (void)hipFree(d);
+}
+
+// what a brn_dtype means to the weight builders and to the activation maps (brn_api.cpp).  BRN_BF16_DEC_SPLIT2 maps to its backbone's
+// arithmetic (BRN_BF16); what it means for a decoder, and whether an entry accepts it at all, is the caller's line
+struct ComputeMode {
+    WeightBuild build;
+    int s16 = 0;                   // map storage: 0 fp32, 1 bf16, 2 fp16 (Ctx::bf16)
+};
+ComputeMode compute_mode(int dt);
+
+// brn_api.cpp, also behind brn_infer_images_u8 and brn_swin_forward
+void run_model(Model* m, const float* x, int B, int H, int W, brn_mem in_loc, float* out, brn_mem out_loc, void* stream, int apply_sigmoid);
+void swin_entry(const SwinW& w, int device, const float* x, int B, int H, int W, brn_mem in_loc, float* const outs[4], brn_mem out_loc,
+                void* stream, int bf16 = 0);
+}  // namespace brn
+
+struct brn_model { brn::Model m; };

@@ -1,6 +1,7 @@
 // brn_diag.cpp — brn_gemm_microbench (include/birefnet_hip_diag.h): compiled only into libbirefnet_hip_diag.so
 // (make diag, -DBRN_DIAG_BUILD); the product library carries neither this entry nor the probe kernels it drives.
 #include "brn_host.h"
+#include "brn_pack.h"
 #include "../../include/birefnet_hip_diag.h"
 #include <cstring>
 #include <cstdio>
@@ -120,16 +121,10 @@ brn_status brn_gemm_microbench(int M, int N, int K, int tile_cfg, int splitk, in
         int planes = 0;
         if (tile_cfg >= 1000) { planes = tile_cfg / 1000; tile_cfg %= 1000; if (tile_cfg == 999) tile_cfg = -1; }
         if (planes == 4) {        // 4000 + cfg (4999 = the library's plan): the bf16-storage kernel (kernels/gemm_bf16.hip), bf16 A and C
-            auto bf = [](float x) { uint32_t u; std::memcpy(&u, &x, 4); const uint32_t r = u + 0x7fffu + ((u >> 16) & 1u); return (uint16_t)(r >> 16); };
             std::vector<uint16_t> hab((size_t)M * K + 64);
-            for (size_t i = 0; i < (size_t)M * K; ++i) hab[i] = bf(ha[i]);
-            void* dAb = nullptr;
-            BRN_HIP(hipMalloc(&dAb, hab.size() * 2));
-            own.ptrs.push_back(dAb);
-            BRN_HIP(hipMemcpy(dAb, hab.data(), hab.size() * 2, hipMemcpyHostToDevice));
-            set_build_planes(BUILD_BF16);
-            GemmW gw = make_linear(own, hw.data(), nullptr, N, K);
-            set_build_planes(0);
+            for (size_t i = 0; i < (size_t)M * K; ++i) hab[i] = bf16_rne(ha[i]);
+            void* dAb = own.upload_u16(hab);
+            GemmW gw = make_linear(own, WeightBuild{BUILD_BF16, false}, hw.data(), nullptr, N, K);
             const bool epi1 = getenv("BRN_GEMM_EPI1") != nullptr;      // fp32 C + fp32 residual in place (proj / fc2) instead of bf16 C
             std::vector<float> hc(epi1 ? (size_t)M * N : (size_t)M * N / 2 + 64, 0.f);
             float* dC = own.upload(hc);
@@ -158,9 +153,7 @@ brn_status brn_gemm_microbench(int M, int N, int K, int tile_cfg, int splitk, in
             return;
         }
         float* dA = own.upload(ha);
-        set_build_planes(planes);
-        GemmW gw = make_linear(own, hw.data(), nullptr, N, K);
-        set_build_planes(0);
+        GemmW gw = make_linear(own, WeightBuild{planes, false}, hw.data(), nullptr, N, K);
         float* dW = gw.w;
         std::vector<float> hc((size_t)M * N, 0.f);
         float* dC = own.upload(hc);
@@ -170,14 +163,12 @@ brn_status brn_gemm_microbench(int M, int N, int K, int tile_cfg, int splitk, in
         if (tile_cfg >= 0) { pl.cfg = tile_cfg; pl.splitk = splitk > 1 ? splitk : 1; pl.ws_floats = pl.splitk > 1 ? (size_t)pl.splitk * M * N : 0; }
         if (a_p2) {
             if (planes != 2 || K % 32) fail(BRN_ERR_INVALID_ARG, "P2 input needs the 2-plane mode");
-            auto bf = [](float x) { uint32_t u; std::memcpy(&u, &x, 4); const uint32_t r = u + 0x7fffu + ((u >> 16) & 1u); return (uint16_t)(r >> 16); };
-            auto fl = [](uint16_t h) { uint32_t u = (uint32_t)h << 16; float f; std::memcpy(&f, &u, 4); return f; };
             std::vector<float> p2(ha.size());
             uint16_t* q = reinterpret_cast<uint16_t*>(p2.data());
             for (int m = 0; m < M; ++m)
                 for (int k = 0; k < K; ++k) {
                     const float x = ha[(size_t)m * K + k];
-                    const uint16_t h = bf(x), l = bf(x - fl(h));
+                    const uint16_t h = bf16_rne(x), l = bf16_rne(x - bf16_to_f32(h));
                     uint16_t* row = q + (size_t)m * K * 2;
                     row[(k / 32) * 64 + (k % 32)] = h;
                     row[(k / 32) * 64 + 32 + (k % 32)] = l;

@@ -91,6 +91,14 @@ struct Map {
 };
 Map new_map(Ctx& c, int B, int H, int W, int C);
 
+// how the weight builders pack every dense / channels-last conv GemmW beside its fp32 matrix: an argument of each of them
+constexpr int BUILD_BF16 = 16;    // the plain 16-bit matrix of the bf16-storage mode (and the fragment-ordered copies)
+constexpr int BUILD_HALF2 = 18;   // two fp16 planes of the scaled matrix (mode f32_half2)
+struct WeightBuild {
+    int planes = 0;               // 0: fp32 MFMA path only | 1..3: that many bf16 planes | BUILD_HALF2 | BUILD_BF16
+    bool f16 = false;             // with BUILD_BF16: the 16-bit copies are fp16 (compute mode BRN_F16)
+};
+
 // ---- prepared weights ---------------------------------------------------------------------------------------
 struct DevVec { float* p = nullptr; size_t n = 0; };
 
@@ -182,6 +190,7 @@ struct DeviceOwner {     // every hipMalloc of a model, freed together
     std::vector<void*> ptrs;
     float* upload(const float* host, size_t n);
     float* upload(const std::vector<float>& v) { return upload(v.data(), v.size()); }
+    void* upload_u16(const std::vector<uint16_t>& v);
     ~DeviceOwner();
 };
 
@@ -227,18 +236,18 @@ struct Model {
     ~Model();
 };
 
-void build_swin_weights(const WeightTable& wt, const std::string& prefix, const brn_config& cfg, DeviceOwner& own, SwinW& out);
+void build_swin_weights(const WeightTable& wt, const std::string& prefix, const brn_config& cfg, DeviceOwner& own, WeightBuild wb, SwinW& out);
 // ASPPDeformable::new(in_channels, out_channels (0 = in_channels), vb.pp(prefix)) (aspp.rs:236-300)
-void build_aspp_weights(const WeightTable& wt, const std::string& prefix, int deform_mode, DeviceOwner& own, ASPPW& out, int in_channels = 64,
+void build_aspp_weights(const WeightTable& wt, const std::string& prefix, int deform_mode, DeviceOwner& own, WeightBuild wb, ASPPW& out, int in_channels = 64,
                         int out_channels = 0);
-void build_decblk_weights(const WeightTable& wt, const std::string& prefix, int cin, int cout, int deform_mode, DeviceOwner& own, DecBlkW& out,
+void build_decblk_weights(const WeightTable& wt, const std::string& prefix, int cin, int cout, int deform_mode, DeviceOwner& own, WeightBuild wb, DecBlkW& out,
                           bool use_aspp = true, int inter_channels = 64 /* decoder.rs:94-98: 64, or in_channels / 4 when inter_channels_adaptive */);
-void build_decoder_weights(const WeightTable& wt, const std::string& prefix, const brn_config& cfg, DeviceOwner& own, DecoderW& out);
+void build_decoder_weights(const WeightTable& wt, const std::string& prefix, const brn_config& cfg, DeviceOwner& own, WeightBuild wb, DecoderW& out);
 
 // generic weight repack helpers (also used by the op-level entry points)
-GemmW make_linear(DeviceOwner& own, const float* w, const float* bias, int N, int K);
+GemmW make_linear(DeviceOwner& own, WeightBuild wb, const float* w, const float* bias, int N, int K);
 // conv for a channels-last input whose channel count is cin_padded (>= Cin, % 32 == 0); NHWC K order
-GemmW make_conv_nhwc(DeviceOwner& own, const float* w, const float* bias, int O, int Cin, int cin_padded, int kh, int kw,
+GemmW make_conv_nhwc(DeviceOwner& own, WeightBuild wb, const float* w, const float* bias, int O, int Cin, int cin_padded, int kh, int kw,
                      int stride, int pad, int dil);
 // conv that gathers straight from an NCHW tensor; candle K order
 GemmW make_conv_gather(DeviceOwner& own, const float* w, const float* bias, int O, int Cin, int kh, int kw, int stride, int pad, int dil);
@@ -255,9 +264,9 @@ void run_conv(Ctx& c, const GemmW& w, const Map& in, const Map& out, const float
 // true when the deformable conv `w` runs on kernels/deform_bf16.hip, which applies 2 * sigmoid to the modulator itself
 bool deform_fused_sigmoid(const Ctx& c, const GemmW& w);
 // bf16-storage mode: attach the fragment-ordered copy of a channels-last conv weight (w: candle [O][Cin][kh][kw]) for deform_bf16
-void attach_deform_frags(DeviceOwner& own, GemmW& g, const float* w_oihw);
+void attach_deform_frags(DeviceOwner& own, WeightBuild wb, GemmW& g, const float* w_oihw);
 // bf16-storage mode: the fragment-ordered copy of a Linear's [N][K] weight for gemm_wstat_bf16_kernel (K = 192, N % 192 == 0 only)
-void attach_dense_frags(DeviceOwner& own, GemmW& g, const float* w);
+void attach_dense_frags(DeviceOwner& own, WeightBuild wb, GemmW& g, const float* w);
 void run_conv_nchw(Ctx& c, const GemmW& w, const float* x_nchw, int B, int Hin, int Win, const Map& out, bool pad_to_stride = false);
 void run_layernorm(Ctx& c, const LNW& ln, const float* x, int rows, int ldx, float* y, int ldy, int y_coff, int y_planes = 0, int y_bf16 = 0);
 void run_resize(Ctx& c, const Map& in, const Map& out, bool accumulate = false);
@@ -287,13 +296,6 @@ void decoder_forward(Ctx& c, const Model& m, const float* img_nchw, int B, int H
 void model_forward(Model& m, Ctx& c, const float* img_nchw, int B, int H, int W, float* out, int apply_sigmoid);
 
 void ensure_device(int ordinal);
-// number of bf16 planes the weight builders attach to every dense / channels-last conv GemmW (0 = fp32 MFMA path only);
-// BUILD_BF16: attach the plain bf16 matrix of the bf16-storage mode instead
-constexpr int BUILD_BF16 = 16;
-void set_build_f16(bool on);      // with BUILD_BF16: the 16-bit copies are fp16 (compute mode BRN_F16)
-constexpr int BUILD_HALF2 = 18;   // two fp16 planes of the scaled matrix (mode f32_half2)
 float half2_act_scale();          // the power of two GEMM activations are scaled by before the fp16 split (BRN_H2_ASCALE, default 8)
-void set_build_planes(int planes);
-int build_planes();
 
 }  // namespace brn

@@ -1,0 +1,353 @@
+// brn_ops.cpp — the op-level entry points behind the extern "C" boundary (tests, the Rust shim): single layers and modules built from host
+// weights per call, in the arithmetic brn_set_op_compute selected on the calling thread.  Weights are always host pointers; x / y /
+// residual follow `loc`.
+#include "brn_api_util.h"
+#include <cstring>
+#include <memory>
+
+using namespace brn;
+
+struct brn_swin { brn_config cfg; int device; DeviceOwner own; SwinW w; std::mutex mu; int bf16 = 0; };
+
+namespace {
+
+// brn_set_op_compute: thread-local by contract of the ABI (default BRN_F32).  Every entry reads it once and passes it down.
+thread_local WeightBuild g_op;
+inline int op_s16(WeightBuild wb, bool on = true) { return on && wb.planes == BUILD_BF16 ? (wb.f16 ? 2 : 1) : 0; }   // Ctx::bf16 of the entry's maps
+
+// compute modes BRN_BF16 / BRN_F16 at op level: x is rounded to the 16-bit storage type at the edge, as the producing kernel of the
+// model would have written it; what the entry returns stays fp32 at this boundary
+const float* round_to_s16(Ctx& c, const float* dx, size_t n, bool f16) {
+    float* xb = c.arena->alloc_bytes(n * 2);
+    if (!c.dry) BRN_HIP(launch_f32_to_bf16(dx, n, xb, c.stream, f16));
+    return xb;
+}
+
+// x [B][C][H][W] -> channels-last map X of Cp >= C channels (the pad channels zero) -> body(c, X, Y) -> y [B][O][Ho][Wo]
+void through_nhwc(void* stream, int s16, const float* dx, int B, int C, int Cp, int H, int W, float* dy, int O, int Ho, int Wo,
+                  const std::function<void(Ctx&, const Map&, const Map&)>& body) {
+    with_arena((hipStream_t)stream, [&](Ctx& c) {
+        Map X = new_map(c, B, H, W, Cp), Y = new_map(c, B, Ho, Wo, O);
+        if (!c.dry) {
+            if (Cp != C) BRN_HIP(hipMemsetAsync(X.p, 0, (size_t)B * H * W * Cp * c.esz(), c.stream));
+            BRN_HIP(launch_nchw_to_nhwc(dx, B, C, H, W, X.p, X.ld, 0, c.stream, c.bf16));
+        }
+        body(c, X, Y);
+        if (!c.dry) BRN_HIP(launch_nhwc_to_nchw(Y.p, B, O, Ho, Wo, Y.ld, 0, dy, c.stream, c.bf16));
+    }, s16);
+}
+
+}  // namespace
+
+extern "C" {
+
+brn_status brn_set_op_compute(int dtype) {
+    return guarded([&] {
+        if (dtype == BRN_BF16_DEC_SPLIT2) fail(BRN_ERR_INVALID_ARG, "unsupported compute dtype %d", dtype);   // a mode of whole models only
+        g_op = compute_mode(dtype).build;
+    });
+}
+
+// ---- stand-alone SwinTransformer -----------------------------------------------------------------------------------------
+brn_status brn_swin_create(const brn_config* cfg, const brn_named_tensor* weights, size_t n, const char* prefix, int device,
+                           brn_swin** out) {
+    return guarded([&] {
+        if (!cfg || !weights || !out) fail(BRN_ERR_INVALID_ARG, "null argument");
+        *out = nullptr;
+        ensure_device(device);
+        std::unique_ptr<brn_swin> h(new brn_swin());
+        h->cfg = *cfg; h->device = device;
+        WeightTable wt(weights, n);
+        const WeightBuild wb = g_op;
+        h->bf16 = op_s16(wb);
+        build_swin_weights(wt, prefix ? prefix : "", *cfg, h->own, wb, h->w);
+        *out = h.release();
+    });
+}
+void brn_swin_destroy(brn_swin* s) {
+    if (!s) return;
+    (void)hipSetDevice(s->device);
+    (void)hipDeviceSynchronize();
+    delete s;
+}
+brn_status brn_swin_forward(brn_swin* s, const float* x, int B, int H, int W, brn_mem in_loc, float* const outs[4],
+                            brn_mem out_loc, void* stream) {
+    return guarded([&] {
+        if (!s) fail(BRN_ERR_INVALID_ARG, "null handle");
+        std::lock_guard<std::mutex> lk(s->mu);
+        swin_entry(s->w, s->device, x, B, H, W, in_loc, outs, out_loc, stream, s->bf16);
+    });
+}
+
+brn_status brn_linear_forward(const float* x, int M, int K, const float* w, const float* bias, int N, int act,
+                              const float* residual, float* y, brn_mem loc, int device, void* stream) {
+    return guarded([&] {
+        if (!x || !w || !y || M < 1 || N < 1 || K < 1) fail(BRN_ERR_INVALID_ARG, "bad argument");
+        ensure_device(device);
+        DeviceOwner own;
+        const WeightBuild wb = g_op;
+        GemmW g = make_linear(own, wb, w, bias, N, K);
+        g.act = act;
+        Staging st(stream, loc);
+        const float* dx = st.in(x, (size_t)M * K);
+        const float* dr = residual ? st.in(residual, (size_t)M * N) : nullptr;
+        float* dy = st.out(y, (size_t)M * N);
+        const int s16 = op_s16(wb);            // then the product runs on kernels/gemm_bf16.hip; y (and the residual) stay fp32
+        with_arena((hipStream_t)stream, [&](Ctx& c) {
+            const float* a = s16 ? round_to_s16(c, dx, (size_t)M * K, wb.f16) : dx;
+            run_gemm(c, g, a, M, K, dy, N, 0, dr, N, 0, nullptr, 1, 0, 0, s16 ? 1 : 0, s16 ? 1 : 0);
+        }, s16);
+        st.finish();
+    });
+}
+
+brn_status brn_linear_residual_layer_norm_forward(const float* x, int M, int K, const float* w, const float* bias, int N, const float* residual,
+                                                  const float* gamma, const float* beta, float eps, float* x_out, float* y_out, brn_mem loc,
+                                                  int device, void* stream) {
+    return guarded([&] {
+        if (!x || !w || !residual || !gamma || !beta || !x_out || !y_out || M < 1 || N < 1 || K < 1) fail(BRN_ERR_INVALID_ARG, "bad argument");
+        if (N % 4 || N > 3072) fail(BRN_ERR_INVALID_ARG, "layer_norm width %d unsupported (multiple of 4, <= 3072)", N);
+        if (eps != 1e-5f) fail(BRN_ERR_INVALID_ARG, "the fused projection + LayerNorm kernels are built for eps = 1e-5 (swin.rs:333-335)");
+        ensure_device(device);
+        DeviceOwner own;
+        const WeightBuild wb = g_op;
+        GemmW g = make_linear(own, wb, w, bias, N, K);
+        LNW ln; ln.C = N; ln.g = own.upload(gamma, N); ln.b = own.upload(beta, N);
+        Staging st(stream, loc);
+        const float* dx = st.in(x, (size_t)M * K);
+        const float* dr = st.in(residual, (size_t)M * N);
+        float* dxo = st.out(x_out, (size_t)M * N);
+        float* dyo = st.out(y_out, (size_t)M * N);
+        const bool bf = wb.planes == BUILD_BF16;
+        with_arena((hipStream_t)stream, [&](Ctx& c) {
+            const float* a = bf ? round_to_s16(c, dx, (size_t)M * K, wb.f16) : dx;
+            float* yb = bf ? c.arena->alloc_bytes((size_t)M * N * 2) : dyo;     // y produced as a 16-bit matrix and widened
+            // the residual stream is updated in place inside the model: here x_out starts as a copy of the residual
+            if (!c.dry) BRN_HIP(hipMemcpyAsync(dxo, dr, (size_t)M * N * sizeof(float), hipMemcpyDeviceToDevice, c.stream));
+            if (!linear_residual_ln(c, g, a, M, K, dxo, ln, yb, N, true)) {
+                run_gemm(c, g, a, M, K, dxo, N, 0, dxo, N, 0, nullptr, 0, 0, 0, bf ? 1 : 0, bf ? 1 : 0);
+                run_layernorm(c, ln, dxo, M, N, yb, N, 0, 0, bf ? 1 : 0);
+            }
+            if (bf && !c.dry) BRN_HIP(launch_bf16_to_f32(yb, (size_t)M * N, dyo, c.stream, wb.f16));
+        }, op_s16(wb));
+        st.finish();
+    });
+}
+
+brn_status brn_layer_norm_forward(const float* x, int rows, int C, const float* gamma, const float* beta, float eps, float* y,
+                                  brn_mem loc, int device, void* stream) {
+    return guarded([&] {
+        if (!x || !gamma || !beta || !y || rows < 1) fail(BRN_ERR_INVALID_ARG, "bad argument");
+        if (C % 4 || C > 3072) fail(BRN_ERR_INVALID_ARG, "layer_norm width %d unsupported (multiple of 4, <= 3072)", C);
+        ensure_device(device);
+        DeviceOwner own;
+        LNW ln; ln.C = C; ln.g = own.upload(gamma, C); ln.b = own.upload(beta, C);
+        Staging st(stream, loc);
+        const float* dx = st.in(x, (size_t)rows * C);
+        float* dy = st.out(y, (size_t)rows * C);
+        LayerNormParams p{};
+        p.x = dx; p.y = dy; p.rows = rows; p.C = C; p.gamma = ln.g; p.beta = ln.b; p.eps = eps; p.ldx = C; p.ldy = C;
+        BRN_HIP(launch_layernorm(p, (hipStream_t)stream));
+        BRN_HIP(hipStreamSynchronize((hipStream_t)stream));
+        st.finish();
+    });
+}
+
+brn_status brn_conv2d_forward(const float* x, int B, int C, int H, int W, const float* w, const float* bias, int O, int kh,
+                              int kw, int stride, int pad, int dil, const float* bn_g, const float* bn_b, const float* bn_m,
+                              const float* bn_v, float bn_eps, int act, float* y, brn_mem loc, int device, void* stream) {
+    return guarded([&] {
+        if (!x || !w || !y || B < 1 || C < 1 || O < 1 || kh < 1 || kw < 1 || stride < 1 || dil < 1 || pad < 0)
+            fail(BRN_ERR_INVALID_ARG, "bad argument");
+        const int Ho = (H + 2 * pad - dil * (kh - 1) - 1) / stride + 1, Wo = (W + 2 * pad - dil * (kw - 1) - 1) / stride + 1;
+        if (Ho < 1 || Wo < 1) fail(BRN_ERR_INVALID_ARG, "empty conv output");
+        ensure_device(device);
+        DeviceOwner own;
+        const WeightBuild wb = g_op;
+        const bool nhwc = (C % 32) == 0;
+        GemmW g = nhwc ? make_conv_nhwc(own, wb, w, nullptr, O, C, C, kh, kw, stride, pad, dil)
+                       : make_conv_gather(own, w, nullptr, O, C, kh, kw, stride, pad, dil);
+        if (bn_g) fold_bn(own, g, bias, bn_g, bn_b, bn_m, bn_v, bn_eps);
+        else if (bias) g.bias = own.upload(bias, O);
+        g.act = act;
+        Staging st(stream, loc);
+        const float* dx = st.in(x, (size_t)B * C * H * W);
+        float* dy = st.out(y, (size_t)B * O * Ho * Wo);
+        if (nhwc)            // bf16 mode (from 64 channels on): bf16 map in, bf16 map out, like inside the model
+            through_nhwc(stream, op_s16(wb, C >= 64), dx, B, C, C, H, W, dy, O, Ho, Wo, [&](Ctx& c, const Map& X, const Map& Y) { run_conv(c, g, X, Y); });
+        else
+            with_arena((hipStream_t)stream, [&](Ctx& c) {
+                Map Y = new_map(c, B, Ho, Wo, O);
+                run_conv_nchw(c, g, dx, B, H, W, Y);
+                if (!c.dry) BRN_HIP(launch_nhwc_to_nchw(Y.p, B, O, Ho, Wo, Y.ld, 0, dy, c.stream, c.bf16));
+            });
+        st.finish();
+    });
+}
+
+brn_status brn_upsample_bilinear2d(const float* x, int B, int C, int H, int W, int oh, int ow, float* y, brn_mem loc,
+                                   int device, void* stream) {
+    return guarded([&] {
+        if (!x || !y || B < 1 || C < 1 || H < 1 || W < 1 || oh < 1 || ow < 1) fail(BRN_ERR_INVALID_ARG, "bad argument");
+        ensure_device(device);
+        Staging st(stream, loc);
+        const float* dx = st.in(x, (size_t)B * C * H * W);
+        float* dy = st.out(y, (size_t)B * C * oh * ow);
+        BRN_HIP(launch_resize_nchw(dx, B * C, H, W, dy, oh, ow, (hipStream_t)stream));
+        BRN_HIP(hipStreamSynchronize((hipStream_t)stream));
+        st.finish();
+    });
+}
+
+brn_status brn_window_attention_forward(const float* x, int B, int H, int W, int C, int heads, int window_size, int shift,
+                                        const float* qkv_w, const float* qkv_b, const float* proj_w, const float* proj_b,
+                                        const float* rel_table, float* y, brn_mem loc, int device, void* stream) {
+    return guarded([&] {
+        if (!x || !qkv_w || !qkv_b || !proj_w || !proj_b || !rel_table || !y) fail(BRN_ERR_INVALID_ARG, "null argument");
+        if (!(window_size == 12 || window_size == 7) || heads < 1 || C != heads * 32 || !(shift == 0 || shift == window_size / 2))
+            fail(BRN_ERR_INVALID_ARG, "window attention needs window_size 12 or 7, head_dim 32, shift 0 or window_size / 2");
+        ensure_device(device);
+        DeviceOwner own;
+        // reuse the model's weight builder through a one-block table
+        const int T = (2 * window_size - 1) * (2 * window_size - 1);
+        SwinBlockW bk;
+        bk.heads = heads;
+        const WeightBuild wb = g_op;
+        bk.qkv = make_linear(own, wb, qkv_w, qkv_b, 3 * C, C);
+        bk.proj = make_linear(own, wb, proj_w, proj_b, C, C);
+        {
+            std::vector<float> tt((size_t)T * heads);
+            for (int t = 0; t < T; ++t) for (int h = 0; h < heads; ++h) tt[(size_t)h * T + t] = rel_table[(size_t)t * heads + h];
+            bk.rel_table = own.upload(tt);
+        }
+        Staging st(stream, loc);
+        const float* dx = st.in(x, (size_t)B * H * W * C);
+        float* dy = st.out(y, (size_t)B * H * W * C);
+        // compute mode BRN_BF16 at op level: x is rounded to bf16 at the edge (inside the model LayerNorm writes it as bf16), qkv and
+        // the attention output are bf16 matrices (window_attention_bf16_kernel), y = proj(...) stays fp32 like the residual stream
+        const int s16 = op_s16(wb);
+        with_arena((hipStream_t)stream, [&](Ctx& c) {
+            const float* xn = s16 ? round_to_s16(c, dx, (size_t)B * H * W * C, wb.f16) : dx;
+            swin_attention(c, bk, xn, B, H, W, C, shift, dy, nullptr, window_size);
+        }, s16);
+        st.finish();
+    });
+}
+
+brn_status brn_patch_merging_forward(const float* x, int B, int H, int W, int C, const float* ng, const float* nb,
+                                     const float* rw, float* y, brn_mem loc, int device, void* stream) {
+    return guarded([&] {
+        if (!x || !ng || !nb || !rw || !y || B < 1 || H < 1 || W < 1) fail(BRN_ERR_INVALID_ARG, "bad argument");
+        if (C % 32 || 4 * C > 3072) fail(BRN_ERR_INVALID_ARG, "patch merging width %d unsupported", C);
+        ensure_device(device);
+        DeviceOwner own;
+        LNW ln; ln.C = 4 * C; ln.g = own.upload(ng, 4 * C); ln.b = own.upload(nb, 4 * C);
+        GemmW red = make_linear(own, WeightBuild{}, rw, nullptr, 2 * C, 4 * C);   // fp32 in every op mode
+        const int Ho = (H + 1) / 2, Wo = (W + 1) / 2, M2 = B * Ho * Wo;
+        Staging st(stream, loc);
+        const float* dx = st.in(x, (size_t)B * H * W * C);
+        float* dy = st.out(y, (size_t)M2 * 2 * C);
+        with_arena((hipStream_t)stream, [&](Ctx& c) {
+            float* pm = c.arena->alloc((size_t)M2 * 4 * C);
+            if (!c.dry) {
+                LayerNormParams p{};
+                p.x = dx; p.y = pm; p.rows = M2; p.C = 4 * C; p.gamma = ln.g; p.beta = ln.b; p.eps = 1e-5f;
+                p.ldy = 4 * C; p.mode = 1; p.H = H; p.W = W; p.Cin = C;
+                BRN_HIP(launch_layernorm(p, c.stream));
+            }
+            run_gemm(c, red, pm, M2, 4 * C, dy, 2 * C, 0);
+        });
+        st.finish();
+    });
+}
+
+brn_status brn_aspp_deformable_forward(const brn_named_tensor* weights, size_t n, const char* prefix, int in_channels, int out_channels, int mode,
+                                       const float* x, int B, int H, int W, float* y, brn_mem loc, int device, void* stream) {
+    return guarded([&] {
+        if (!weights || !x || !y || B < 1 || H < 1 || W < 1 || in_channels < 1 || out_channels < 0) fail(BRN_ERR_INVALID_ARG, "bad argument");
+        if (mode != BRN_DEFORM_REFERENCE_CPU && mode != BRN_DEFORM_DEFORMABLE) fail(BRN_ERR_INVALID_ARG, "unknown deform mode %d", mode);
+        ensure_device(device);
+        DeviceOwner own;
+        const WeightBuild wb = g_op;
+        WeightTable wt(weights, n);
+        ASPPW a;
+        build_aspp_weights(wt, prefix ? prefix : "", mode, own, wb, a, in_channels, out_channels);
+        Staging st(stream, loc);
+        const float* dx = st.in(x, (size_t)B * a.ic * H * W);
+        float* dy = st.out(y, (size_t)B * a.oc * H * W);
+        through_nhwc(stream, op_s16(wb), dx, B, a.ic, a.icp, H, W, dy, a.oc, H, W, [&](Ctx& c, const Map& T, const Map& U) { aspp_forward(c, a, T, U, mode); });
+        st.finish();
+    });
+}
+
+brn_status brn_decblk_forward(const brn_named_tensor* weights, size_t n, const char* prefix, int cin, int cout, int inter, int use_aspp, int mode,
+                              const float* x, int B, int H, int W, float* y, brn_mem loc, int device, void* stream) {
+    return guarded([&] {
+        if (!weights || !x || !y || B < 1 || H < 1 || W < 1 || cin < 1 || cout < 1 || inter < 0) fail(BRN_ERR_INVALID_ARG, "bad argument");
+        if (mode != BRN_DEFORM_REFERENCE_CPU && mode != BRN_DEFORM_DEFORMABLE) fail(BRN_ERR_INVALID_ARG, "unknown deform mode %d", mode);
+        ensure_device(device);
+        DeviceOwner own;
+        const WeightBuild wb = g_op;
+        WeightTable wt(weights, n);
+        DecBlkW blk;
+        build_decblk_weights(wt, prefix ? prefix : "", cin, cout, mode, own, wb, blk, use_aspp != 0, inter > 0 ? inter : 64);
+        const int cinp = blk.conv_in.Cinp;                   // in_channels rounded up to the kernels' channel granule (zero weights there)
+        Staging st(stream, loc);
+        const float* dx = st.in(x, (size_t)B * cin * H * W);
+        float* dy = st.out(y, (size_t)B * cout * H * W);
+        through_nhwc(stream, op_s16(wb), dx, B, cin, cinp, H, W, dy, cout, H, W, [&](Ctx& c, const Map& X, const Map& Y) { decblk_forward(c, blk, X, Y, mode); });
+        st.finish();
+    });
+}
+
+brn_status brn_deform_conv2d_forward(const float* x, int B, int C, int H, int W, const float* offset_w, const float* offset_b,
+                                     const float* mod_w, const float* mod_b, const float* w, const float* bias, int O, int k,
+                                     int stride, int pad, int mode, float* y, brn_mem loc, int device, void* stream) {
+    return guarded([&] {
+        if (!x || !offset_w || !offset_b || !mod_w || !mod_b || !w || !y || k < 1 || stride < 1 || pad < 0)
+            fail(BRN_ERR_INVALID_ARG, "bad argument");
+        if (mode == BRN_DEFORM_REFERENCE_CPU) {
+            // deform_conv.rs:95-98: offsets and modulator are computed and discarded; the result is regular_conv(x)
+            brn_status s = brn_conv2d_forward(x, B, C, H, W, w, bias, O, k, k, stride, pad, 1, nullptr, nullptr, nullptr,
+                                              nullptr, 0.f, BRN_ACT_NONE, y, loc, device, stream);
+            if (s != BRN_OK) fail(s, "%s", brn_last_error());
+            return;
+        }
+        if (mode != BRN_DEFORM_DEFORMABLE) fail(BRN_ERR_INVALID_ARG, "unknown deform mode %d", mode);
+        const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1, kk = k * k;
+        ensure_device(device);
+        DeviceOwner own;
+        // compute mode BRN_BF16 at op level (brn_set_op_compute): bf16 map in / out as inside the model, offsets / modulator fp32, the
+        // gather on kernels/deform_bf16.hip where the shape allows; every other mode runs the fp32-MFMA gather kernel.
+        // Any in_channels (deform_conv.rs:29-36): the channels-last map is padded with zero channels to the kernels' granule (32; 64 for
+        // the bf16 gather kernel), the weights with zero columns
+        const bool bf = g_op.planes == BUILD_BF16 && (O % 8) == 0;
+        const int Cp = (C + (bf ? 63 : 31)) / (bf ? 64 : 32) * (bf ? 64 : 32);
+        const WeightBuild wb = bf ? g_op : WeightBuild{};     // (a split mode builds fp32 here)
+        std::vector<float> w3((size_t)3 * kk * C * kk), b3((size_t)3 * kk);
+        memcpy(w3.data(), offset_w, (size_t)2 * kk * C * kk * sizeof(float));
+        memcpy(w3.data() + (size_t)2 * kk * C * kk, mod_w, (size_t)kk * C * kk * sizeof(float));
+        memcpy(b3.data(), offset_b, (size_t)2 * kk * sizeof(float));
+        memcpy(b3.data() + 2 * kk, mod_b, (size_t)kk * sizeof(float));
+        GemmW om = make_conv_nhwc(own, wb, w3.data(), b3.data(), 3 * kk, C, Cp, k, k, stride, pad, 1);
+        om.mode = GEMM_CONV_NHWC;
+        GemmW reg = make_conv_nhwc(own, wb, w, bias, O, C, Cp, k, k, stride, pad, 1);
+        reg.mode = GEMM_DEFORM_NHWC;
+        attach_deform_frags(own, wb, reg, w);
+        Staging st(stream, loc);
+        const float* dx = st.in(x, (size_t)B * C * H * W);
+        float* dy = st.out(y, (size_t)B * O * Ho * Wo);
+        through_nhwc(stream, op_s16(wb), dx, B, C, Cp, H, W, dy, O, Ho, Wo, [&](Ctx& c, const Map& X, const Map& Y) {
+            const int ldom = (3 * kk + 3) / 4 * 4;
+            Map OM; OM.B = B; OM.H = Ho; OM.W = Wo; OM.C = 3 * kk; OM.ld = ldom; OM.coff = 0;
+            OM.p = c.arena->alloc((size_t)B * Ho * Wo * ldom);
+            run_conv(c, om, X, OM, nullptr, 0, 0, 1);
+            const bool fused_sig = deform_fused_sigmoid(c, reg);
+            if (!c.dry && !fused_sig) BRN_HIP(launch_mod_sigmoid2(OM.p, (size_t)B * Ho * Wo, ldom, 2 * kk, 3 * kk, c.stream));
+            run_conv(c, reg, X, Y, OM.p, ldom, 2 * kk, 0, fused_sig ? 1 : 0);
+        });
+        st.finish();
+    });
+}
+
+}  // extern "C"
