@@ -102,8 +102,7 @@ static void run_model_locked(Model* m, const float* x, int B, int H, int W, brn_
 
 // sub-batches a device-resident batch of B images runs as (BRN_SPLIT_STREAMS, default 2; at least two images per part)
 static int sub_batch_parts(int B, int override_parts = 0) {
-    static const int parts_env = getenv("BRN_SPLIT_STREAMS") ? atoi(getenv("BRN_SPLIT_STREAMS")) : 2;
-    const int want = override_parts > 0 ? override_parts : parts_env;     // brn_model_set_streams beats the environment
+    const int want = override_parts > 0 ? override_parts : switches().split_streams;     // brn_model_set_streams beats the environment
     int parts = want < 1 ? 1 : (want > 8 ? 8 : want);
     if (parts > B / 2) parts = B / 2;
     return parts < 1 ? 1 : parts;
@@ -184,13 +183,10 @@ static void run_model_locked(Model* m, const float* x, int B, int H, int W, brn_
     // loops of the others (measured at batch 8, 1024^2, bf16: +5.6 % with 2 parts).  BRN_SPLIT_STREAMS = number of
     // parts (default 2; 1 = one stream).  Each part has its own workspace; the results do not depend on how the host interleaves the
     // enqueues (same kernels, same plans per part, no atomics).  Profiled forwards run on one stream (per-launch events).
-    // Independent branches of one forward (ASPP branches, the image-patch convolutions) go to auxiliary streams (brn_graph.cpp: Branch);
-    // BRN_BRANCH_STREAMS=0 keeps everything on the forward's own stream.
-    // Default: on when the batch runs as ONE part (measured: +1.4 % at batch 1, 1024^2; with two sub-batch streams the extra
-    // concurrency costs 2.5 % at batch 8); a positive value is the mask of auxiliary streams to use, for every batch
-    // (31 = all: 7 the ASPP branches, 8 the image-patch convolutions, 16 the lateral convolutions).
-    static const int branches_env0 = getenv("BRN_BRANCH_STREAMS") ? atoi(getenv("BRN_BRANCH_STREAMS")) : -1;
-    const int branches_env = m->opt_branches > -2 ? m->opt_branches : branches_env0;    // brn_model_set_streams beats the environment
+    // Independent branches of one forward (ASPP branches, the image-patch convolutions) go to auxiliary streams (brn_graph.h: Branch);
+    // BRN_BRANCH_STREAMS (brn_host.h): by default on when the batch runs as ONE part (measured: +1.4 % at batch 1, 1024^2; with two
+    // sub-batch streams the extra concurrency costs 2.5 % at batch 8).
+    const int branches_env = m->opt_branches > -2 ? m->opt_branches : switches().branch_streams;    // brn_model_set_streams beats the environment
     bool branches_on = branches_env != 0;
     auto branch_set = [&](int k) -> BranchSet* {
         if (!branches_on || m->profiling) return nullptr;
@@ -211,10 +207,9 @@ static void run_model_locked(Model* m, const float* x, int B, int H, int W, brn_
             Model::Side& sd = m->sides[k];
             sd.arena.top = 0; sd.arena.peak = 0; sd.arena.dry = false;
         }
-        // BRN_CU_PARTITION (A/B switch, two parts only): each part's stream is confined to its own half of the chip by a CU mask
-        // (hipExtStreamCreateWithCUMask; mask bit i = CU i / 8 of XCD i % 8): 1 = half the CUs of every XCD (both parts share every L2),
-        // 2 = four whole XCDs each.  The persistent GEMM grids are sized for the CUs of the mask (set_launch_cus).
-        static const int cu_part = getenv("BRN_CU_PARTITION") ? atoi(getenv("BRN_CU_PARTITION")) : 0;
+        // BRN_CU_PARTITION (A/B switch, two parts only): each part's stream is confined to its own half of the chip by a CU mask (mask bit
+        // i = CU i / 8 of XCD i % 8; 1 shares every L2, 2 does not).  The persistent GEMM grids are sized for the CUs of the mask (set_launch_cus).
+        const int cu_part = switches().cu_partition;
         const bool masked = cu_part > 0 && parts == 2;
         if (masked && !m->cu_stream[0]) {
             for (int k = 0; k < 2; ++k) {
@@ -269,7 +264,8 @@ static void swin_outputs_nchw(Ctx& c, const SwinW& w, const float* dx, int B, in
     swin_stage_dims(H, W, w.patch, hs, ws);
     Map hm[4];
     for (int i = 0; i < 4; ++i) hm[i] = new_map(c, B, hs[i], ws[i], w.embed_dim << i);
-    swin_forward(c, w, dx, B, H, W, hm);
+    const SwinIn in{dx, H, W, hm};
+    swin_forward_multi(c, w, &in, 1, B);
     if (!c.dry)
         for (int i = 0; i < 4; ++i)     // NHWC -> NCHW: the permute(0,3,1,2) of swin.rs:786-788
             BRN_HIP(launch_nhwc_to_nchw(hm[i].p, B, hm[i].C, hs[i], ws[i], hm[i].ld, 0, douts[i], c.stream, c.bf16));

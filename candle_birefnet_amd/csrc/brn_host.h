@@ -56,7 +56,7 @@ struct Arena {
 };
 
 // auxiliary streams of one forward: branches of the graph that do not depend on each other (the four ASPP branches of a decoder
-// block, the image-patch convolutions beside the backbone) are enqueued on them between a fork and a join event (brn_graph.cpp)
+// block, the image-patch convolutions beside the backbone) are enqueued on them between a fork and a join event (brn_graph.h)
 constexpr int BRN_AUX_STREAMS = 5;   // 0-2: ASPP branches, 3: image-patch convolutions, 4: lateral convolutions
 struct BranchSet {
     hipStream_t stream[BRN_AUX_STREAMS] = {};
@@ -86,10 +86,37 @@ struct Ctx {
 struct Map {
     float* p = nullptr;
     int B = 0, H = 0, W = 0, C = 0, ld = 0, coff = 0;
+    Map() = default;
+    Map(float* p_, int B_, int H_, int W_, int C_) : p(p_), B(B_), H(H_), W(W_), C(C_), ld(C_) {}   // a whole dense map at p_
     size_t pixels() const { return (size_t)B * H * W; }
     Map window(int c0, int c) const { Map m = *this; m.coff = coff + c0; m.C = c; return m; }
 };
 Map new_map(Ctx& c, int B, int H, int W, int C);
+static inline int roundup(int x, int m) { return (x + m - 1) / m * m; }
+
+// ---- environment switches: all read together, once per process, at the first use of any (BRN_DUMP_LAUNCHES and BRN_FAULT_SIDE_ARENA,
+// brn_api.cpp, are read per call and are not of this kind).  DESIGN.md carries the same table: field, name, default, meaning
+#define BRN_SWITCHES(X)                                                                                                                        \
+    X(split_streams,    "BRN_SPLIT_STREAMS",     2,  "sub-batch streams of a device-resident batch (at least two images per part; 1 = one stream)") \
+    X(branch_streams,   "BRN_BRANCH_STREAMS",    -1, "-1 = auxiliary branch streams when the batch is one part; 0 = none; else the mask forced (7 ASPP, 8 image-patch, 16 lateral)") \
+    X(cu_partition,     "BRN_CU_PARTITION",      0,  "1 / 2 = two sub-batch streams confined to half the CUs of every XCD / to four XCDs each") \
+    X(wstat,            "BRN_WSTAT",             3,  "mask of the K served by gemm_wstat_bf16_kernel (1 = 192, 2 = 384)")                     \
+    X(wstat_ln,         "BRN_WSTAT_LN",          1,  "0 = stage-0 projection and norm2 as two launches instead of gemm_wstat_ln_bf16_kernel")   \
+    X(rowln,            "BRN_ROWLN",             0,  "mask of the widths whose projection + LayerNorm run on gemm_rowln_bf16_kernel (1 = 768, 2 = 384)") \
+    X(patch_ln,         "BRN_PATCH_LN",          1,  "0 = PatchEmbed as gather GEMM + LayerNorm in the 16-bit modes too; 2 = fused without the first block's norm1") \
+    X(p1_f32,           "BRN_P1_F32",            1,  "0 = the decoder's last map p1 is a 16-bit map like every other in the 16-bit modes")     \
+    X(h2_att,           "BRN_H2_ATT",            1,  "0 = mode f32_half2 runs the fp32-MFMA attention kernel instead of the fp16-pair one")     \
+    X(h2_ascale,        "BRN_H2_ASCALE",         3,  "log2 of the scale of GEMM input activations before the fp16 split of mode f32_half2 (0 .. 8)") \
+    X(deform_f32,       "BRN_DEFORM_F32_KERNEL", 0,  "1 = the 16-bit modes run deformable convolutions on the fp32-MFMA gather kernel")        \
+    X(planes_kernel,    "BRN_PLANES_KERNEL",     0,  "1 = split modes with P-layout A on the LDS-DMA plane kernel (diag build only)")           \
+    X(conv_chunk_major, "BRN_CONV_CHUNK_MAJOR",  1,  "0 = tap-major K order of the 16-bit implicit-GEMM conv weights (read when weights are packed)") \
+    X(offmod_pad8,      "BRN_OFFMOD_PAD8",       1,  "0 = the offset / modulator conv's N padded to 4 instead of 8")
+struct Switches {
+#define BRN_X(field, name, dflt, doc) int field = dflt;
+    BRN_SWITCHES(BRN_X)
+#undef BRN_X
+};
+const Switches& switches();
 
 // how the weight builders pack every dense / channels-last conv GemmW beside its fp32 matrix: an argument of each of them
 constexpr int BUILD_BF16 = 16;    // the plain 16-bit matrix of the bf16-storage mode (and the fragment-ordered copies)
@@ -100,7 +127,6 @@ struct WeightBuild {
 };
 
 // ---- prepared weights ---------------------------------------------------------------------------------------
-struct DevVec { float* p = nullptr; size_t n = 0; };
 
 struct GemmW {          // one Linear / Conv2d, repacked for gemm_f32
     float* w = nullptr; // [roundup(N,128)][K]
@@ -255,12 +281,33 @@ void fold_bn(DeviceOwner& own, GemmW& g, const float* conv_bias_host, const floa
              const float* mean, const float* var, float eps);
 
 // ---- graph pieces ------------------------------------------------------------------------------------------------
-void run_gemm(Ctx& c, const GemmW& w, const float* A, int M, int lda, float* C, int ldc, int c_coff,
-              const float* R = nullptr, int ldr = 0, int r_coff = 0, const float* bbias = nullptr, int bbias_rows = 1,
-              int a_planes = 0, int c_planes = 0 /* 2: operand in the P2 layout (kernels/split_planes.h) */,
-              int c_f32 = 0, int r_f32 = 0 /* compute mode BRN_BF16 only: C written / R read as fp32 (the residual stream) */);
-void run_conv(Ctx& c, const GemmW& w, const Map& in, const Map& out, const float* om = nullptr, int om_ld = 0, int om_mask_off = 0,
-              int c_f32 = 0, int om_sigmoid = 0 /* the modulator columns are raw logits (only with deform_fused_sigmoid(c, w)) */);
+// The operands of run_gemm: C[m][c_coff + n] = epilogue(sum_k A[m][k] W[n][k]); A and C as matrices or Map windows, the rest set by name
+struct GemmIO {
+    const float* A = nullptr; int M = 0, lda = 0;
+    float* C = nullptr; int ldc = 0, c_coff = 0;
+    const float* R = nullptr; int ldr = 0, r_coff = 0;       // + R[m][r_coff + n] after the activation
+    const float* bbias = nullptr; int bbias_rows = 0;        // + bbias[m / bbias_rows][n] (a bias per image)
+    int a_planes = 0, c_planes = 0;                          // 2: the operand is in the P2 layout (kernels/split_planes.h)
+    int c_f32 = 0, r_f32 = 0;                                // 16-bit modes only: C written / R read as fp32 (the residual stream)
+    GemmIO(const float* A_, int M_, int lda_) : A(A_), M(M_), lda(lda_) {}
+    GemmIO(const Ctx& c, const Map& a) : A(c.at(a.p, a.coff)), M((int)a.pixels()), lda(a.ld) {}
+    GemmIO& to(float* C_, int ldc_) { C = C_; ldc = ldc_; return *this; }
+    GemmIO& to(const Map& m) { C = m.p; ldc = m.ld; c_coff = m.coff; return *this; }
+    GemmIO& add(const float* R_, int ldr_) { R = R_; ldr = ldr_; return *this; }
+    GemmIO& add(const Map& m) { R = m.p; ldr = m.ld; r_coff = m.coff; return *this; }
+    GemmIO& image_bias(const float* b, int rows_per_image) { bbias = b; bbias_rows = rows_per_image; return *this; }
+    GemmIO& planes(int a, int c_) { a_planes = a; c_planes = c_; return *this; }
+    GemmIO& f32(int c_, int r) { c_f32 = c_; r_f32 = r; return *this; }
+};
+void run_gemm(Ctx& c, const GemmW& w, const GemmIO& io);
+// what run_conv takes beside the maps: the offset / modulator map of a deformable conv, fp32 output in the 16-bit modes
+struct ConvOpts {
+    const float* om = nullptr; int om_ld = 0, om_mask_off = 0;
+    int om_sigmoid = 0, c_f32 = 0;      // om_sigmoid: the modulator columns are raw logits (only with deform_fused_sigmoid(c, w))
+    ConvOpts& offsets(const Map& m, int mask_off, bool raw_logits) { om = m.p; om_ld = m.ld; om_mask_off = mask_off; om_sigmoid = raw_logits ? 1 : 0; return *this; }
+    ConvOpts& f32(int on = 1) { c_f32 = on; return *this; }
+};
+void run_conv(Ctx& c, const GemmW& w, const Map& in, const Map& out, const ConvOpts& o = ConvOpts());
 // true when the deformable conv `w` runs on kernels/deform_bf16.hip, which applies 2 * sigmoid to the modulator itself
 bool deform_fused_sigmoid(const Ctx& c, const GemmW& w);
 // bf16-storage mode: attach the fragment-ordered copy of a channels-last conv weight (w: candle [O][Cin][kh][kw]) for deform_bf16
@@ -268,18 +315,25 @@ void attach_deform_frags(DeviceOwner& own, WeightBuild wb, GemmW& g, const float
 // bf16-storage mode: the fragment-ordered copy of a Linear's [N][K] weight for gemm_wstat_bf16_kernel (K = 192, N % 192 == 0 only)
 void attach_dense_frags(DeviceOwner& own, WeightBuild wb, GemmW& g, const float* w);
 void run_conv_nchw(Ctx& c, const GemmW& w, const float* x_nchw, int B, int Hin, int Win, const Map& out, bool pad_to_stride = false);
-void run_layernorm(Ctx& c, const LNW& ln, const float* x, int rows, int ldx, float* y, int ldy, int y_coff, int y_planes = 0, int y_bf16 = 0);
+// where run_layernorm writes: a matrix or a Map window, fp32 unless said otherwise
+struct LnOut {
+    float* y; int ldy, y_coff = 0;
+    int y_planes = 0, y_s16 = 0;   // y_planes 2: the P2 layout (kernels/split_planes.h); y_s16: a 16-bit matrix (x stays fp32: the residual stream)
+    LnOut(float* y_, int ldy_) : y(y_), ldy(ldy_) {}
+    LnOut(const Map& m) : y(m.p), ldy(m.ld), y_coff(m.coff) {}
+    LnOut& planes(int n) { y_planes = n; return *this; }
+    LnOut& s16(int on) { y_s16 = on; return *this; }
+};
+void run_layernorm(Ctx& c, const LNW& ln, const float* x, int rows, int ldx, const LnOut& out);
 void run_resize(Ctx& c, const Map& in, const Map& out, bool accumulate = false);
 // compute mode BRN_BF16: x = A W^T + bias + x (fp32, in place) and y = LayerNorm(x) as a bf16 matrix in ONE launch where a row-owning
 // kernel covers the shape (N = 192: gemm_wstat_ln_bf16_kernel; N = 768 / 384: gemm_rowln_bf16_kernel); false = nothing enqueued
 // every_fused_kernel: also the kernels the model does not use by default (the op-level entry point exercises them all)
 bool linear_residual_ln(Ctx& c, const GemmW& w, const float* A, int M, int lda, float* x, const LNW& ln, float* y, int ldy, bool every_fused_kernel = false);
 
-// SwinTransformer::forward (swin.rs:768-797): outs[i] are destination windows (stage outputs after norm_i)
-void swin_forward(Ctx& c, const SwinW& w, const float* img_nchw, int B, int H, int W, const Map outs[4]);
 void swin_stage_dims(int H, int W, int patch, int hs[4], int ws[4]);
-struct SwinIn { const float* img; int H, W; const Map* outs; };   // one backbone input and its 4 destination windows
-// 1 or 2 inputs through the same weights in one pass over concatenated token rows; outs_f32: in compute mode BRN_BF16 the stage outputs
+struct SwinIn { const float* img; int H, W; const Map* outs; };   // one backbone input and its 4 destination windows (stage outputs after norm_i)
+// SwinTransformer::forward (swin.rs:768-797) of 1 or 2 inputs through the same weights in one pass over concatenated token rows; outs_f32: in compute mode BRN_BF16 the stage outputs
 // (norm_i of the fp32 residual stream) are written as fp32 maps (the mixed mode, whose decoder runs on fp32 maps)
 void swin_forward_multi(Ctx& c, const SwinW& w, const SwinIn* ins, int nin, int B, bool outs_f32 = false);
 // the attention half of one block (swin.rs:356-403), x is the norm1 output, y = proj(attn) (no residual) or += residual

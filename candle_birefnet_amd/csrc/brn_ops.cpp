@@ -95,7 +95,7 @@ brn_status brn_linear_forward(const float* x, int M, int K, const float* w, cons
         const int s16 = op_s16(wb);            // then the product runs on kernels/gemm_bf16.hip; y (and the residual) stay fp32
         with_arena((hipStream_t)stream, [&](Ctx& c) {
             const float* a = s16 ? round_to_s16(c, dx, (size_t)M * K, wb.f16) : dx;
-            run_gemm(c, g, a, M, K, dy, N, 0, dr, N, 0, nullptr, 1, 0, 0, s16 ? 1 : 0, s16 ? 1 : 0);
+            run_gemm(c, g, GemmIO(a, M, K).to(dy, N).add(dr, N).f32(s16 ? 1 : 0, s16 ? 1 : 0));
         }, s16);
         st.finish();
     });
@@ -125,8 +125,8 @@ brn_status brn_linear_residual_layer_norm_forward(const float* x, int M, int K, 
             // the residual stream is updated in place inside the model: here x_out starts as a copy of the residual
             if (!c.dry) BRN_HIP(hipMemcpyAsync(dxo, dr, (size_t)M * N * sizeof(float), hipMemcpyDeviceToDevice, c.stream));
             if (!linear_residual_ln(c, g, a, M, K, dxo, ln, yb, N, true)) {
-                run_gemm(c, g, a, M, K, dxo, N, 0, dxo, N, 0, nullptr, 0, 0, 0, bf ? 1 : 0, bf ? 1 : 0);
-                run_layernorm(c, ln, dxo, M, N, yb, N, 0, 0, bf ? 1 : 0);
+                run_gemm(c, g, GemmIO(a, M, K).to(dxo, N).add(dxo, N).f32(bf ? 1 : 0, bf ? 1 : 0));
+                run_layernorm(c, ln, dxo, M, N, LnOut(yb, N).s16(bf ? 1 : 0));
             }
             if (bf && !c.dry) BRN_HIP(launch_bf16_to_f32(yb, (size_t)M * N, dyo, c.stream, wb.f16));
         }, op_s16(wb));
@@ -255,7 +255,7 @@ brn_status brn_patch_merging_forward(const float* x, int B, int H, int W, int C,
                 p.ldy = 4 * C; p.mode = 1; p.H = H; p.W = W; p.Cin = C;
                 BRN_HIP(launch_layernorm(p, c.stream));
             }
-            run_gemm(c, red, pm, M2, 4 * C, dy, 2 * C, 0);
+            run_gemm(c, red, GemmIO(pm, M2, 4 * C).to(dy, 2 * C));
         });
         st.finish();
     });
@@ -339,12 +339,11 @@ brn_status brn_deform_conv2d_forward(const float* x, int B, int C, int H, int W,
         float* dy = st.out(y, (size_t)B * O * Ho * Wo);
         through_nhwc(stream, op_s16(wb), dx, B, C, Cp, H, W, dy, O, Ho, Wo, [&](Ctx& c, const Map& X, const Map& Y) {
             const int ldom = (3 * kk + 3) / 4 * 4;
-            Map OM; OM.B = B; OM.H = Ho; OM.W = Wo; OM.C = 3 * kk; OM.ld = ldom; OM.coff = 0;
-            OM.p = c.arena->alloc((size_t)B * Ho * Wo * ldom);
-            run_conv(c, om, X, OM, nullptr, 0, 0, 1);
+            const Map OM = Map(c.arena->alloc((size_t)B * Ho * Wo * ldom), B, Ho, Wo, ldom).window(0, 3 * kk);
+            run_conv(c, om, X, OM, ConvOpts().f32());
             const bool fused_sig = deform_fused_sigmoid(c, reg);
             if (!c.dry && !fused_sig) BRN_HIP(launch_mod_sigmoid2(OM.p, (size_t)B * Ho * Wo, ldom, 2 * kk, 3 * kk, c.stream));
-            run_conv(c, reg, X, Y, OM.p, ldom, 2 * kk, 0, fused_sig ? 1 : 0);
+            run_conv(c, reg, X, Y, ConvOpts().offsets(OM, 2 * kk, fused_sig));
         });
         st.finish();
     });

@@ -69,8 +69,6 @@ const brn_named_tensor* WeightTable::get(const std::string& name, std::initializ
     return t;
 }
 
-static inline int roundup(int x, int m) { return (x + m - 1) / m * m; }
-
 // one 16-bit buffer of a model (planes, bf16-storage matrix, fragments), with the same slack as the fp32 uploads
 void* DeviceOwner::upload_u16(const std::vector<uint16_t>& v) {
     void* d = nullptr;
@@ -82,12 +80,8 @@ void* DeviceOwner::upload_u16(const std::vector<uint16_t>& v) {
 }
 
 float half2_act_scale() {
-    static const float s = [] {
-        const char* e = getenv("BRN_H2_ASCALE");
-        const int k = e ? atoi(e) : 3;                  // log2 of the scale
-        return ldexpf(1.f, k < 0 ? 0 : (k > 8 ? 8 : k));
-    }();
-    return s;
+    const int k = switches().h2_ascale;                 // log2 of the scale
+    return ldexpf(1.f, k < 0 ? 0 : (k > 8 ? 8 : k));
 }
 
 // the 16-bit copy of the packed fp32 matrix pk [rows][K] that mode wb computes with (layouts: brn_pack.h)
@@ -95,8 +89,7 @@ static void attach_planes(DeviceOwner& own, WeightBuild wb, GemmW& g, const std:
     const size_t K = (size_t)g.K;
     if (wb.planes <= 0) return;
     if (wb.planes == BUILD_BF16) {
-        static const bool cm_off = getenv("BRN_CONV_CHUNK_MAJOR") && atoi(getenv("BRN_CONV_CHUNK_MAJOR")) == 0;
-        const size_t conv_taps = !cm_off && g.mode == GEMM_CONV_NHWC ? (size_t)g.kh * g.kw : 0;
+        const size_t conv_taps = switches().conv_chunk_major && g.mode == GEMM_CONV_NHWC ? (size_t)g.kh * g.kw : 0;
         const S16Storage s = pack_s16_storage(pk, K, wb.f16, conv_taps, (size_t)g.Cinp);
         g.wb = own.upload_u16(s.w);
         g.wb_chunk_major = s.chunk_major ? 1 : 0; g.wb_rows = (int)s.rows; g.wb_ld = (int)s.ld;
@@ -311,8 +304,7 @@ void build_aspp_weights(const WeightTable& wt, const std::string& ap, int deform
             attach_deform_frags(own, wb, d.regular, wt.get(cp + "regular_conv.weight", {PL, IC, k, k})->data);
             // offset_conv and modulator_conv stacked on N = 3 k^2, padded with zero filters to a multiple of 8 (3 / 27 / 147 -> 8 / 32 / 152): the
             // fp32 offset map then leaves the bf16 GEMM through its vector-store epilogue instead of the per-element one
-            static const bool pad8 = !(getenv("BRN_OFFMOD_PAD8") && atoi(getenv("BRN_OFFMOD_PAD8")) == 0);   // (A/B switch: 0 = pad to 4 as before)
-            const int n3p = roundup(3 * kk, pad8 ? 8 : 4);
+            const int n3p = roundup(3 * kk, switches().offmod_pad8 ? 8 : 4);   // (A/B switch BRN_OFFMOD_PAD8: 0 = pad to 4 as before)
             std::vector<float> w3((size_t)n3p * IC * kk, 0.f), b3((size_t)n3p, 0.f);
             memcpy(w3.data(), ow, (size_t)2 * kk * IC * kk * sizeof(float));
             memcpy(w3.data() + (size_t)2 * kk * IC * kk, mw, (size_t)kk * IC * kk * sizeof(float));
