@@ -318,12 +318,15 @@ brn_status brn_deform_conv2d_forward(const float* x, int B, int C, int H, int W,
         ensure_device(device);
         DeviceOwner own;
         // compute mode BRN_BF16 at op level (brn_set_op_compute): bf16 map in / out as inside the model, offsets / modulator fp32, the
-        // gather on kernels/deform_bf16.hip where the shape allows; every other mode runs the fp32-MFMA gather kernel.
+        // gather on kernels/deform_bf16.hip where the shape allows.  The plane modes (f32_split3 / f32_split2 / f32_half2) build both convs with
+        // the op's planes, as the ASPP and decoder-block entries do: the offset / modulator conv and the gather run on the split kernels
+        // (launch_gemm: deform_on_split).  Mode f32 and whatever those do not cover run the fp32-MFMA gather kernel.
         // Any in_channels (deform_conv.rs:29-36): the channels-last map is padded with zero channels to the kernels' granule (32; 64 for
         // the bf16 gather kernel), the weights with zero columns
         const bool bf = g_op.planes == BUILD_BF16 && (O % 8) == 0;
         const int Cp = (C + (bf ? 63 : 31)) / (bf ? 64 : 32) * (bf ? 64 : 32);
-        const WeightBuild wb = bf ? g_op : WeightBuild{};     // (a split mode builds fp32 here)
+        const bool pl = g_op.planes == 2 || g_op.planes == 3 || g_op.planes == BUILD_HALF2;
+        const WeightBuild wb = (bf || pl) ? g_op : WeightBuild{};
         std::vector<float> w3((size_t)3 * kk * C * kk), b3((size_t)3 * kk);
         memcpy(w3.data(), offset_w, (size_t)2 * kk * C * kk * sizeof(float));
         memcpy(w3.data() + (size_t)2 * kk * C * kk, mod_w, (size_t)kk * C * kk * sizeof(float));

@@ -304,6 +304,25 @@ GemmPlan plan_gemm(int M, int N, int K, int planes) {
     return pl;
 }
 
+// A deformable conv whose weights carry planes runs on the split kernels too (gemm_split.hip, DeformLoader): fp32 maps in and out, whole
+// K tiles inside a tap, and the batch of sampled maps within the loader's 32-bit byte offsets.  Everything else — mode f32, the 16-bit modes'
+// fallback shapes, the diag build's one-plane mode — keeps gemm_f32_kernel.
+static bool deform_on_split(const GemmParams& p) {
+    return p.mode == GEMM_DEFORM_NHWC && p.planes >= 2 && p.Wp && p.om && !p.a_bf16 && !p.c_bf16 && (p.Cin % 32) == 0 && p.K == p.kh * p.kw * p.Cin &&
+           ((p.lda | p.a_coff) & 3) == 0 && p.Hin + p.pad < 32768 && p.Win + p.pad < 32768 &&       // (a row's window origin is kept as two 16-bit halves)
+           ((double)p.M / ((double)p.Hout * p.Wout) + 1.0) * p.Hin * p.Win * p.lda * 4.0 < 2147483648.0;
+}
+// How it is launched: as the plain conv of the same mode and shape would be — plan_gemm with the planes: the same tile class (the warp-specialised
+// 128 x 128 kernel, or a 4-wave tile: 64 x 64 here, same MFMA and K order as 128 x 64) and the same split-K, so every output element is summed in
+// the order the mode's convs sum it (with zero offsets the two are bit-identical), on a plan tuned for these kernels.  The caller planned for
+// gemm_f32_kernel and sized the scratch for that plan's slices: never more slices than those (the partial layout does not depend on the tile).
+static int deform_split_plan(const GemmParams& p, int caller_slices, int& splitk) {
+    const GemmPlan pp = plan_gemm(p.M, p.N, p.K, p.planes);
+    splitk = pp.splitk < caller_slices ? pp.splitk : caller_slices;
+    if (splitk < 1) splitk = 1;
+    return gemm_split_is_ws(pp.cfg) ? 0 : 2;
+}
+
 hipError_t launch_gemm(const GemmParams& p_in, const GemmPlan& pl, float* ws, hipStream_t s) {
     if (p_in.M <= 0 || p_in.N <= 0 || p_in.K <= 0 || (p_in.K % BK) != 0) return hipErrorInvalidValue;
     if ((p_in.mode == GEMM_CONV_NHWC || p_in.mode == GEMM_DEFORM_NHWC) && (p_in.Cin % BK) != 0) return hipErrorInvalidValue;
@@ -313,7 +332,10 @@ hipError_t launch_gemm(const GemmParams& p_in, const GemmPlan& pl, float* ws, hi
     if (p.splitk > 1 && !ws) return hipErrorInvalidValue;
     if (p.a_bf16 && p.mode != GEMM_DEFORM_NHWC) return hipErrorInvalidValue;       // only the deformable loader reads bf16 maps here
     if (p.c_bf16 && (p.splitk > 1 || p.R || (p.planes > 0 && p.Wp && p.mode != GEMM_DEFORM_NHWC && p.mode != GEMM_GATHER_NCHW))) return hipErrorInvalidValue;
-    if (p.h2 && !(p.planes == 2 && p.Wp && (p.mode == GEMM_DENSE || p.mode == GEMM_CONV_NHWC))) p.h2 = 0;     // (the fp32-MFMA kernel reads W itself: nothing is scaled)
+    const bool deform_split = deform_on_split(p);
+    int deform_cfg = 0;
+    if (deform_split) deform_cfg = deform_split_plan(p, p.splitk, p.splitk);
+    if (p.h2 && !(p.planes == 2 && p.Wp && (p.mode == GEMM_DENSE || p.mode == GEMM_CONV_NHWC || deform_split))) p.h2 = 0;     // (the fp32-MFMA kernel reads W itself: nothing is scaled)
     if (p.h2 && !(p.a_scale > 0.f && p.out_scale > 0.f)) return hipErrorInvalidValue;
     if (p.a_planes || p.c_planes) {         // P2 layouts: 2-plane split mode, dense, on the warp-specialised kernel only
         if (!(p.planes == 2 || p.planes == 3) || !p.Wp || p.mode != GEMM_DENSE || !gemm_split_is_ws(pl.cfg)) return hipErrorInvalidValue;
@@ -322,6 +344,7 @@ hipError_t launch_gemm(const GemmParams& p_in, const GemmPlan& pl, float* ws, hi
     }
     hipError_t e;
     if (p.planes > 0 && p.Wp && (p.mode == GEMM_DENSE || p.mode == GEMM_CONV_NHWC)) e = launch_gemm_split(p, pl.cfg, s);   // split-bf16 path: tile choice by the same plan
+    else if (deform_split) e = launch_gemm_split(p, deform_cfg, s);
     else if (pl.cfg == 0) e = launch_cfg<128, 128, 2, 2>(p, s);
     else if (pl.cfg == 1) e = launch_cfg<128, 64, 2, 2>(p, s);
     else if (pl.cfg == 3) e = launch_cfg<128, 128, 2, 4>(p, s);

@@ -19,6 +19,135 @@ namespace brn {
 // =====================================================================================================================
 constexpr int SLD = 40;   // bf16 elements per LDS row
 
+// ---------------------------------------------------------------------------------------------------------------------
+// DeformLoader — the modulated-deformable A loader of both kernels below (MODE == GEMM_DEFORM_NHWC): the bilinear gather x modulator of
+// gemm_f32_kernel's loader (torchvision deform_conv2d, one offset group; a sample counts when y > -1 && y < Hin && x > -1 && x < Win, every
+// corner is tested on its own, rows >= M are zero), computed in fp32 while A is staged and handed to split4 / split4h like any other A value.
+// A staging thread holds one float4 (4 channels) of PA tile rows; the LPR lanes of a row are neighbours in the wave.
+//   * Sampling parameters are computed ONCE per (pixel, tap): lane q of a row's lane group owns (tile row q % PA, tap TPB blk + q / PA) of the
+//     current block of TPB = LPR / PA taps — offsets and modulator loaded one block ahead, floor / clamp / validity / four weights x modulator
+//     worked out once per block — and keeps ONE packed corner word and four weights.  Whoever stages a K tile of that (row, tap) fetches them
+//     with ds_bpermute (lanes of its own wave: no LDS bytes, no barrier), for each of the tap's Cin / KS K tiles.
+//   * Corners are clamped into the map and carry a zero weight when they are not real corners: no exec branch around a load (see
+//     load4_masked), so the corner loads of a later K tile stay in flight while an earlier one is blended, split and stored.  All four are
+//     buffer loads off one resource (the whole batch of maps: launch_gemm checks it spans < 2 GiB); the K tile's channel offset is uniform.
+//     The packed word is the byte offset of corner (yl, xl) — a multiple of 16 — with bit 0 / bit 1 saying whether the x / y neighbour is
+//     one pixel / one map row further or (clamped at a border) the same pixel.
+//   * The blend happens when the registers are consumed (finish), with the weights of the tile's tap: those live in two buffers by block
+//     parity, because the tile being blended may belong to the block before the one whose corners are being issued.
+// (A clamped corner's value is multiplied by a zero weight, not masked: a non-finite value there gives NaN, never a wrong finite number.
+// A NaN offset poisons its sample where gemm_f32_kernel's loader drops it: see param_compute.)
+// ---------------------------------------------------------------------------------------------------------------------
+template <int PA, int LPR>
+struct DeformLoader {
+    static constexpr int TPB = LPR / PA;
+    static_assert(TPB >= 1 && TPB * PA == LPR, "a row's lanes share out (tile row, tap) pairs evenly");
+    __amdgpu_buffer_rsrc_t rsrc;
+    int kq16, grp4;               // this lane's 16 bytes inside a K tile; 4 x the first lane of the row's lane group (ds_bpermute addresses bytes)
+    int pixb, rowb, ntaps;
+    // owner role (kept small: the staging waves of the warp-specialised kernel live within 128 VGPRs)
+    int o_yx;                     // the row's window origin, (iy << 16) | (ix & 0xffff)
+    unsigned o_img, o_om;         // byte offset of its image; element offset of its offsets / modulator row
+    float om_y, om_x, om_m;       // offsets / modulator of the owner's tap in the next block
+    unsigned own_off;
+    float own_w[2][4];
+    int cur_blk;
+
+    __device__ __forceinline__ void init(const GemmParams& p, int m0, int lrow, int rpp, int kq, int lane) {
+        rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.A + p.a_coff), 0, 0x7fffffff, 0x00020000);
+        kq16 = kq * 16;
+        grp4 = (lane & ~(LPR - 1)) * 4;
+        pixb = p.lda * 4;
+        rowb = p.Win * pixb;
+        ntaps = p.kh * p.kw;
+        const int m = m0 + lrow + (kq % PA) * rpp;
+        const int mm = min(m, p.M - 1);
+        const int hw = p.Hout * p.Wout;
+        const int b = mm / hw, rem = mm - b * hw;
+        const int oy = rem / p.Wout, ox = rem - oy * p.Wout;
+        // a row >= M reads row M - 1's offsets from an origin far above the map: never inside, so it is staged as zeros (launch_gemm bounds the geometry)
+        const int iy = m < p.M ? oy * p.stride - p.pad : -32768, ix = ox * p.stride - p.pad;
+        o_yx = (int)(((unsigned)iy << 16) | ((unsigned)ix & 0xffffu));
+        o_img = (unsigned)b * (unsigned)(p.Hin * rowb);
+        o_om = (unsigned)mm * (unsigned)p.om_ld;
+        om_y = om_x = om_m = 0.f;
+        own_off = 0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) own_w[0][c] = own_w[1][c] = 0.f;
+        cur_blk = -1;
+    }
+    __device__ __forceinline__ void param_load(const GemmParams& p, int blk) {
+        const int tap = min(blk * TPB + (kq16 >> 4) / PA, ntaps - 1);
+        const float* om = p.om + o_om;
+        om_y = om[2 * tap]; om_x = om[2 * tap + 1]; om_m = om[p.om_mask_off + tap];
+    }
+    __device__ __forceinline__ void param_compute(const GemmParams& p, int blk) {
+        const int tap = min(blk * TPB + (kq16 >> 4) / PA, ntaps - 1);
+        const int ky = tap / p.kw, kx = tap - ky * p.kw;
+        const float y = (float)((o_yx >> 16) + ky * p.dil) + om_y;
+        const float x = (float)((short)o_yx + kx * p.dil) + om_x;
+        const bool inside = y > -1.f && y < (float)p.Hin && x > -1.f && x < (float)p.Win;
+        const float yf = floorf(y), xf = floorf(x);
+        const float ly = y - yf, lx = x - xf, hy = 1.f - ly, hx = 1.f - lx;
+        // (an inside sample has yl in [-1, Hin - 1]; the clamps tame NaN and huge offsets: such a sample is not inside, every weight is zero)
+        const int yl = (int)fminf(fmaxf(yf, -1.f), (float)(p.Hin - 1)), xl = (int)fminf(fmaxf(xf, -1.f), (float)(p.Win - 1));
+        const bool yl_ok = yl >= 0, yh_ok = yl + 1 <= p.Hin - 1, xl_ok = xl >= 0, xh_ok = xl + 1 <= p.Win - 1;
+        // (selects, not a multiply by 0: ly / lx of a sample that is not inside may be NaN.)  A NaN position is not "outside": the offsets come
+        // from a conv of the same mode, and beyond f32_half2's range that conv answers NaN — the sample is poisoned, not dropped, so that the
+        // result stays non-finite instead of silently losing a tap.
+        const float out = (y != y || x != x) ? __builtin_nanf("") : 0.f;
+        const float w0 = (inside && yl_ok && xl_ok) ? om_m * (hy * hx) : out;
+        const float w1 = (inside && yl_ok && xh_ok) ? om_m * (hy * lx) : out;
+        const float w2 = (inside && yh_ok && xl_ok) ? om_m * (ly * hx) : out;
+        const float w3 = (inside && yh_ok && xh_ok) ? om_m * (ly * lx) : out;
+        const bool odd = blk & 1;
+        own_w[0][0] = odd ? own_w[0][0] : w0; own_w[1][0] = odd ? w0 : own_w[1][0];
+        own_w[0][1] = odd ? own_w[0][1] : w1; own_w[1][1] = odd ? w1 : own_w[1][1];
+        own_w[0][2] = odd ? own_w[0][2] : w2; own_w[1][2] = odd ? w2 : own_w[1][2];
+        own_w[0][3] = odd ? own_w[0][3] : w3; own_w[1][3] = odd ? w3 : own_w[1][3];
+        const int ylc = max(yl, 0), xlc = max(xl, 0);
+        // x / y neighbour distinct from the clamped low corner: only when both are real pixels
+        own_off = (o_img + (unsigned)(ylc * p.Win + xlc) * (unsigned)pixb) | ((xl_ok && xh_ok) ? 1u : 0u) | ((yl_ok && yh_ok) ? 2u : 0u);
+    }
+    // the four corner loads of K tile [k0, k0 + KS) for tile rows [I0, I1) of this thread; called with ascending k0
+    template <int I0, int I1>
+    __device__ __forceinline__ void issue(const GemmParams& p, int k0, f32x4 (&qc)[PA][4]) {
+        const int tap = k0 / p.Cin, ci0 = k0 - tap * p.Cin;
+        const int blk = tap / TPB;
+        if (blk != cur_blk) {                       // uniform: a new block of taps
+            if (cur_blk < 0) param_load(p, blk);    // (the first tile of a split-K slice)
+            param_compute(p, blk);
+            cur_blk = blk;
+            if ((blk + 1) * TPB < ntaps) param_load(p, blk + 1);
+        }
+        const int src = grp4 + (tap - blk * TPB) * (PA * 4);
+#pragma unroll
+        for (int i = I0; i < I1; ++i) {
+            const unsigned v = (unsigned)__builtin_amdgcn_ds_bpermute(src + i * 4, (int)own_off);
+            const unsigned o = (v & ~3u) + (unsigned)kq16;
+            const unsigned sx = (v & 1u) ? (unsigned)pixb : 0u, sy = (v & 2u) ? (unsigned)rowb : 0u;
+            qc[i][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, o, ci0 * 4, 0));
+            qc[i][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, o + sx, ci0 * 4, 0));
+            qc[i][2] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, o + sy, ci0 * 4, 0));
+            qc[i][3] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, o + sx + sy, ci0 * 4, 0));
+        }
+    }
+    // modulator x bilinear blend of row i of the K tile that starts at k0 (its corners: qc)
+    __device__ __forceinline__ f32x4 finish(const GemmParams& p, int k0, int i, const f32x4 (&qc)[4]) const {
+        const int tap = k0 / p.Cin, blk = tap / TPB;
+        const int src = grp4 + (tap - blk * TPB) * (PA * 4) + i * 4;
+        const bool odd = blk & 1;
+        float w[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            w[c] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src, __builtin_bit_cast(int, odd ? own_w[1][c] : own_w[0][c])));
+        f32x4 r;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) r[e] = fmaf(w[3], qc[3][e], fmaf(w[2], qc[2][e], fmaf(w[1], qc[1][e], w[0] * qc[0][e])));
+        return r;
+    }
+};
+
 template <int BM, int BN, int WM, int WN, int MODE, int NP, bool H = false>   // H: the two planes are fp16 (mode f32_half2)
 __global__ void __launch_bounds__(WM* WN * 64) gemm_split_kernel(const GemmParams p) {
     static_assert(!H || NP == 2, "fp16 planes come in pairs");
@@ -58,6 +187,13 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_split_kernel(const GemmParam
     f32x4 ra[2][PA];
     bf16x8 rb[2][NP][PB];
     unsigned am[2][PA];
+    // The deformable loader (DeformLoader above): a staged row is its four corner float4s, blended at the LDS store.  Two sets of those
+    // would cost the workgroups per CU that hide this kernel's latencies, so there is one (rc, for K tile rk), loaded one tile ahead.
+    constexpr bool DEFORM = MODE == GEMM_DEFORM_NHWC;
+    f32x4 rc[DEFORM ? PA : 1][4];
+    int rk = 0;
+    DeformLoader<PA, 8> dl;
+    if constexpr (DEFORM) dl.init(p, m0, lrow, RPP, kq, lane);
 
     auto gload = [&](int kt, f32x4 (&qa)[PA], bf16x8 (&qb)[NP][PB], unsigned (&qm)[PA]) {
         const int k0 = kt * BK;
@@ -66,7 +202,10 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_split_kernel(const GemmParam
 #pragma unroll
             for (int i = 0; i < PB; ++i)
                 qb[pl][i] = *reinterpret_cast<const bf16x8*>(wsrc + (long)i * WRPP * wrow_stride + (long)kt * (NP * 32) + pl * 32);
-        if (MODE == GEMM_DENSE) {
+        if constexpr (DEFORM) {
+            rk = k0;
+            dl.template issue<0, PA>(p, k0, rc);
+        } else if (MODE == GEMM_DENSE) {
 #pragma unroll
             for (int i = 0; i < PA; ++i)
                 {
@@ -89,7 +228,10 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_split_kernel(const GemmParam
 #pragma unroll
         for (int i = 0; i < PA; ++i) {
             bf16x4 sp[NP];
-            if constexpr (H) split4h<true>(qa[i], qm[i], p.a_scale, sp); else split4<NP>(qa[i], qm[i], sp);
+            if constexpr (DEFORM) {
+                const f32x4 v = dl.finish(p, rk, i, rc[i]);
+                if constexpr (H) split4h<false>(v, 0xffffffffu, p.a_scale, sp); else split4<NP, false>(v, 0xffffffffu, sp);
+            } else if constexpr (H) split4h<true>(qa[i], qm[i], p.a_scale, sp); else split4<NP>(qa[i], qm[i], sp);
 #pragma unroll
             for (int pl = 0; pl < NP; ++pl)
                 *reinterpret_cast<bf16x4*>(As + (pl * BM + lrow + i * RPP) * SLD + kq * 4) = sp[pl];
@@ -141,6 +283,22 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_split_kernel(const GemmParam
         }
     };
 
+    if constexpr (DEFORM) {
+        if (kt0 < nk) {
+            gload(kt0, ra[0], rb[0], am[0]);
+            lds_store(ra[0], rb[0], am[0]);
+        }
+        __syncthreads();
+        for (int kt = kt0; kt < nk; ++kt) {
+            if (kt + 1 < nk) gload(kt + 1, ra[0], rb[0], am[0]);
+            compute();
+            __syncthreads();
+            if (kt + 1 < nk) {
+                lds_store(ra[0], rb[0], am[0]);
+                __syncthreads();
+            }
+        }
+    } else {
     if (kt0 < nk) {
         gload(kt0, ra[0], rb[0], am[0]);
         if (kt0 + 1 < nk) gload(kt0 + 1, ra[1], rb[1], am[1]);
@@ -163,6 +321,7 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_split_kernel(const GemmParam
         if (kt + 1 < nk) BRN_SPLIT_STEP(kt + 1, 1, 0)
     }
 #undef BRN_SPLIT_STEP
+    }
     gemm_epilogue<TM, TN, WTM, WTN>(p, acc, m0, n0, wm, wn, lane, slice, reinterpret_cast<float*>(smem_raw) + wave * EPI_WAVE_FLOATS);
 }
 
@@ -182,7 +341,9 @@ template <int MODE, int NP, int KS, bool DIAG, bool APL, bool H = false>   // AP
 #ifndef BRN_WS_M16
 #define BRN_WS_M16 1          // 2-plane, 32-deep stages: the consumers issue 16 x 16 x 32 MFMAs (0: 32 x 32 x 16, same-box A/B builds)
 #endif
-__global__ void __launch_bounds__(512) gemm_split_ws_kernel(const GemmParams p) {
+// (the deformable producers hold four corners per staged row: the 2-plane form is told to stay within the 128 VGPRs of two workgroups per CU)
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MODE == GEMM_DEFORM_NHWC && NP == 2 ? 4 : 1)))
+gemm_split_ws_kernel(const GemmParams p) {
     constexpr int BM = 128, BN = 128, WTM = 64, WTN = 64, TM = 2, TN = 2;
     static_assert(!APL || ((NP == 2 || NP == 3) && MODE == GEMM_DENSE), "the P input layout is the NP-plane split of a dense A");
     static_assert(!H || NP == 2, "fp16 planes come in pairs");
@@ -371,6 +532,57 @@ __global__ void __launch_bounds__(512) gemm_split_ws_kernel(const GemmParams p) 
                 for (int i = 0; i < PB; ++i)
                     *reinterpret_cast<bf16x8*>(Bs + (pl * BN + wrow + i * WRPP) * SLD + w_sw) = qb[pl][i];
         };
+        if constexpr (MODE == GEMM_DEFORM_NHWC) {
+        // The deformable loader (DeformLoader above).  A staged row is four corner float4s: two register sets of those are more than the
+        // 128 VGPRs of two workgroups per CU hold, so there is one, and a tile's rows go in two halves: blend, split and store half h of tile
+        // u, then issue half h of tile u + 1.  The corner loads of the next tile are then in flight across the other half's split and LDS
+        // stores, the barrier and the consumers' K tile.  W has one register set as well, loaded one tile ahead.
+        static_assert(!APL && !DIAG && NBUF == 2 && PA % 2 == 0, "the deformable producer: plain A, the 2-deep ring, rows in two halves");
+        constexpr int HR = PA / 2;
+        DeformLoader<PA, AQ> dl;
+        dl.init(p, m0, lrow, RPP, kq, lane);
+        f32x4 rc[PA][4];
+        auto a_store = [&](int t, int i, const f32x4 v) {
+            __bf16* As = smem + (t % NBUF) * BUF;
+            bf16x4 sp[NP];
+            if constexpr (H) split4h<false>(v, 0xffffffffu, p.a_scale, sp); else split4<NP, false>(v, 0xffffffffu, sp);
+#pragma unroll
+            for (int pl = 0; pl < NP; ++pl) *reinterpret_cast<bf16x4*>(As + (pl * BM + lrow + i * RPP) * SLD + a_sw) = sp[pl];
+            __builtin_amdgcn_sched_barrier(0);      // one row at a time: interleaved rows' temporaries do not fit beside the corners in flight
+        };
+        auto w_store = [&](int t, const bf16x8 (&qb)[NP][PB]) {
+            __bf16* Bs = smem + (t % NBUF) * BUF + AREG;
+#pragma unroll
+            for (int pl = 0; pl < NP; ++pl)
+#pragma unroll
+                for (int i = 0; i < PB; ++i) *reinterpret_cast<bf16x8*>(Bs + (pl * BN + wrow + i * WRPP) * SLD + w_sw) = qb[pl][i];
+        };
+        // prologue: LDS tile 0 stored, the corners and the W planes of tile 1 in flight
+        if (nt > 0) { wload(kt0, rb[0]); dl.template issue<0, PA>(p, kt0 * KS, rc); }
+        if (nt > 0) {
+#pragma unroll
+            for (int i = 0; i < PA; ++i) a_store(0, i, dl.finish(p, kt0 * KS, i, rc[i]));
+            w_store(0, rb[0]);
+        }
+        if (nt > 1) { dl.template issue<0, PA>(p, (kt0 + 1) * KS, rc); wload(kt0 + 1, rb[0]); }
+        __syncthreads();
+        // step t (the consumers multiply tile t): stage tile u = t + 1
+        for (int t = 0; t < nt; ++t) {
+            const int u = t + 1;
+            if (u < nt) {
+                const int k0 = (kt0 + u) * KS;
+#pragma unroll
+                for (int i = 0; i < HR; ++i) a_store(u, i, dl.finish(p, k0, i, rc[i]));
+                if (u + 1 < nt) dl.template issue<0, HR>(p, k0 + KS, rc);
+#pragma unroll
+                for (int i = HR; i < PA; ++i) a_store(u, i, dl.finish(p, k0, i, rc[i]));
+                if (u + 1 < nt) dl.template issue<HR, PA>(p, k0 + KS, rc);
+                w_store(u, rb[0]);
+                if (u + 1 < nt) wload(kt0 + u + 1, rb[0]);
+            }
+            __syncthreads();
+        }
+        } else {
         constexpr int AHEAD = NBUF - 1;     // LDS tiles the producers run ahead of the consumers
         // prologue: LDS tiles 0 .. AHEAD-1 stored, register sets hold the next two tiles
         if (nt > 0) gload(0, ra[0], rb[0], am[0]);
@@ -401,6 +613,7 @@ __global__ void __launch_bounds__(512) gemm_split_ws_kernel(const GemmParams p) 
             if (t + 1 < nt) BRN_PROD_STEP(t + 1, (AHEAD + 1) & 1)
         }
 #undef BRN_PROD_STEP
+        }   // (the register-staged producers)
         if (trc && tid == 256) { trc[8 + 4] = clock64(); trc[8 + 5] = wall_clock64(); }
     } else if constexpr (BRN_WS_M16 != 0 && KS == 32 && NP == 2 && !DIAG) {
     // ---- consumers, 16 x 16 x 32 MFMAs (round 4): the same cycles per flop as 32 x 32 x 16, but the chip holds a higher clock under the smaller
@@ -567,6 +780,7 @@ static hipError_t launch_split_ws_ks(const GemmParams& p, dim3 grid, hipStream_t
                 hipLaunchKernelGGL((gemm_split_ws_kernel<GEMM_DENSE, 2, 32, false, true, true>), grid, block, 0, s, p);
             } else if (p.mode == GEMM_DENSE) hipLaunchKernelGGL((gemm_split_ws_kernel<GEMM_DENSE, 2, 32, false, false, true>), grid, block, 0, s, p);
             else if (p.mode == GEMM_CONV_NHWC) hipLaunchKernelGGL((gemm_split_ws_kernel<GEMM_CONV_NHWC, 2, 32, false, false, true>), grid, block, 0, s, p);
+            else if (p.mode == GEMM_DEFORM_NHWC) hipLaunchKernelGGL((gemm_split_ws_kernel<GEMM_DEFORM_NHWC, 2, 32, false, false, true>), grid, block, 0, s, p);
             else return hipErrorInvalidValue;
             return hipGetLastError();
         }
@@ -588,6 +802,10 @@ static hipError_t launch_split_ws_ks(const GemmParams& p, dim3 grid, hipStream_t
 #endif
     if (p.mode == GEMM_DENSE) hipLaunchKernelGGL((gemm_split_ws_kernel<GEMM_DENSE, NP, KS, false, false>), grid, block, 0, s, p);
     else if (p.mode == GEMM_CONV_NHWC) hipLaunchKernelGGL((gemm_split_ws_kernel<GEMM_CONV_NHWC, NP, KS, false, false>), grid, block, 0, s, p);
+    else if (p.mode == GEMM_DEFORM_NHWC) {
+        if constexpr (NP >= 2 && KS == 32) hipLaunchKernelGGL((gemm_split_ws_kernel<GEMM_DEFORM_NHWC, NP, 32, false, false>), grid, block, 0, s, p);
+        else return hipErrorInvalidValue;
+    }
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
@@ -597,7 +815,8 @@ static hipError_t launch_split_ws(const GemmParams& p, hipStream_t s) {
     const dim3 grid(tiles);
     // 3 planes: 32-deep stages need 120 KB of LDS (one workgroup per CU); 16-deep stages (2 x 36 KB) let two share a CU like the
     // 2-plane kernel's do, at twice the barriers per K: worth it as soon as there is more than one workgroup per CU to place
-    if (NP == 3 && tiles > 256 && !(p.abl || p.trace)) return launch_split_ws_ks<NP, 16>(p, grid, s);
+    // (the deformable loader is built for 32-deep stages only)
+    if (NP == 3 && tiles > 256 && !(p.abl || p.trace) && p.mode != GEMM_DEFORM_NHWC) return launch_split_ws_ks<NP, 16>(p, grid, s);
     return launch_split_ws_ks<NP, 32>(p, grid, s);
 }
 
@@ -609,6 +828,10 @@ static hipError_t launch_split_cfg(const GemmParams& p, hipStream_t s) {
         if constexpr (NP == 2) {
             if (p.mode == GEMM_DENSE) hipLaunchKernelGGL((gemm_split_kernel<BM, BN, WM, WN, GEMM_DENSE, 2, true>), grid, block, 0, s, p);
             else if (p.mode == GEMM_CONV_NHWC) hipLaunchKernelGGL((gemm_split_kernel<BM, BN, WM, WN, GEMM_CONV_NHWC, 2, true>), grid, block, 0, s, p);
+            else if (p.mode == GEMM_DEFORM_NHWC) {
+                if constexpr (BM == 64 && BN == 64) hipLaunchKernelGGL((gemm_split_kernel<64, 64, WM, WN, GEMM_DEFORM_NHWC, 2, true>), grid, block, 0, s, p);
+                else return hipErrorInvalidValue;
+            }
             else return hipErrorInvalidValue;
             return hipGetLastError();
         }
@@ -616,6 +839,10 @@ static hipError_t launch_split_cfg(const GemmParams& p, hipStream_t s) {
     }
     if (p.mode == GEMM_DENSE) hipLaunchKernelGGL((gemm_split_kernel<BM, BN, WM, WN, GEMM_DENSE, NP>), grid, block, 0, s, p);
     else if (p.mode == GEMM_CONV_NHWC) hipLaunchKernelGGL((gemm_split_kernel<BM, BN, WM, WN, GEMM_CONV_NHWC, NP>), grid, block, 0, s, p);
+    else if (p.mode == GEMM_DEFORM_NHWC) {
+        if constexpr (NP >= 2 && BM == 64 && BN == 64) hipLaunchKernelGGL((gemm_split_kernel<64, 64, WM, WN, GEMM_DEFORM_NHWC, NP>), grid, block, 0, s, p);   // (launch_gemm's deformable tiles: this one and the warp-specialised kernel)
+        else return hipErrorInvalidValue;
+    }
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }

@@ -53,7 +53,9 @@ typedef enum { BRN_MEM_HOST = 0, BRN_MEM_DEVICE = 1 } brn_mem;
  *                      lands in (2^13, 2^14]; activations: by 8), 3 fp16 MFMAs per product (hh, hl, lh), fp32 accumulate, the
  *                      accumulator un-scaled exactly: ~2^-22 relative per product — fp32-class accuracy at twice BRN_F32_SPLIT3's
  *                      matrix rate.  Range: a GEMM input activation of magnitude >= 8190 overflows fp16 and the logits come back
- *                      NaN (never silently wrong); BRN_F32_SPLIT3 has fp32's full range.
+ *                      NaN (never silently wrong); BRN_F32_SPLIT3 has fp32's full range.  A deformable convolution's GEMM input is
+ *                      modulator x bilinear sample, up to 2 |x|: there the ceiling on the sampled map is half that, 4095.  Beyond it the
+ *                      result is non-finite as well (an offset that is itself NaN poisons its sample instead of dropping it).
  *   BRN_BF16_OPERANDS  operands rounded to bf16, fp32 accumulate, fp32 storage: superseded by BRN_BF16; the value is reserved, the
  *                      product library answers BRN_ERR_INVALID_ARG (only libbirefnet_hip_diag.so, `make diag`, still builds it)
  *   BRN_BF16           the bf16 throughput mode of BASELINE configs[2..4]: activations AND weights live in HBM as bf16,
@@ -248,7 +250,9 @@ brn_status brn_window_attention_forward(const float* x, int B, int H, int W, int
 brn_status brn_patch_merging_forward(const float* x, int B, int H, int W, int C, const float* norm_g,
                                      const float* norm_b, const float* reduction_w, float* y, brn_mem loc,
                                      int device_ordinal, void* stream);
-/* DeformableConv2d::forward (deform_conv.rs:82-99 / :101-215), NCHW.  mode = brn_deform_mode.
+/* DeformableConv2d::forward (deform_conv.rs:82-99 / :101-215), NCHW.  mode = brn_deform_mode.  Runs in the arithmetic selected with
+ * brn_set_op_compute, like brn_conv2d_forward: in BRN_F32_SPLIT3 / BRN_F32_SPLIT2 / BRN_F32_HALF2 the offset / modulator conv and the
+ * modulated gather x weights both multiply that mode's planes (the gather itself — bilinear blend x modulator — is fp32).
  * offset_w [2k^2,C,k,k]+offset_b, mod_w [k^2,C,k,k]+mod_b, w [O,C,k,k], bias [O] or NULL. */
 brn_status brn_deform_conv2d_forward(const float* x, int B, int C, int H, int W,
                                      const float* offset_w, const float* offset_b,
