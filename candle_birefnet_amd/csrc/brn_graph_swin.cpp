@@ -41,6 +41,7 @@ static bool swin_attention_multi(Ctx& c, const SwinBlockW& blk, const float* xn,
             p.planes = (!c.bf16 && window == 12 && (blk.qkv.planes == 2 || blk.qkv.planes == 1)) ? blk.qkv.planes : 0;
             p.h2 = (p.planes == 2 && blk.qkv.half && switches().h2_att) ? 1 : 0;
             if (blk.qkv.half && !p.h2) p.planes = 0;        // BRN_H2_ATT=0: the fp32-MFMA kernel, like f32_split3
+            p.pack_q = switches().att_pack_q;
             p.out_planes = p2;
             p.out_h2 = (p2 == 2 && blk.qkv.half) ? c.h2_scale : 0.f;
             nwin += (double)B * (p.Hp / window) * (p.Wp / window) * blk.heads;

@@ -106,6 +106,7 @@ static inline int roundup(int x, int m) { return (x + m - 1) / m * m; }
     X(patch_ln,         "BRN_PATCH_LN",          1,  "0 = PatchEmbed as gather GEMM + LayerNorm in the 16-bit modes too; 2 = fused without the first block's norm1") \
     X(p1_f32,           "BRN_P1_F32",            1,  "0 = the decoder's last map p1 is a 16-bit map like every other in the 16-bit modes")     \
     X(h2_att,           "BRN_H2_ATT",            1,  "0 = mode f32_half2 runs the fp32-MFMA attention kernel instead of the fp16-pair one")     \
+    X(att_pack_q,       "BRN_ATT_PACK_Q",        1,  "0 = the split / bf16 attention kernels compute the pad queries too, windows in grid order; 2 = real queries only, grid order") \
     X(h2_ascale,        "BRN_H2_ASCALE",         3,  "log2 of the scale of GEMM input activations before the fp16 split of mode f32_half2 (0 .. 8)") \
     X(deform_f32,       "BRN_DEFORM_F32_KERNEL", 0,  "1 = the 16-bit modes run deformable convolutions on the fp32-MFMA gather kernel")        \
     X(planes_kernel,    "BRN_PLANES_KERNEL",     0,  "1 = split modes with P-layout A on the LDS-DMA plane kernel (diag build only)")           \

@@ -152,6 +152,8 @@ struct WindowAttnParams {
     float out_h2;         // > 0 (with out_planes == 2, planes == 0 or h2): fp16 planes of out_h2 * out (mode f32_half2, written by the fp32-MFMA kernel)
     int ws;               // window side: 12 (0 = 12) or 7 (Swin-T / S: fp32 kernel only)
     int io_bf16;          // 1: qkv and out are bf16 matrices (compute mode BRN_BF16; qkv_bias / rel_table stay fp32)
+    int pack_q;           // split / bf16 kernels at window 12 (BRN_ATT_PACK_Q): 1 = real queries only, windows with the most query tiles first;
+                          // 2 = real queries only, grid order; 0 = all 144 positions of every window (kernels/window_geometry.h)
 };
 hipError_t launch_window_attention(const WindowAttnParams& p, hipStream_t s);
 // two maps of the same stage in one launch (p2 may be null)

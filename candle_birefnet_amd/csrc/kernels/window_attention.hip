@@ -22,6 +22,7 @@
 //                               the same key permutation.  No transpose, no LDS round trip for P.
 #include "../brn_kernels.h"
 #include "split_planes.h"
+#include "window_geometry.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -37,7 +38,8 @@ constexpr int ATT_THREADS = 192;   // 3 waves, 3 query tiles each
 
 // Both kernels take TWO geometries (the full- and the half-scale map of a co-batched backbone pass, same C / heads / shift):
 // blocks [0, nblk0) work on pa, the rest on pb — one launch, one ramp and one tail instead of two (the half-scale launch alone
-// fills a fifth of the CU slots).  nblk0 = all blocks when there is only one map.
+// fills a fifth of the CU slots).  nblk0 = all blocks when there is only one map.  (The split and the bf16 kernel take a WindowOrder
+// instead: the same two geometries, their windows in the order the launcher chose.)
 // WSZ = window side: 12 (Swin-B / L, swin.rs:60,74) or 7 (Swin-T / S, swin.rs:32,46); head_dim is 32 in all four configurations.
 // A window holds WSZ^2 tokens = NT16 key / query tiles of 16; the tail of the last tile (49 -> 64) is dummy: zero K / V rows, scores
 // forced to -3e38 so that they leave the softmax, queries never stored.
@@ -261,7 +263,26 @@ __global__ void __launch_bounds__(NWV * 64) window_attention_f32_kernel(const Wi
 //                       of an MFMA over key tiles (2t, 2t+1) are ordered so that lane group g contracts keys 16*(2t)+4g+0..3
 //                       and 16*(2t+1)+4g+0..3 — exactly the keys whose P^T values the lane already holds in its S^T
 //                       accumulators (C/D map row = 4g + reg) — so P never leaves registers.
+// Queries: the REAL tokens of the window only, packed into 16-query tiles (kernels/window_geometry.h) — the reference crops a pad
+// token's output row (swin.rs:387-401), and a query's result depends on its own lane group only, so the rows that are stored keep
+// their bits.  Pad tokens stay KEYS.  A window on the padded border has fewer tiles (a corner window of the 32 x 32 map: 64 real
+// queries = 4 tiles of 9); the launcher orders the windows so that those workgroups come last (WindowOrder).
 // =====================================================================================================================
+// which (window, head) a workgroup of the split / bf16 kernels works on: grid = (windows, heads or head groups), flattened x-major;
+// ord.heads_inner puts the workgroups of one window next to each other and the windows in ord's order (most query tiles first)
+struct AttBlock { WindowId win; int head; };
+__device__ __forceinline__ AttBlock att_block(const WindowOrder& ord) {
+    int flat = blockIdx.x, head = blockIdx.y;
+    if (ord.heads_inner) {
+        const int f = blockIdx.y * gridDim.x + blockIdx.x;
+        flat = f / (int)gridDim.y;
+        head = f - flat * (int)gridDim.y;
+    }
+    AttBlock r;
+    r.win = order_window(ord, flat);
+    r.head = head;
+    return r;
+}
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
@@ -274,9 +295,10 @@ __device__ __forceinline__ int kswz(int key) { return (0x78 >> (2 * ((key >> 2) 
 // un-scaled exactly.  ~2^-22 relative per product instead of 2^-16.
 constexpr float ATT_H_QKV = 8.0f, ATT_H_P = 2048.0f;
 template <int NP, bool H = false>
-__global__ void __launch_bounds__(ATT_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3))) window_attention_split_kernel(const WindowAttnParams pa, const WindowAttnParams pb, const int nblk0) {
+__global__ void __launch_bounds__(ATT_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3))) window_attention_split_kernel(const WindowAttnParams pa, const WindowAttnParams pb, const WindowOrder ord) {
     static_assert(!H || NP == 2, "fp16 planes come in pairs");
-    const bool second = (int)blockIdx.x >= nblk0;
+    const AttBlock blk = att_block(ord);
+    const bool second = blk.win.geom != 0;
     const WindowAttnParams& p = second ? pb : pa;
     __shared__ __attribute__((aligned(16))) __bf16 Kp[NP * NTOK * HD];
     __shared__ __attribute__((aligned(16))) __bf16 Vt[NP * HD * VT_LD];
@@ -287,12 +309,13 @@ __global__ void __launch_bounds__(ATT_THREADS) __attribute__((amdgpu_waves_per_e
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, g = lane >> 4;
-    const int head = blockIdx.y;
-    const int nWw = p.Wp / WS, nW = (p.Hp / WS) * nWw;
-    const int bw = second ? (int)blockIdx.x - nblk0 : (int)blockIdx.x;
-    const int b = bw / nW, w = bw - b * nW;
-    const int wr = w / nWw, wc = w - wr * nWw;
+    const int head = blk.head;
+    const int nWw = p.Wp / WS;
+    const int b = blk.win.b, wr = blk.win.wr, wc = blk.win.wc;
     const int C = p.C, C3 = 3 * C;
+    // the query slots of this window: its real tokens only (a pad query's row is cropped, swin.rs:387-401; pad KEYS stay), wave-uniform
+    const WindowReal wg = window_real(wr, wc, p.shift, p.H, p.W, p.Hp, p.Wp, ord.pack != 0);
+    const int nq = wg.nq, ntile = window_tiles(wg);
     // the shift mask (swin.rs:283-296) is non-zero only in the last row / column of windows; elsewhere the old form added +0.0 to every
     // score, which the result cannot see (a -0.0 score becomes +0.0; max and exp treat them alike)
     const bool has_mask = p.shift > 0 && (wr == p.Hp / WS - 1 || wc == nWw - 1);
@@ -334,10 +357,12 @@ __global__ void __launch_bounds__(ATT_THREADS) __attribute__((amdgpu_waves_per_e
     const f32x4 qbias0 = *reinterpret_cast<const f32x4*>(qbp);
     const f32x4 qbias1 = *reinterpret_cast<const f32x4*>(qbp + 4);
     // the Q fragment of the NEXT query tile is requested while this one is multiplied (8 registers; all three up front cost occupancy)
-    int qsrc_n;
+    // (a slot past nq — the tail of the last tile, or a wave with no tile — reads the last real query's row and is never stored)
+    int qsrc_n, qtok_n;
     f32x4 qn0, qn1;
-    auto load_q = [&](int qtok) {
-        qsrc_n = tok_src(qtok);
+    auto load_q = [&](int slot) {
+        qtok_n = slot_token(wg, min(slot, nq - 1));
+        qsrc_n = tok_src(qtok_n);
         const float* qp = p.qkv + (long)max(qsrc_n, 0) * C3 + head * HD + g * 8;
         qn0 = *reinterpret_cast<const f32x4*>(qp);
         qn1 = *reinterpret_cast<const f32x4*>(qp + 4);
@@ -418,8 +443,9 @@ __global__ void __launch_bounds__(ATT_THREADS) __attribute__((amdgpu_waves_per_e
     }
     __syncthreads();
 
-    for (int qt = wave; qt < 9; qt += 3) {
-        const int qtok = qt * 16 + li;
+    for (int qt = wave; qt < ntile; qt += 3) {
+        const int slot = qt * 16 + li;
+        const int qtok = qtok_n;
         const int qsrc = qsrc_n;
         const int qrid = rid_s[qtok];
         const int qbase = (qtok / WS + WS - 1) * (2 * WS - 1) + (qtok % WS) + WS - 1;
@@ -431,7 +457,7 @@ __global__ void __launch_bounds__(ATT_THREADS) __attribute__((amdgpu_waves_per_e
             float r[8];
 #pragma unroll
             for (int e = 0; e < 4; ++e) { r[e] = q0[e] * p.scale; r[4 + e] = q1[e] * p.scale; }
-            if (qt + 3 < 9) load_q(qtok + 48);
+            if (qt + 3 < ntile) load_q(slot + 48);
             if constexpr (H) {
                 typedef unsigned u32x4_q __attribute__((ext_vector_type(4)));
                 u32x4_q hi, lo;
@@ -556,7 +582,7 @@ __global__ void __launch_bounds__(ATT_THREADS) __attribute__((amdgpu_waves_per_e
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        if (qsrc >= 0) {
+        if (qsrc >= 0 && slot < nq) {
             const float inv = (H ? 1.0f / (ATT_H_P * ATT_H_QKV) : 1.0f) / sum;
             if (H && p.out_planes == 2) {
                 float* orow = p.out + (long)qsrc * C;
@@ -600,7 +626,7 @@ __device__ __forceinline__ auto bias8_s16(const float* bp) {
 // 128-byte line, so the staging loads fetch whole lines (one head per workgroup used half of every line it touched).
 // F16: qkv / out are fp16 matrices (compute mode BRN_F16): the same kernel on v_mfma_f32_16x16x32_f16
 template <int ATT_BF16_HPW, bool F16 = false>
-__global__ void __launch_bounds__(ATT_BF16_HPW * ATT_THREADS) __attribute__((amdgpu_waves_per_eu(5, 8))) window_attention_bf16_kernel(const WindowAttnParams pa, const WindowAttnParams pb, const int nblk0) {
+__global__ void __launch_bounds__(ATT_BF16_HPW * ATT_THREADS) __attribute__((amdgpu_waves_per_eu(5, 8))) window_attention_bf16_kernel(const WindowAttnParams pa, const WindowAttnParams pb, const WindowOrder ord) {
     using E = std::conditional_t<F16, _Float16, __bf16>;
     typedef E ex8 __attribute__((ext_vector_type(8)));
     typedef E ex4 __attribute__((ext_vector_type(4)));
@@ -609,7 +635,8 @@ __global__ void __launch_bounds__(ATT_BF16_HPW * ATT_THREADS) __attribute__((amd
         if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
         else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
     };
-    const bool second = (int)blockIdx.x >= nblk0;
+    const AttBlock blk = att_block(ord);
+    const bool second = blk.win.geom != 0;
     const WindowAttnParams& p = second ? pb : pa;
     constexpr int TABN = (2 * WS - 1) * (2 * WS - 1);                 // 529
     constexpr float LOG2E = 1.4426950408889634f;
@@ -623,12 +650,13 @@ __global__ void __launch_bounds__(ATT_BF16_HPW * ATT_THREADS) __attribute__((amd
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int hp = wave / 3, wv = wave - 3 * hp;                      // head of the pair, wave within the head
-    const int head = blockIdx.y * ATT_BF16_HPW + hp;
-    const int nWh = p.Hp / WS, nWw = p.Wp / WS, nW = nWh * nWw;
-    const int bw = second ? (int)blockIdx.x - nblk0 : (int)blockIdx.x;
-    const int b = bw / nW, w = bw - b * nW;
-    const int wr = w / nWw, wc = w - wr * nWw;
+    const int head0 = blk.head * ATT_BF16_HPW, head = head0 + hp;
+    const int nWh = p.Hp / WS, nWw = p.Wp / WS;
+    const int b = blk.win.b, wr = blk.win.wr, wc = blk.win.wc;
     const int C = p.C, C3 = 3 * C;
+    // the query slots of this window: its real tokens only (window_attention_split_kernel), wave-uniform
+    const WindowReal wg = window_real(wr, wc, p.shift, p.H, p.W, p.Hp, p.Wp, ord.pack != 0);
+    const int nq = wg.nq, ntile = window_tiles(wg);
     const E* qkv = reinterpret_cast<const E*>(p.qkv);
     const int li = lane & 15, g = lane >> 4;
     // the shift mask (swin.rs:283-296) is non-zero only in the last row / column of windows
@@ -656,7 +684,7 @@ __global__ void __launch_bounds__(ATT_BF16_HPW * ATT_THREADS) __attribute__((amd
     int qsrc_[3];
 #pragma unroll
     for (int u = 0; u < 3; ++u) {
-        const int qs = tok_src((wv + 3 * u) * 16 + li);
+        const int qs = tok_src(slot_token(wg, min((wv + 3 * u) * 16 + li, nq - 1)));     // (a slot past nq: the last real query's row, never stored)
         qsrc_[u] = qs;
         qf[u] = *reinterpret_cast<const ex8*>(qkv + (long)max(qs, 0) * C3 + head * HD + g * 8);
     }
@@ -664,7 +692,7 @@ __global__ void __launch_bounds__(ATT_BF16_HPW * ATT_THREADS) __attribute__((amd
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         const int i = min(tid + j * NTHR, NTAB - 1), hh = i / TABN, jj = i - hh * TABN;
-        tbw[j] = p.rel_table[(blockIdx.y * ATT_BF16_HPW + hh) * TABN + (TABN - 1 - jj)];
+        tbw[j] = p.rel_table[(head0 + hh) * TABN + (TABN - 1 - jj)];
     }
     ex8 kv[2][2], vv[2][2];
     int ssrc[2][2];
@@ -672,7 +700,7 @@ __global__ void __launch_bounds__(ATT_BF16_HPW * ATT_THREADS) __attribute__((amd
     for (int it = 0; it < 2; ++it) {
         const int idx = min(tid + it * NTHR, NITEM - 1);
         const int c8 = (idx & 3) * 8, hh = (idx >> 2) & (ATT_BF16_HPW - 1), tp = idx / (4 * ATT_BF16_HPW);
-        const int hd = (blockIdx.y * ATT_BF16_HPW + hh) * HD;
+        const int hd = (head0 + hh) * HD;
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int src = tok_src(tp * 2 + u);
@@ -704,7 +732,7 @@ __global__ void __launch_bounds__(ATT_BF16_HPW * ATT_THREADS) __attribute__((amd
         const int idx = tid + it * NTHR;
         if (idx < NITEM) {
             const int c8 = (idx & 3) * 8, hh = (idx >> 2) & (ATT_BF16_HPW - 1), tp = idx / (4 * ATT_BF16_HPW);
-            const int hd = (blockIdx.y * ATT_BF16_HPW + hh) * HD;
+            const int hd = (head0 + hh) * HD;
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 if (ssrc[it][u] < 0) {
@@ -742,7 +770,9 @@ __global__ void __launch_bounds__(ATT_BF16_HPW * ATT_THREADS) __attribute__((amd
 #pragma unroll
     for (int u = 0; u < 3; ++u) {
         const int qt = wv + 3 * u;
-        const int qtok = qt * 16 + li;
+        if (qt >= ntile) break;                                       // wave-uniform: the window has fewer real queries
+        const int slot = qt * 16 + li;
+        const int qtok = slot_token(wg, min(slot, nq - 1));
         const int qsrc = qsrc_[u];
         const unsigned qrid4 = 0x01010101u * (unsigned)rid_s[qtok];
         // table index of (query, key) = qbase - key - 11 (key / 12), qbase = (qi + 11) 23 + qj + 11 (swin.rs:143-152 arithmetically)
@@ -812,7 +842,7 @@ __global__ void __launch_bounds__(ATT_BF16_HPW * ATT_THREADS) __attribute__((amd
             osum = mfma(ones8, pf, osum);
             __builtin_amdgcn_sched_barrier(0);
         }
-        if (qsrc >= 0) {
+        if (qsrc >= 0 && slot < nq) {
             const float inv = __builtin_amdgcn_rcpf(osum[0]);
             E* op = reinterpret_cast<E*>(p.out) + (long)qsrc * C + head * HD + g * 4;
             ex4 h0, h1;
@@ -848,6 +878,13 @@ hipError_t launch_window_attention2(const WindowAttnParams& p, const WindowAttnP
     if (p2 && (p2->out_h2 != p.out_h2 || p2->h2 != p.h2)) return hipErrorInvalidValue;
     const WindowAttnParams& q = p2 ? *p2 : p;
     dim3 grid(n0 + n1, p.heads), block(ATT_THREADS);
+    // split / bf16 kernels: real queries only, windows with the most query tiles first (kernels/window_geometry.h; pack_q == 0: all 144
+    // positions of every window in grid order, the form before).  A few integers computed here and passed by value: no table in memory
+    WindowOrder ord;
+    {
+        const WindowGeom g[2] = {{p.B, p.H, p.W, p.Hp, p.Wp, p.shift}, {q.B, q.H, q.W, q.Hp, q.Wp, q.shift}};
+        build_window_order(g, p2 ? 2 : 1, ws == WS && p.pack_q != 0, p.pack_q != 2, ord);
+    }
     if (p.io_bf16 && ws == 7) {
         if (p.out_planes || (p.C & 3)) return hipErrorInvalidValue;
         if (p.io_bf16 == 2) hipLaunchKernelGGL((window_attention_f32_kernel<7, 3, 2>), grid, block, 0, s, p, q, n0);
@@ -860,14 +897,14 @@ hipError_t launch_window_attention2(const WindowAttnParams& p, const WindowAttnP
         // two sub-batch streams sharing the HBM the step is 1.0 % faster (tools/ab_env.sh BRN_ATT_HPW "1 2"); BRN_ATT_HPW=1 selects one head
         static const bool two_heads = !(getenv("BRN_ATT_HPW") && atoi(getenv("BRN_ATT_HPW")) == 1);
         if (p.io_bf16 == 2) {                  // fp16 matrices (compute mode BRN_F16)
-            if (two_heads && !(p.heads & 1)) hipLaunchKernelGGL((window_attention_bf16_kernel<2, true>), dim3(n0 + n1, p.heads / 2), dim3(2 * ATT_THREADS), 0, s, p, q, n0);
-            else hipLaunchKernelGGL((window_attention_bf16_kernel<1, true>), grid, block, 0, s, p, q, n0);
-        } else if (two_heads && !(p.heads & 1)) hipLaunchKernelGGL(window_attention_bf16_kernel<2>, dim3(n0 + n1, p.heads / 2), dim3(2 * ATT_THREADS), 0, s, p, q, n0);
-        else hipLaunchKernelGGL(window_attention_bf16_kernel<1>, grid, block, 0, s, p, q, n0);
-    } else if (p.planes == 2 && p.h2) hipLaunchKernelGGL((window_attention_split_kernel<2, true>), grid, block, 0, s, p, q, n0);
-    else if (p.planes == 2) hipLaunchKernelGGL(window_attention_split_kernel<2>, grid, block, 0, s, p, q, n0);
+            if (two_heads && !(p.heads & 1)) hipLaunchKernelGGL((window_attention_bf16_kernel<2, true>), dim3(n0 + n1, p.heads / 2), dim3(2 * ATT_THREADS), 0, s, p, q, ord);
+            else hipLaunchKernelGGL((window_attention_bf16_kernel<1, true>), grid, block, 0, s, p, q, ord);
+        } else if (two_heads && !(p.heads & 1)) hipLaunchKernelGGL(window_attention_bf16_kernel<2>, dim3(n0 + n1, p.heads / 2), dim3(2 * ATT_THREADS), 0, s, p, q, ord);
+        else hipLaunchKernelGGL(window_attention_bf16_kernel<1>, grid, block, 0, s, p, q, ord);
+    } else if (p.planes == 2 && p.h2) hipLaunchKernelGGL((window_attention_split_kernel<2, true>), grid, block, 0, s, p, q, ord);
+    else if (p.planes == 2) hipLaunchKernelGGL(window_attention_split_kernel<2>, grid, block, 0, s, p, q, ord);
 #ifdef BRN_DIAG_BUILD
-    else if (p.planes == 1) hipLaunchKernelGGL(window_attention_split_kernel<1>, grid, block, 0, s, p, q, n0);
+    else if (p.planes == 1) hipLaunchKernelGGL(window_attention_split_kernel<1>, grid, block, 0, s, p, q, ord);
 #else
     else if (p.planes == 1) return hipErrorInvalidValue;      // mode bf16_operands: diag build only
 #endif
