@@ -23,18 +23,145 @@
 #include "../brn_kernels.h"
 #include "split_planes.h"
 #include "window_geometry.h"
+#include "window_attention_select.h"
 #include <cstdlib>
 #include <type_traits>
 
 namespace brn {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int WS = 12;
 constexpr int NTOK = 144;
 constexpr int HD = 32;
 constexpr int KV_LD = 36;          // floats per LDS row of K and V
-constexpr int ATT_THREADS = 192;   // 3 waves, 3 query tiles each
+constexpr int VT_LD = 148;         // 16-bit elements per LDS row of V^T (split and bf16 kernels)
+
+// ---- what the three kernels share, each piece once.  Token helpers: WSZ = window side (7 only in the fp32 kernel) ----
+// source row of window token t of window (wr, wc) of image b (roll + partition), -1 = pad token
+template <int WSZ = WS>
+__device__ __forceinline__ int att_tok_src(const WindowAttnParams& p, int b, int wr, int wc, int t) {
+    const int ti = t / WSZ, tj = t - ti * WSZ;
+    int sh = wr * WSZ + ti + p.shift, sw = wc * WSZ + tj + p.shift;   // shifted[i] = x[(i + shift) mod Hp] (swin.rs:412-444)
+    if (sh >= p.Hp) sh -= p.Hp;
+    if (sw >= p.Wp) sw -= p.Wp;
+    return (sh < p.H && sw < p.W) ? (b * p.H + sh) * p.W + sw : -1;
+}
+// SW-MSA region id of window token t (h_slices / w_slices, swin.rs:608-629), by its position on the shifted, padded canvas
+template <int WSZ = WS>
+__device__ __forceinline__ int att_region(const WindowAttnParams& p, int wr, int wc, int t) {
+    const int ti = t / WSZ, tj = t - ti * WSZ;
+    const int ph = wr * WSZ + ti, pw = wc * WSZ + tj;
+    const int fh = ph < p.Hp - WSZ ? 0 : (ph < p.Hp - p.shift ? 1 : 2);
+    const int fw = pw < p.Wp - WSZ ? 0 : (pw < p.Wp - p.shift ? 1 : 2);
+    return fh * 3 + fw;
+}
+// the shift mask (swin.rs:283-296) is non-zero only in the last row / column of windows; elsewhere it would add +0.0 to every score,
+// which the result cannot see (a -0.0 score becomes +0.0; max and exp treat them alike)
+template <int WSZ = WS>
+__device__ __forceinline__ bool att_has_mask(const WindowAttnParams& p, int wr, int wc) {
+    return p.shift > 0 && ((wr == p.Hp / WSZ - 1) | (wc == p.Wp / WSZ - 1));
+}
+// relative position index (swin.rs:182-184) of (query (qi, qj), key) = (qi-ki+W-1)*(2W-1) + (qj-kj+W-1) = att_qbase(qi, qj) - (key + (W-1)*(key/W));
+// att_qrev: the same base into a table stored reversed (rev[j] = table[(2W-1)^2 - 1 - j]), where the index GROWS with the key
+template <int WSZ = WS>
+__device__ __forceinline__ int att_qbase(int qi, int qj) { return (qi + WSZ - 1) * (2 * WSZ - 1) + qj + WSZ - 1; }
+template <int WSZ = WS>
+__device__ __forceinline__ int att_qrev(int qi, int qj) { return (2 * WSZ - 1) * (2 * WSZ - 1) - 1 - att_qbase<WSZ>(qi, qj); }
+
+// ---- split and bf16 kernels: 16-bit operands (E = __bf16 or _Float16), LDS images Kp[key][32 d] and Vt[d][VT_LD keys] ----
+template <typename E> using vec8 = E __attribute__((ext_vector_type(8)));
+template <typename E> using vec4 = E __attribute__((ext_vector_type(4)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+// every global load goes out unconditionally from a clamped address: a pad token (src < 0) reads row 0 and is replaced afterwards
+template <typename E>
+__device__ __forceinline__ const E* att_row_ptr(const E* qkv, int src, int C3) { return qkv + (long)max(src, 0) * C3; }
+// Kp: the 16-byte chunk c (d = 8c .. 8c+7) of row `key` is stored at c ^ kswz(key) = c ^ perm[(key >> 2) & 3], perm = {0,2,3,1}
+// (the split kernel passes row = plane * NTOK + key: NTOK % 16 == 0, so the plane does not change the swizzle)
+__device__ __forceinline__ int kswz(int key) { return (0x78 >> (2 * ((key >> 2) & 3))) & 3; }
+// A operand of S^T = K Q^T: d = 8g .. 8g+7 of row `key` (conflict-free ds_read_b128)
+template <typename E>
+__device__ __forceinline__ vec8<E> att_k_frag(const E* Kp, int key, int g) { return *reinterpret_cast<const vec8<E>*>(Kp + key * HD + ((g ^ kswz(key)) << 3)); }
+// A operand of O^T = V^T P^T at k-step t (key tiles 2t, 2t+1; the 10th tile does not exist: zeros); vrow = Vt + d * VT_LD + 4g
+template <typename E>
+__device__ __forceinline__ vec8<E> att_vt_frag(const E* vrow, int t) {
+    const vec4<E> lo = *reinterpret_cast<const vec4<E>*>(vrow + (2 * t) * 16);
+    vec4<E> hi = {(E)0.f, (E)0.f, (E)0.f, (E)0.f};
+    if (2 * t + 1 < 9) hi = *reinterpret_cast<const vec4<E>*>(vrow + (2 * t + 1) * 16);
+    vec8<E> vf;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { vf[e] = lo[e]; vf[4 + e] = hi[e]; }
+    return vf;
+}
+// B operand of the same k-step: the lane's 8 softmax numerators, straight out of the S^T accumulators
+__device__ __forceinline__ void att_p_step(const f32x4 (&st)[9], int t, float (&r)[8]) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { r[e] = st[2 * t][e]; r[4 + e] = (2 * t + 1 < 9) ? st[(2 * t + 1 < 9) ? 2 * t + 1 : 0][e] : 0.f; }
+}
+template <bool F16, typename V>
+__device__ __forceinline__ f32x4 att_mfma(const V a, const V b, const f32x4 c) {
+    if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+    else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+// H (mode f32_half2): the two planes are fp16 planes of the scaled operands (kernels/split_planes.h, split_pair_h) — q (with its head_dim^-0.5), k
+// and v scaled by 8, the un-normalised probabilities (in (0, 1]) by 2048 — on v_mfma_f32_16x16x32_f16; the scores and the output are
+// un-scaled exactly.  ~2^-22 relative per product instead of 2^-16.
+constexpr float ATT_H_QKV = 8.0f, ATT_H_P = 2048.0f;
+// eight floats r (used up) -> NP plane fragments: bf16 (x ~ x_h + x_l [+ x_ll]), or with H the two fp16 planes of s x (bf16x8 = the 16-byte container)
+template <int NP, bool H>
+__device__ __forceinline__ void att_split8(float (&r)[8], const float s, bf16x8 (&out)[NP]) {
+    if constexpr (H) {
+        u32x4 hi, lo;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { unsigned a, b; split_pair_h(r[2 * e], r[2 * e + 1], s, a, b); hi[e] = a; lo[e] = b; }
+        out[0] = __builtin_bit_cast(bf16x8, hi);
+        out[1] = __builtin_bit_cast(bf16x8, lo);
+    } else {
+#pragma unroll
+        for (int pl = 0; pl < NP; ++pl) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const __bf16 h = (__bf16)r[e];
+                out[pl][e] = h;
+                r[e] -= (float)h;
+            }
+        }
+    }
+}
+// acc + the NP (NP + 1) / 2 leading plane products of a . b, smallest first
+template <int NP, bool H>
+__device__ __forceinline__ f32x4 att_plane_mfma(const bf16x8 (&a)[NP], const bf16x8 (&b)[NP], f32x4 acc) {
+    if constexpr (NP == 2) {
+        acc = att_mfma<H>(a[1], b[0], acc);
+        acc = att_mfma<H>(a[0], b[1], acc);
+    }
+    return att_mfma<H>(a[0], b[0], acc);
+}
+// lane group g's rows of the two d tiles of a query's output (o0 * inv: d = 4g .. 4g + 3 of the head, o1 * inv: 16 further) in the form the proj
+// GEMM reads; FORMS = the forms the calling kernel can be asked for: planes by p.out_planes, else 16-bit elements E or fp32
+enum : unsigned { ST_F32 = 1, ST_S16 = 2, ST_P2 = 4, ST_P3 = 8, ST_H2 = 16 };
+template <unsigned FORMS, typename E = float>
+__device__ __forceinline__ void att_store(const WindowAttnParams& p, int qsrc, int head, int g, const f32x4 o0, const f32x4 o1, const float inv) {
+    const int C = p.C, col = head * HD + g * 4;
+    if ((FORMS & ST_P3) && p.out_planes == 3) {           // mode f32_split3: the 3-plane P layout (rows 1.5x as long)
+        float* orow = p.out + (long)qsrc * (C + C / 2);
+        store_planes<3>(orow, col, o0 * inv), store_planes<3>(orow, col + 16, o1 * inv);
+    } else if ((FORMS & ST_H2) && p.out_planes == 2) {    // mode f32_half2: two fp16 planes of out_h2 * out (rows as long as fp32 rows)
+        float* orow = p.out + (long)qsrc * C;
+        store_planes_h(orow, col, o0 * inv, p.out_h2), store_planes_h(orow, col + 16, o1 * inv, p.out_h2);
+    } else if ((FORMS & ST_P2) && p.out_planes == 2) {    // the P layout: a head's 32 outputs are one K tile of the row
+        float* orow = p.out + (long)qsrc * C;
+        store_planes<2>(orow, col, o0 * inv), store_planes<2>(orow, col + 16, o1 * inv);
+    } else if constexpr ((FORMS & ST_S16) != 0) {
+        E* op = reinterpret_cast<E*>(p.out) + (long)qsrc * C + head * HD + g * 4;
+        vec4<E> h0, h1;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { h0[e] = (E)(o0[e] * inv); h1[e] = (E)(o1[e] * inv); }
+        *reinterpret_cast<vec4<E>*>(op) = h0, *reinterpret_cast<vec4<E>*>(op + 16) = h1;
+    } else {
+        float* op = p.out + (long)qsrc * C + head * HD + g * 4;
+        *reinterpret_cast<f32x4*>(op) = o0 * inv, *reinterpret_cast<f32x4*>(op + 16) = o1 * inv;
+    }
+}
 
 // Both kernels take TWO geometries (the full- and the half-scale map of a co-batched backbone pass, same C / heads / shift):
 // blocks [0, nblk0) work on pa, the rest on pb — one launch, one ramp and one tail instead of two (the half-scale launch alone
@@ -88,17 +215,8 @@ __global__ void __launch_bounds__(NWV * 64) window_attention_f32_kernel(const Wi
     const int wr = w / nWw, wc = w - wr * nWw;
     const int C = p.C, C3 = 3 * C;
 
-    if (tid < NTOK) {
-        const int ti = tid / WS, tj = tid - ti * WS;
-        const int ph = wr * WS + ti, pw = wc * WS + tj;       // position on the shifted, padded canvas
-        int sh = ph + p.shift, sw = pw + p.shift;              // shifted[i] = x[(i + shift) mod Hp] (swin.rs:412-444)
-        if (sh >= p.Hp) sh -= p.Hp;
-        if (sw >= p.Wp) sw -= p.Wp;
-        src_s[tid] = (sh < p.H && sw < p.W) ? (b * p.H + sh) * p.W + sw : -1;
-        const int fh = ph < p.Hp - WS ? 0 : (ph < p.Hp - p.shift ? 1 : 2);   // h_slices / w_slices, swin.rs:608-617
-        const int fw = pw < p.Wp - WS ? 0 : (pw < p.Wp - p.shift ? 1 : 2);
-        rid_s[tid] = fh * 3 + fw;
-    } else if (tid < NPADTOK) { src_s[tid] = -1; rid_s[tid] = 0; }
+    if (tid < NTOK) { src_s[tid] = att_tok_src<WS>(p, b, wr, wc, tid); rid_s[tid] = att_region<WS>(p, wr, wc, tid); }
+    else if (tid < NPADTOK) { src_s[tid] = -1; rid_s[tid] = 0; }
     // window 12: the table is kept REVERSED and in log2 units (tab_s[j] = log2(e) * table[528 - j]): the 4 keys 16 kt + 4 g + {0..3} of
     // a lane lie in one window row (12 % 4 == 0), so their entries are 4 consecutive words — one index per key tile instead of
     // one per score — and the softmax runs on exp2.  Window 7 keeps the plain table and the per-score index.
@@ -106,8 +224,7 @@ __global__ void __launch_bounds__(NWV * 64) window_attention_f32_kernel(const Wi
     constexpr bool REV = WS == 12;
     constexpr float LOG2E = 1.4426950408889634f;
     for (int i = tid; i < TABN; i += NTHR) tab_s[i] = REV ? LOG2E * p.rel_table[head * TABN + (TABN - 1 - i)] : p.rel_table[head * TABN + i];
-    // the shift mask (swin.rs:283-296) is non-zero only in the last row / column of windows
-    const bool has_mask = p.shift > 0 && (wr == p.Hp / WS - 1 || wc == nWw - 1);
+    const bool has_mask = att_has_mask<WS>(p, wr, wc);
     __syncthreads();
 
     // ---- stage K and V of this (window, head) into LDS: 144 rows x 8 float4 each ----
@@ -138,9 +255,8 @@ __global__ void __launch_bounds__(NWV * 64) window_attention_f32_kernel(const Wi
         const int qtok = qt * 16 + li;
         const int qsrc = src_s[qtok];
         const int qrid = rid_s[qtok];
-        // relative position index (swin.rs:182-184): (qi-ki+11)*23 + (qj-kj+11) = qbase - (key + 11*(key/12))
         const int qt_ = qtok < NTOK ? qtok : NTOK - 1;            // (dummy queries of the last tile compute on a valid row, never stored)
-        const int qbase = (qt_ / WS + WS - 1) * (2 * WS - 1) + (qt_ % WS) + WS - 1;
+        const int qbase = att_qbase<WS>(qt_ / WS, qt_ % WS);
         // Q fragment: d = 8g .. 8g+7 of query row qtok, scaled before the product (swin.rs:278)
         float qf[8];
 #pragma unroll
@@ -164,7 +280,7 @@ __global__ void __launch_bounds__(NWV * 64) window_attention_f32_kernel(const Wi
         // + relative position bias (swin.rs:284-285), + SW-MSA mask (swin.rs:288-297, value -100 swin.rs:651)
         float mx = -3.0e38f;
         if constexpr (REV) {
-            const int qrev = (TABN - 1) - qbase;
+            const int qrev = att_qrev<WS>(qt_ / WS, qt_ % WS);
 #pragma unroll
             for (int kt = 0; kt < NT16; ++kt) {
                 const int key0 = kt * 16 + g * 4;
@@ -225,28 +341,7 @@ __global__ void __launch_bounds__(NWV * 64) window_attention_f32_kernel(const Wi
         // lane holds O^T[d = 16*dt + 4g + r][query = li]; softmax denominator applied here (swin.rs:300,303)
         if (qsrc >= 0 && qtok < NTOK) {
             const float inv = 1.0f / sum;
-            if (p.out_planes == 3) {        // mode f32_split3: the proj GEMM reads the 3-plane P layout (rows 1.5x as long)
-                float* orow = p.out + (long)qsrc * (C + C / 2);
-                store_planes<3>(orow, head * HD + g * 4, o0 * inv);
-                store_planes<3>(orow, head * HD + 16 + g * 4, o1 * inv);
-            } else if (p.out_planes == 2) { // mode f32_half2: the proj GEMM reads the two fp16 planes (rows as long as fp32 rows)
-                float* orow = p.out + (long)qsrc * C;
-                store_planes_h(orow, head * HD + g * 4, o0 * inv, p.out_h2);
-                store_planes_h(orow, head * HD + 16 + g * 4, o1 * inv, p.out_h2);
-            } else if constexpr (IOB != 0) {
-                using E = std::conditional_t<IOB == 2, _Float16, __bf16>;
-                typedef E ex4_st __attribute__((ext_vector_type(4)));
-                E* op = reinterpret_cast<E*>(p.out) + (long)qsrc * C + head * HD + g * 4;
-                ex4_st h0, h1;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { h0[e] = (E)(o0[e] * inv); h1[e] = (E)(o1[e] * inv); }
-                *reinterpret_cast<ex4_st*>(op) = h0;
-                *reinterpret_cast<ex4_st*>(op + 16) = h1;
-            } else {
-                float* op = p.out + (long)qsrc * C + head * HD + g * 4;
-                *reinterpret_cast<f32x4*>(op) = o0 * inv;
-                *reinterpret_cast<f32x4*>(op + 16) = o1 * inv;
-            }
+            att_store<ST_P3 | ST_H2 | (IOB != 0 ? ST_S16 : ST_F32), std::conditional_t<IOB == 2, _Float16, __bf16>>(p, qsrc, head, g, o0, o1, inv);
         }
     }
 }
@@ -283,17 +378,7 @@ __device__ __forceinline__ AttBlock att_block(const WindowOrder& ord) {
     r.head = head;
     return r;
 }
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-constexpr int VT_LD = 148;
-
-__device__ __forceinline__ int kswz(int key) { return (0x78 >> (2 * ((key >> 2) & 3))) & 3; }
-
-// H (mode f32_half2): the two planes are fp16 planes of the scaled operands (kernels/split_planes.h, split_pair_h) — q (with its head_dim^-0.5), k
-// and v scaled by 8, the un-normalised probabilities (in (0, 1]) by 2048 — on v_mfma_f32_16x16x32_f16; the scores and the output are
-// un-scaled exactly.  ~2^-22 relative per product instead of 2^-16.
-constexpr float ATT_H_QKV = 8.0f, ATT_H_P = 2048.0f;
+// H (mode f32_half2): two fp16 planes on v_mfma_f32_16x16x32_f16 (ATT_H_QKV, att_split8)
 template <int NP, bool H = false>
 __global__ void __launch_bounds__(ATT_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3))) window_attention_split_kernel(const WindowAttnParams pa, const WindowAttnParams pb, const WindowOrder ord) {
     static_assert(!H || NP == 2, "fp16 planes come in pairs");
@@ -310,23 +395,14 @@ __global__ void __launch_bounds__(ATT_THREADS) __attribute__((amdgpu_waves_per_e
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, g = lane >> 4;
     const int head = blk.head;
-    const int nWw = p.Wp / WS;
     const int b = blk.win.b, wr = blk.win.wr, wc = blk.win.wc;
     const int C = p.C, C3 = 3 * C;
     // the query slots of this window: its real tokens only (a pad query's row is cropped, swin.rs:387-401; pad KEYS stay), wave-uniform
     const WindowReal wg = window_real(wr, wc, p.shift, p.H, p.W, p.Hp, p.Wp, ord.pack != 0);
     const int nq = wg.nq, ntile = window_tiles(wg);
-    // the shift mask (swin.rs:283-296) is non-zero only in the last row / column of windows; elsewhere the old form added +0.0 to every
-    // score, which the result cannot see (a -0.0 score becomes +0.0; max and exp treat them alike)
-    const bool has_mask = p.shift > 0 && (wr == p.Hp / WS - 1 || wc == nWw - 1);
+    const bool has_mask = att_has_mask(p, wr, wc);
+    auto tok_src = [&](int t) { return att_tok_src(p, b, wr, wc, t); };     // (kept a lambda: called directly, the helper compiled to other scalar code)
 
-    auto tok_src = [&](int t) {                                       // source row of window token t (roll + partition), -1 = pad token
-        const int ti = t / WS, tj = t - ti * WS;
-        int sh = wr * WS + ti + p.shift, sw = wc * WS + tj + p.shift;
-        if (sh >= p.Hp) sh -= p.Hp;
-        if (sw >= p.Wp) sw -= p.Wp;
-        return (sh < p.H && sw < p.W) ? (b * p.H + sh) * p.W + sw : -1;
-    };
     // ---- every global load of the workgroup goes out FIRST, unconditionally, from clamped addresses (a pad token reads row 0 and is
     // replaced by the qkv bias afterwards, by a select): the K / V rows of the thread's three staging items = (token pair, 4-wide d chunk),
     // the bias chunks a pad token needs, the table words, the wave's first Q fragment.  The source rows are computed in registers: with
@@ -345,7 +421,7 @@ __global__ void __launch_bounds__(ATT_THREADS) __attribute__((amdgpu_waves_per_e
         for (int u = 0; u < 2; ++u) {
             const int src = tok_src(((tid >> 3) + it * (ATT_THREADS / 8)) * 2 + u);
             ssrc[it][u] = src;
-            const float* kp = p.qkv + (long)max(src, 0) * C3 + C + head * HD + c4;
+            const float* kp = att_row_ptr(p.qkv, src, C3) + C + head * HD + c4;
             kvr[it][u] = *reinterpret_cast<const f32x4*>(kp);
             vvr[it][u] = *reinterpret_cast<const f32x4*>(kp + C);
         }
@@ -363,21 +439,15 @@ __global__ void __launch_bounds__(ATT_THREADS) __attribute__((amdgpu_waves_per_e
     auto load_q = [&](int slot) {
         qtok_n = slot_token(wg, min(slot, nq - 1));
         qsrc_n = tok_src(qtok_n);
-        const float* qp = p.qkv + (long)max(qsrc_n, 0) * C3 + head * HD + g * 8;
+        const float* qp = att_row_ptr(p.qkv, qsrc_n, C3) + head * HD + g * 8;
         qn0 = *reinterpret_cast<const f32x4*>(qp);
         qn1 = *reinterpret_cast<const f32x4*>(qp + 4);
     };
     load_q(wave * 16 + li);
 
-    if (tid < NTOK) {
-        const int ti = tid / WS, tj = tid - ti * WS;
-        const int ph = wr * WS + ti, pw = wc * WS + tj;
-        const int fh = ph < p.Hp - WS ? 0 : (ph < p.Hp - p.shift ? 1 : 2);
-        const int fw = pw < p.Wp - WS ? 0 : (pw < p.Wp - p.shift ? 1 : 2);
-        rid_s[tid] = (unsigned char)(fh * 3 + fw);
-    }
+    if (tid < NTOK) rid_s[tid] = (unsigned char)att_region(p, wr, wc, tid);
 
-    // ---- consume: K (row-major, swizzled) and V (transposed), split into bf16 planes; pad tokens take the qkv bias; the table ----
+    // ---- consume: K (row-major, swizzled) and V (transposed), split into planes; pad tokens take the qkv bias; the table ----
 #pragma unroll
     for (int it = 0; it < 3; ++it) {
         const int tp = (tid >> 3) + it * (ATT_THREADS / 8);
@@ -387,15 +457,14 @@ __global__ void __launch_bounds__(ATT_THREADS) __attribute__((amdgpu_waves_per_e
             kv[u] = ssrc[it][u] < 0 ? kbias : kvr[it][u];
             vv[u] = ssrc[it][u] < 0 ? vbias : vvr[it][u];
         }
+        // (4-wide K chunks and key PAIRS of V: not att_split8 — with it the fp16-plane kernel's store addresses compiled differently)
         if constexpr (H) {
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
-                const int t = tp * 2 + u;
                 bf16x4 sp[2];
                 split4h<false>(kv[u], 0xffffffffu, ATT_H_QKV, sp);
 #pragma unroll
-                for (int pl = 0; pl < 2; ++pl)
-                    *reinterpret_cast<bf16x4*>(Kp + (pl * NTOK + t) * HD + (((c4 >> 3) ^ kswz(t)) << 3) + (c4 & 4)) = sp[pl];
+                for (int pl = 0; pl < 2; ++pl) *reinterpret_cast<bf16x4*>(Kp + (pl * NTOK + tp * 2 + u) * HD + (((c4 >> 3) ^ kswz(tp * 2 + u)) << 3) + (c4 & 4)) = sp[pl];
             }
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -406,32 +475,31 @@ __global__ void __launch_bounds__(ATT_THREADS) __attribute__((amdgpu_waves_per_e
             }
         } else {
 #pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int t = tp * 2 + u;
-            f32x4 r = kv[u];
+            for (int u = 0; u < 2; ++u) {
+                f32x4 r = kv[u];
 #pragma unroll
-            for (int pl = 0; pl < NP; ++pl) {
-                bf16x4 h;
+                for (int pl = 0; pl < NP; ++pl) {
+                    bf16x4 h;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) h[e] = (__bf16)r[e];
-                *reinterpret_cast<bf16x4*>(Kp + (pl * NTOK + t) * HD + (((c4 >> 3) ^ kswz(t)) << 3) + (c4 & 4)) = h;
-                if (pl + 1 < NP) {
+                    for (int e = 0; e < 4; ++e) h[e] = (__bf16)r[e];
+                    *reinterpret_cast<bf16x4*>(Kp + (pl * NTOK + tp * 2 + u) * HD + (((c4 >> 3) ^ kswz(tp * 2 + u)) << 3) + (c4 & 4)) = h;
+                    if (pl + 1 < NP) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) r[e] -= (float)h[e];
+                        for (int e = 0; e < 4; ++e) r[e] -= (float)h[e];
+                    }
                 }
             }
-        }
-        f32x4 r0 = vv[0], r1 = vv[1];
+            f32x4 r0 = vv[0], r1 = vv[1];
 #pragma unroll
-        for (int pl = 0; pl < NP; ++pl) {
+            for (int pl = 0; pl < NP; ++pl) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                bf16x2 h;
-                h[0] = (__bf16)r0[e]; h[1] = (__bf16)r1[e];
-                *reinterpret_cast<bf16x2*>(Vt + (pl * HD + c4 + e) * VT_LD + tp * 2) = h;   // keys (2tp, 2tp+1) of row d = c4+e
-                if (pl + 1 < NP) { r0[e] -= (float)h[0]; r1[e] -= (float)h[1]; }
+                for (int e = 0; e < 4; ++e) {
+                    bf16x2 h;
+                    h[0] = (__bf16)r0[e]; h[1] = (__bf16)r1[e];
+                    *reinterpret_cast<bf16x2*>(Vt + (pl * HD + c4 + e) * VT_LD + tp * 2) = h;   // keys (2tp, 2tp+1) of row d = c4+e
+                    if (pl + 1 < NP) { r0[e] -= (float)h[0]; r1[e] -= (float)h[1]; }
+                }
             }
-        }
         }
     }
 #pragma unroll
@@ -448,7 +516,7 @@ __global__ void __launch_bounds__(ATT_THREADS) __attribute__((amdgpu_waves_per_e
         const int qtok = qtok_n;
         const int qsrc = qsrc_n;
         const int qrid = rid_s[qtok];
-        const int qbase = (qtok / WS + WS - 1) * (2 * WS - 1) + (qtok % WS) + WS - 1;
+        const int qbase = att_qbase(qtok / WS, qtok % WS);
         // Q fragment (B operand of S^T = K Q^T): d = 8g .. 8g+7 of this lane's query, scaled (swin.rs:278), split
         bf16x8 qf[NP];
         {
@@ -458,46 +526,15 @@ __global__ void __launch_bounds__(ATT_THREADS) __attribute__((amdgpu_waves_per_e
 #pragma unroll
             for (int e = 0; e < 4; ++e) { r[e] = q0[e] * p.scale; r[4 + e] = q1[e] * p.scale; }
             if (qt + 3 < ntile) load_q(slot + 48);
-            if constexpr (H) {
-                typedef unsigned u32x4_q __attribute__((ext_vector_type(4)));
-                u32x4_q hi, lo;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { unsigned a, b2; split_pair_h(r[2 * e], r[2 * e + 1], ATT_H_QKV, a, b2); hi[e] = a; lo[e] = b2; }
-                qf[0] = __builtin_bit_cast(bf16x8, hi);
-                qf[1] = __builtin_bit_cast(bf16x8, lo);
-            } else {
-#pragma unroll
-            for (int pl = 0; pl < NP; ++pl) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const __bf16 h = (__bf16)r[e];
-                    qf[pl][e] = h;
-                    r[e] -= (float)h;
-                }
-            }
-            }
+            att_split8<NP, H>(r, ATT_H_QKV, qf);
         }
         f32x4 st[9];
 #pragma unroll
         for (int kt = 0; kt < 9; ++kt) {
-            const int key = kt * 16 + li;
             bf16x8 kf[NP];
 #pragma unroll
-            for (int pl = 0; pl < NP; ++pl)
-                kf[pl] = *reinterpret_cast<const bf16x8*>(Kp + (pl * NTOK + key) * HD + ((g ^ kswz(key)) << 3));
-            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-            if constexpr (H) {
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, kf[1]), __builtin_bit_cast(f16x8, qf[0]), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, kf[0]), __builtin_bit_cast(f16x8, qf[1]), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, kf[0]), __builtin_bit_cast(f16x8, qf[0]), acc, 0, 0, 0);
-            } else {
-            if (NP == 2) {
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[1], qf[0], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[0], qf[1], acc, 0, 0, 0);
-            }
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[0], qf[0], acc, 0, 0, 0);
-            }
-            st[kt] = acc;
+            for (int pl = 0; pl < NP; ++pl) kf[pl] = att_k_frag(Kp, pl * NTOK + kt * 16 + li, g);
+            st[kt] = att_plane_mfma<NP, H>(kf, qf, f32x4{0.f, 0.f, 0.f, 0.f});
             if (kt % 3 == 2) __builtin_amdgcn_sched_barrier(0);
         }
         float mx = -3.0e38f;
@@ -530,73 +567,23 @@ __global__ void __launch_bounds__(ATT_THREADS) __attribute__((amdgpu_waves_per_e
         f32x4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int t = 0; t < 5; ++t) {
+            float pr[8];
+            att_p_step(st, t, pr);
             bf16x8 pf[NP];
-            {
-                float r[8];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { r[e] = st[2 * t][e]; r[4 + e] = (2 * t + 1 < 9) ? st[(2 * t + 1 < 9) ? 2 * t + 1 : 0][e] : 0.f; }
-                if constexpr (H) {
-                    typedef unsigned u32x4_p __attribute__((ext_vector_type(4)));
-                    u32x4_p hi, lo;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { unsigned a, b2; split_pair_h(r[2 * e], r[2 * e + 1], ATT_H_P, a, b2); hi[e] = a; lo[e] = b2; }
-                    pf[0] = __builtin_bit_cast(bf16x8, hi);
-                    pf[1] = __builtin_bit_cast(bf16x8, lo);
-                } else {
-#pragma unroll
-                for (int pl = 0; pl < NP; ++pl) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const __bf16 h = (__bf16)r[e];
-                        pf[pl][e] = h;
-                        r[e] -= (float)h;
-                    }
-                }
-                }
-            }
+            att_split8<NP, H>(pr, ATT_H_P, pf);
 #pragma unroll
             for (int dt = 0; dt < 2; ++dt) {
                 bf16x8 vf[NP];
 #pragma unroll
-                for (int pl = 0; pl < NP; ++pl) {
-                    const __bf16* vrow = Vt + (pl * HD + dt * 16 + li) * VT_LD + g * 4;
-                    const bf16x4 lo = *reinterpret_cast<const bf16x4*>(vrow + (2 * t) * 16);
-                    bf16x4 hi = {(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
-                    if (2 * t + 1 < 9) hi = *reinterpret_cast<const bf16x4*>(vrow + (2 * t + 1) * 16);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { vf[pl][e] = lo[e]; vf[pl][4 + e] = hi[e]; }
-                }
-                f32x4 o = dt == 0 ? o0 : o1;
-                if constexpr (H) {
-                    o = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, vf[1]), __builtin_bit_cast(f16x8, pf[0]), o, 0, 0, 0);
-                    o = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, vf[0]), __builtin_bit_cast(f16x8, pf[1]), o, 0, 0, 0);
-                    o = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, vf[0]), __builtin_bit_cast(f16x8, pf[0]), o, 0, 0, 0);
-                } else {
-                if (NP == 2) {
-                    o = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[1], pf[0], o, 0, 0, 0);
-                    o = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[0], pf[1], o, 0, 0, 0);
-                }
-                o = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[0], pf[0], o, 0, 0, 0);
-                }
-                if (dt == 0) o0 = o; else o1 = o;
+                for (int pl = 0; pl < NP; ++pl) vf[pl] = att_vt_frag(Vt + (pl * HD + dt * 16 + li) * VT_LD + g * 4, t);
+                if (dt == 0) o0 = att_plane_mfma<NP, H>(vf, pf, o0);
+                else o1 = att_plane_mfma<NP, H>(vf, pf, o1);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
         if (qsrc >= 0 && slot < nq) {
             const float inv = (H ? 1.0f / (ATT_H_P * ATT_H_QKV) : 1.0f) / sum;
-            if (H && p.out_planes == 2) {
-                float* orow = p.out + (long)qsrc * C;
-                store_planes_h(orow, head * HD + g * 4, o0 * inv, p.out_h2);
-                store_planes_h(orow, head * HD + 16 + g * 4, o1 * inv, p.out_h2);
-            } else if (p.out_planes == 2) {        // the proj GEMM reads the P layout: a head's 32 outputs are one K tile of the row
-                float* orow = p.out + (long)qsrc * C;
-                store_planes<2>(orow, head * HD + g * 4, o0 * inv);
-                store_planes<2>(orow, head * HD + 16 + g * 4, o1 * inv);
-            } else {
-                float* op = p.out + (long)qsrc * C + head * HD + g * 4;
-                *reinterpret_cast<f32x4*>(op) = o0 * inv;
-                *reinterpret_cast<f32x4*>(op + 16) = o1 * inv;
-            }
+            att_store<ST_F32 | (H ? ST_H2 : ST_P2)>(p, qsrc, head, g, o0, o1, inv);
         }
     }
 }
@@ -614,9 +601,8 @@ __device__ __forceinline__ float max3f(float a, float b, float c) {
     return r;
 }
 template <typename E>
-__device__ __forceinline__ auto bias8_s16(const float* bp) {
-    typedef E ex8_b __attribute__((ext_vector_type(8)));
-    ex8_b r;
+__device__ __forceinline__ vec8<E> bias8_s16(const float* bp) {
+    vec8<E> r;
 #pragma unroll
     for (int e = 0; e < 8; ++e) r[e] = (E)bp[e];
     return r;
@@ -628,13 +614,8 @@ __device__ __forceinline__ auto bias8_s16(const float* bp) {
 template <int ATT_BF16_HPW, bool F16 = false>
 __global__ void __launch_bounds__(ATT_BF16_HPW * ATT_THREADS) __attribute__((amdgpu_waves_per_eu(5, 8))) window_attention_bf16_kernel(const WindowAttnParams pa, const WindowAttnParams pb, const WindowOrder ord) {
     using E = std::conditional_t<F16, _Float16, __bf16>;
-    typedef E ex8 __attribute__((ext_vector_type(8)));
-    typedef E ex4 __attribute__((ext_vector_type(4)));
+    typedef vec8<E> ex8;
     typedef E ex2 __attribute__((ext_vector_type(2)));
-    auto mfma = [](const ex8 a, const ex8 b, const f32x4 c) -> f32x4 {
-        if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-        else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-    };
     const AttBlock blk = att_block(ord);
     const bool second = blk.win.geom != 0;
     const WindowAttnParams& p = second ? pb : pa;
@@ -651,7 +632,6 @@ __global__ void __launch_bounds__(ATT_BF16_HPW * ATT_THREADS) __attribute__((amd
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int hp = wave / 3, wv = wave - 3 * hp;                      // head of the pair, wave within the head
     const int head0 = blk.head * ATT_BF16_HPW, head = head0 + hp;
-    const int nWh = p.Hp / WS, nWw = p.Wp / WS;
     const int b = blk.win.b, wr = blk.win.wr, wc = blk.win.wc;
     const int C = p.C, C3 = 3 * C;
     // the query slots of this window: its real tokens only (window_attention_split_kernel), wave-uniform
@@ -659,19 +639,12 @@ __global__ void __launch_bounds__(ATT_BF16_HPW * ATT_THREADS) __attribute__((amd
     const int nq = wg.nq, ntile = window_tiles(wg);
     const E* qkv = reinterpret_cast<const E*>(p.qkv);
     const int li = lane & 15, g = lane >> 4;
-    // the shift mask (swin.rs:283-296) is non-zero only in the last row / column of windows
-    const bool has_mask = p.shift > 0 && (wr == nWh - 1 || wc == nWw - 1);
+    const bool has_mask = att_has_mask(p, wr, wc);
+    auto tok_src = [&](int t) { return att_tok_src(p, b, wr, wc, t); };
     E* Kp = Kp_[hp];
     E* Vt = Vt_[hp];
     const float* rev_s = rev_[hp];
 
-    auto tok_src = [&](int t) {                                       // source row of window token t (roll + partition), -1 = pad token
-        const int ti = t / WS, tj = t - ti * WS;
-        int sh = wr * WS + ti + p.shift, sw = wc * WS + tj + p.shift;
-        if (sh >= p.Hp) sh -= p.Hp;
-        if (sw >= p.Wp) sw -= p.Wp;
-        return (sh < p.H && sw < p.W) ? (b * p.H + sh) * p.W + sw : -1;
-    };
     // ---- every global load of the workgroup goes out FIRST, unconditionally, from clamped addresses (a pad token reads row 0 and is
     // fixed up afterwards): the three Q fragments, the head's bias table, the K / V rows.  The first version loaded under lane-dependent
     // branches and in two dependent loops — hipcc waits vmcnt(0) at every join — and paid five HBM round trips one after the other
@@ -686,7 +659,7 @@ __global__ void __launch_bounds__(ATT_BF16_HPW * ATT_THREADS) __attribute__((amd
     for (int u = 0; u < 3; ++u) {
         const int qs = tok_src(slot_token(wg, min((wv + 3 * u) * 16 + li, nq - 1)));     // (a slot past nq: the last real query's row, never stored)
         qsrc_[u] = qs;
-        qf[u] = *reinterpret_cast<const ex8*>(qkv + (long)max(qs, 0) * C3 + head * HD + g * 8);
+        qf[u] = *reinterpret_cast<const ex8*>(att_row_ptr(qkv, qs, C3) + head * HD + g * 8);
     }
     float tbw[3];
 #pragma unroll
@@ -705,18 +678,12 @@ __global__ void __launch_bounds__(ATT_BF16_HPW * ATT_THREADS) __attribute__((amd
         for (int u = 0; u < 2; ++u) {
             const int src = tok_src(tp * 2 + u);
             ssrc[it][u] = src;
-            const E* kp = qkv + (long)max(src, 0) * C3 + C + hd + c8;
+            const E* kp = att_row_ptr(qkv, src, C3) + C + hd + c8;
             kv[it][u] = *reinterpret_cast<const ex8*>(kp);
             vv[it][u] = *reinterpret_cast<const ex8*>(kp + C);
         }
     }
-    if (tid < NTOK) {
-        const int ti = tid / WS, tj = tid - ti * WS;
-        const int ph = wr * WS + ti, pw = wc * WS + tj;
-        const int fh = ph < p.Hp - WS ? 0 : (ph < p.Hp - p.shift ? 1 : 2);
-        const int fw = pw < p.Wp - WS ? 0 : (pw < p.Wp - p.shift ? 1 : 2);
-        rid_s[tid] = (unsigned char)(fh * 3 + fw);
-    }
+    if (tid < NTOK) rid_s[tid] = (unsigned char)att_region(p, wr, wc, tid);
     // ---- consume: table, K (row-major, chunk-swizzled), V (transposed); pad tokens take the qkv bias (swin.rs:359-366: their LayerNorm
     // output row is zero) in a second, divergent step that only the windows on the padded border execute ----
 #pragma unroll
@@ -741,10 +708,7 @@ __global__ void __launch_bounds__(ATT_BF16_HPW * ATT_THREADS) __attribute__((amd
                 }
             }
 #pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int t = tp * 2 + u;
-                *reinterpret_cast<ex8*>(Kp_[hh] + t * HD + (((c8 >> 3) ^ kswz(t)) << 3)) = kv[it][u];
-            }
+            for (int u = 0; u < 2; ++u) *reinterpret_cast<ex8*>(Kp_[hh] + (tp * 2 + u) * HD + (((c8 >> 3) ^ kswz(tp * 2 + u)) << 3)) = kv[it][u];
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 ex2 h;
@@ -775,15 +739,11 @@ __global__ void __launch_bounds__(ATT_BF16_HPW * ATT_THREADS) __attribute__((amd
         const int qtok = slot_token(wg, min(slot, nq - 1));
         const int qsrc = qsrc_[u];
         const unsigned qrid4 = 0x01010101u * (unsigned)rid_s[qtok];
-        // table index of (query, key) = qbase - key - 11 (key / 12), qbase = (qi + 11) 23 + qj + 11 (swin.rs:143-152 arithmetically)
-        const int qrev = (TABN - 1) - ((qtok / WS + WS - 1) * (2 * WS - 1) + (qtok % WS) + WS - 1);
+        const int qrev = att_qrev(qtok / WS, qtok % WS);
         f32x4 st[9];
 #pragma unroll
         for (int kt = 0; kt < 9; ++kt) {
-            const int key = kt * 16 + li;
-            const ex8 kf = *reinterpret_cast<const ex8*>(Kp + key * HD + ((g ^ kswz(key)) << 3));
-            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-            st[kt] = mfma(kf, qf[u], acc);
+            st[kt] = att_mfma<F16>(att_k_frag(Kp, kt * 16 + li, g), qf[u], f32x4{0.f, 0.f, 0.f, 0.f});
             if (kt % 3 == 2) __builtin_amdgcn_sched_barrier(0);
         }
         float mx = -3.0e38f;
@@ -821,98 +781,64 @@ __global__ void __launch_bounds__(ATT_BF16_HPW * ATT_THREADS) __attribute__((amd
         f32x4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = {0.f, 0.f, 0.f, 0.f}, osum = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int t = 0; t < 5; ++t) {
+            float pr[8];
+            att_p_step(st, t, pr);
             ex8 pf;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                pf[e] = (E)st[2 * t][e];
-                pf[4 + e] = (2 * t + 1 < 9) ? (E)st[(2 * t + 1 < 9) ? 2 * t + 1 : 0][e] : (E)0.f;
-            }
+            for (int e = 0; e < 8; ++e) pf[e] = (E)pr[e];
 #pragma unroll
             for (int dt = 0; dt < 2; ++dt) {
-                const E* vrow = Vt + (dt * 16 + li) * VT_LD + g * 4;
-                const ex4 lo = *reinterpret_cast<const ex4*>(vrow + (2 * t) * 16);
-                ex4 hi = {(E)0.f, (E)0.f, (E)0.f, (E)0.f};
-                if (2 * t + 1 < 9) hi = *reinterpret_cast<const ex4*>(vrow + (2 * t + 1) * 16);
-                ex8 vf;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { vf[e] = lo[e]; vf[4 + e] = hi[e]; }
-                if (dt == 0) o0 = mfma(vf, pf, o0);
-                else o1 = mfma(vf, pf, o1);
+                const ex8 vf = att_vt_frag(Vt + (dt * 16 + li) * VT_LD + g * 4, t);
+                if (dt == 0) o0 = att_mfma<F16>(vf, pf, o0);
+                else o1 = att_mfma<F16>(vf, pf, o1);
             }
-            osum = mfma(ones8, pf, osum);
+            osum = att_mfma<F16>(ones8, pf, osum);
             __builtin_amdgcn_sched_barrier(0);
         }
         if (qsrc >= 0 && slot < nq) {
             const float inv = __builtin_amdgcn_rcpf(osum[0]);
-            E* op = reinterpret_cast<E*>(p.out) + (long)qsrc * C + head * HD + g * 4;
-            ex4 h0, h1;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { h0[e] = (E)(o0[e] * inv); h1[e] = (E)(o1[e] * inv); }
-            *reinterpret_cast<ex4*>(op) = h0;
-            *reinterpret_cast<ex4*>(op + 16) = h1;
+            att_store<ST_S16, E>(p, qsrc, head, g, o0, o1, inv);
         }
     }
 }
 
-static hipError_t check_attention(const WindowAttnParams& p) {
-    const int ws = p.ws ? p.ws : WS;
-    if (!(ws == 12 || ws == 7)) return hipErrorInvalidValue;
-    if (p.C != p.heads * HD || p.Hp % ws || p.Wp % ws || p.Hp < p.H || p.Wp < p.W) return hipErrorInvalidValue;
-    if (!(p.shift == 0 || p.shift == ws / 2)) return hipErrorInvalidValue;
-    if (ws != WS && (p.planes || p.out_planes)) return hipErrorInvalidValue;   // window 7 (Swin-T / S): the fp32-MFMA kernel (fp32 or bf16 matrices in / out)
-    return hipSuccess;
-}
+// which kernel, grid and block: select_window_attention (kernels/window_attention_select.h); here only the two process-wide switches and the launch
 hipError_t launch_window_attention2(const WindowAttnParams& p, const WindowAttnParams* p2, hipStream_t s) {
-    if (check_attention(p) != hipSuccess) return hipErrorInvalidValue;
-    const int ws = p.ws ? p.ws : WS;
-    const int n0 = p.B * (p.Hp / ws) * (p.Wp / ws);
-    int n1 = 0;
-    if (p2) {
-        if ((p2->ws ? p2->ws : WS) != ws) return hipErrorInvalidValue;
-        if (check_attention(*p2) != hipSuccess || p2->C != p.C || p2->heads != p.heads || p2->planes != p.planes || p2->out_planes != p.out_planes || p2->io_bf16 != p.io_bf16) return hipErrorInvalidValue;
-        n1 = p2->B * (p2->Hp / ws) * (p2->Wp / ws);
-    }
-    if (p.out_planes && !((p.out_planes == 2 && p.planes == 2 && (p.out_h2 > 0.f) == (p.h2 != 0)) || (p.out_planes == 3 && p.planes == 0) || (p.out_planes == 2 && p.planes == 0 && p.out_h2 > 0.f && !p.io_bf16)))
-        return hipErrorInvalidValue;
-    if (p.h2 && (p.planes != 2 || p.io_bf16)) return hipErrorInvalidValue;
-    if (p2 && (p2->out_h2 != p.out_h2 || p2->h2 != p.h2)) return hipErrorInvalidValue;
+    // BRN_ATT_HPW: two heads per workgroup of the bf16 kernel is the default — alone the launch is 6 % slower (3.25 against 3.05 ms per 8-image step),
+    // but it reads whole 128-byte lines (one head touches half of every line it fetches: 8.5 GB read against 5.9 algorithmic), and with two sub-batch
+    // streams sharing the HBM the step is 1.0 % faster (tools/ab_env.sh BRN_ATT_HPW "1 2"); BRN_ATT_HPW=1 selects one head
+    static const int hpw = getenv("BRN_ATT_HPW") ? atoi(getenv("BRN_ATT_HPW")) : 2;
+    static const int f32_waves = getenv("BRN_ATT_F32_WAVES") ? atoi(getenv("BRN_ATT_F32_WAVES")) : 9;
+#ifdef BRN_DIAG_BUILD
+    constexpr bool diag = true;
+#else
+    constexpr bool diag = false;
+#endif
+    const AttLaunch l = select_window_attention(p, p2, hpw, f32_waves, diag);
+    if (l.kernel == ATT_INVALID) return hipErrorInvalidValue;
     const WindowAttnParams& q = p2 ? *p2 : p;
-    dim3 grid(n0 + n1, p.heads), block(ATT_THREADS);
     // split / bf16 kernels: real queries only, windows with the most query tiles first (kernels/window_geometry.h; pack_q == 0: all 144
     // positions of every window in grid order, the form before).  A few integers computed here and passed by value: no table in memory
     WindowOrder ord;
-    {
-        const WindowGeom g[2] = {{p.B, p.H, p.W, p.Hp, p.Wp, p.shift}, {q.B, q.H, q.W, q.Hp, q.Wp, q.shift}};
-        build_window_order(g, p2 ? 2 : 1, ws == WS && p.pack_q != 0, p.pack_q != 2, ord);
-    }
-    if (p.io_bf16 && ws == 7) {
-        if (p.out_planes || (p.C & 3)) return hipErrorInvalidValue;
-        if (p.io_bf16 == 2) hipLaunchKernelGGL((window_attention_f32_kernel<7, 3, 2>), grid, block, 0, s, p, q, n0);
-        else hipLaunchKernelGGL((window_attention_f32_kernel<7, 3, 1>), grid, block, 0, s, p, q, n0);
-    } else if (p.io_bf16) {
-        if (p.out_planes || (p.C & 7)) return hipErrorInvalidValue;
-        // (round 2, one stream: two heads per workgroup measured 1 % slower end to end, 224.5 vs 226.8 img/s at batch 8)
-        // round 3: two heads per workgroup is the default — alone the launch is 6 % slower (3.25 against 3.05 ms per 8-image step), but it reads
-        // whole 128-byte lines (one head per workgroup touches half of every line it fetches: 8.5 GB read against 5.9 algorithmic), and with
-        // two sub-batch streams sharing the HBM the step is 1.0 % faster (tools/ab_env.sh BRN_ATT_HPW "1 2"); BRN_ATT_HPW=1 selects one head
-        static const bool two_heads = !(getenv("BRN_ATT_HPW") && atoi(getenv("BRN_ATT_HPW")) == 1);
-        if (p.io_bf16 == 2) {                  // fp16 matrices (compute mode BRN_F16)
-            if (two_heads && !(p.heads & 1)) hipLaunchKernelGGL((window_attention_bf16_kernel<2, true>), dim3(n0 + n1, p.heads / 2), dim3(2 * ATT_THREADS), 0, s, p, q, ord);
-            else hipLaunchKernelGGL((window_attention_bf16_kernel<1, true>), grid, block, 0, s, p, q, ord);
-        } else if (two_heads && !(p.heads & 1)) hipLaunchKernelGGL(window_attention_bf16_kernel<2>, dim3(n0 + n1, p.heads / 2), dim3(2 * ATT_THREADS), 0, s, p, q, ord);
-        else hipLaunchKernelGGL(window_attention_bf16_kernel<1>, grid, block, 0, s, p, q, ord);
-    } else if (p.planes == 2 && p.h2) hipLaunchKernelGGL((window_attention_split_kernel<2, true>), grid, block, 0, s, p, q, ord);
-    else if (p.planes == 2) hipLaunchKernelGGL(window_attention_split_kernel<2>, grid, block, 0, s, p, q, ord);
+    const WindowGeom geom[2] = {{p.B, p.H, p.W, p.Hp, p.Wp, p.shift}, {q.B, q.H, q.W, q.Hp, q.Wp, q.shift}};
+    build_window_order(geom, p2 ? 2 : 1, (p.ws ? p.ws : WS) == WS && p.pack_q != 0, p.pack_q != 2, ord);
+    const dim3 grid(l.grid_x, l.grid_y), block(l.block);
+    switch (l.kernel) {
+    case ATT_F32_W7: hipLaunchKernelGGL(window_attention_f32_kernel<7>, grid, block, 0, s, p, q, l.nblk0); break;
+    case ATT_F32_W7_BF16: hipLaunchKernelGGL((window_attention_f32_kernel<7, 3, 1>), grid, block, 0, s, p, q, l.nblk0); break;
+    case ATT_F32_W7_F16: hipLaunchKernelGGL((window_attention_f32_kernel<7, 3, 2>), grid, block, 0, s, p, q, l.nblk0); break;
+    case ATT_F32_W12_9: hipLaunchKernelGGL((window_attention_f32_kernel<12, 9>), grid, block, 0, s, p, q, l.nblk0); break;
+    case ATT_F32_W12_3: hipLaunchKernelGGL((window_attention_f32_kernel<12, 3>), grid, block, 0, s, p, q, l.nblk0); break;
+    case ATT_SPLIT2: hipLaunchKernelGGL(window_attention_split_kernel<2>, grid, block, 0, s, p, q, ord); break;
+    case ATT_SPLIT2_H: hipLaunchKernelGGL((window_attention_split_kernel<2, true>), grid, block, 0, s, p, q, ord); break;
 #ifdef BRN_DIAG_BUILD
-    else if (p.planes == 1) hipLaunchKernelGGL(window_attention_split_kernel<1>, grid, block, 0, s, p, q, ord);
-#else
-    else if (p.planes == 1) return hipErrorInvalidValue;      // mode bf16_operands: diag build only
+    case ATT_SPLIT1: hipLaunchKernelGGL(window_attention_split_kernel<1>, grid, block, 0, s, p, q, ord); break;
 #endif
-    else if (ws == 7) hipLaunchKernelGGL(window_attention_f32_kernel<7>, grid, block, 0, s, p, q, n0);
-    else {
-        static const int f32_waves = getenv("BRN_ATT_F32_WAVES") ? atoi(getenv("BRN_ATT_F32_WAVES")) : 9;
-        if (f32_waves == 9) hipLaunchKernelGGL((window_attention_f32_kernel<12, 9>), grid, dim3(9 * 64), 0, s, p, q, n0);
-        else hipLaunchKernelGGL((window_attention_f32_kernel<12, 3>), grid, block, 0, s, p, q, n0);
+    case ATT_BF16_1: hipLaunchKernelGGL(window_attention_bf16_kernel<1>, grid, block, 0, s, p, q, ord); break;
+    case ATT_BF16_2: hipLaunchKernelGGL(window_attention_bf16_kernel<2>, grid, block, 0, s, p, q, ord); break;
+    case ATT_F16_1: hipLaunchKernelGGL((window_attention_bf16_kernel<1, true>), grid, block, 0, s, p, q, ord); break;
+    case ATT_F16_2: hipLaunchKernelGGL((window_attention_bf16_kernel<2, true>), grid, block, 0, s, p, q, ord); break;
+    default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }

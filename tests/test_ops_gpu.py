@@ -480,6 +480,43 @@ def test_window_attention_bf16_two_heads_per_workgroup(gpu, tmp_path):
         np.testing.assert_array_equal(res["1"][k], res["2"][k])
 
 
+_ATT_F32_WAVES_CASES = [(1, 18, 18, 2, 0), (1, 18, 18, 2, 6),      # four windows, pad tokens, the mask on edge windows
+                        (1, 12, 30, 2, 6)]                         # one row of three windows, pad columns only
+
+
+def test_window_attention_f32_three_and_nine_waves_per_workgroup(gpu, tmp_path):
+    """both window-12 instantiations of window_attention_f32_kernel — nine waves per workgroup (one query tile each, the default) and three
+    (BRN_ATT_F32_WAVES=3, three query tiles each; the switch is read once per process, hence the child processes) — in the two modes that
+    run the kernel, f32 and f32_split3 (between that mode's three-plane GEMMs): each result against the fp64 restatement at
+    test_window_attention's tolerance, and bit-equal between the two (a query tile's arithmetic is the same code in the same order; only
+    which wave runs it differs)."""
+    import subprocess
+    code = (
+        "import sys, numpy as np, torch; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+        "from candle_birefnet_amd import ops\nimport test_ops_gpu as T\nouts = {}\n"
+        "for i, (B, H, W, heads, shift) in enumerate(T._ATT_F32_WAVES_CASES):\n"
+        "    w, x = T._attn_weights(heads * 32, heads, seed=10), T.rnd(B, H, W, heads * 32, seed=99)\n"
+        "    ref = T.R.window_attention_block(torch.from_numpy(x).double(), w, '', heads, 12, shift, torch.float64).numpy()\n"
+        "    for mode in ('f32', 'f32_split3'):\n"
+        "        ops.set_compute(mode)\n"
+        "        y = ops.window_attention(x, heads, shift, w['attn.qkv.weight'], w['attn.qkv.bias'], w['attn.proj.weight'], w['attn.proj.bias'], w['attn.relative_position_bias_table'])\n"
+        "        ops.set_compute('f32')\n"
+        "        print('f32 attention', mode, (B, H, W, heads, shift), 'max abs err %%.2e, |ref| max %%.2f' %% (np.abs(np.asarray(y, np.float64) - ref).max(), np.abs(ref).max()), flush=True)\n"
+        "        T._close(y, ref)\n"
+        "        outs['%%s_%%d' %% (mode, i)] = np.asarray(y)\n"
+        "np.savez(sys.argv[1], **outs)\n") % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), os.path.dirname(os.path.abspath(__file__)))
+    res = {}
+    for waves in ("3", "9"):
+        out = str(tmp_path / f"waves{waves}.npz")
+        pr = subprocess.run([sys.executable, "-c", code, out], env=dict(os.environ, BRN_ATT_F32_WAVES=waves), capture_output=True, text=True, timeout=600)
+        print(pr.stdout)
+        assert pr.returncode == 0, pr.stdout[-2000:] + pr.stderr[-2000:]
+        res[waves] = np.load(out)
+    assert sorted(res["3"].files) == sorted(res["9"].files) and len(res["3"].files) == 2 * len(_ATT_F32_WAVES_CASES)
+    for k in res["3"].files:
+        np.testing.assert_array_equal(res["3"][k], res["9"][k])
+
+
 @pytest.mark.parametrize("C,H,W,O,act", [(192, 192, 192, 576, None), (192, 181, 183, 768, "gelu_erf"), (192, 192, 171, 192, "relu"), (192, 256, 256, 1152, "gelu_erf"),
                                          (384, 192, 192, 1152, None), (384, 181, 183, 1536, "gelu_erf"), (384, 192, 171, 384, "relu"), (384, 200, 203, 192, None)])
 def test_short_k_weight_stationary_gemm_bf16_mode(gpu, C, H, W, O, act):
