@@ -159,6 +159,18 @@ hipError_t launch_window_attention(const WindowAttnParams& p, hipStream_t s);
 // two maps of the same stage in one launch (p2 may be null)
 hipError_t launch_window_attention2(const WindowAttnParams& p, const WindowAttnParams* p2, hipStream_t s);
 
+// q/k/v attention with an additive bias (kernels/attention_bias.hip; brn_attention_forward):
+// y[b,h] = softmax_rows(scale * (q[b,h] k[b,h]^T + bias[b % n_bias, h])) v[b,h], head_dim 32, 1 <= N <= 144
+struct AttentionBiasParams {
+    const float* q; const float* k; const float* v;   // [batch, heads, N, 32], 16-byte aligned
+    const float* bias;    // [n_bias, heads, N, N] or null (n_bias 0); added to the UNSCALED scores
+    float* y;             // [batch, heads, N, 32]
+    int batch, heads, N, n_bias;
+    float scale;          // > 0 (the entry replaces 0 by head_dim^-0.5)
+    int s16;              // 0: fp32 MFMA kernel; 1 / 2: q, k, v and the probabilities rounded to bf16 / fp16 on the 16-bit matrix instructions
+};
+hipError_t launch_attention_bias(const AttentionBiasParams& p, hipStream_t s);
+
 // ---- data movement / elementwise (HBM-bound) ------------------------------------------------------------
 // bilinear, align_corners=true, channels-last window -> window; optional accumulate (y += )
 hipError_t launch_resize_nhwc(const float* x, int B, int Hin, int Win, int C, int ldx, int x_coff,

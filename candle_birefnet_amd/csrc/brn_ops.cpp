@@ -2,6 +2,7 @@
 // weights per call, in the arithmetic brn_set_op_compute selected on the calling thread.  Weights are always host pointers; x / y /
 // residual follow `loc`.
 #include "brn_api_util.h"
+#include <cmath>
 #include <cstring>
 #include <memory>
 
@@ -230,6 +231,41 @@ brn_status brn_window_attention_forward(const float* x, int B, int H, int W, int
             const float* xn = s16 ? round_to_s16(c, dx, (size_t)B * H * W * C, wb.f16) : dx;
             swin_attention(c, bk, xn, B, H, W, C, shift, dy, nullptr, window_size);
         }, s16);
+        st.finish();
+    });
+}
+
+brn_status brn_attention_forward(const float* q, const float* k, const float* v, int batch, int heads, int N, int head_dim,
+                                 const float* bias, int n_bias, float scale, float* y, brn_mem loc, int device, void* stream) {
+    return guarded([&] {
+        if (!q || !k || !v || !y) fail(BRN_ERR_INVALID_ARG, "attention: null q, k, v or y");
+        if (head_dim != 32) fail(BRN_ERR_INVALID_ARG, "attention: head_dim %d unsupported (head_dim must be 32)", head_dim);
+        if (N < 1 || N > 144) fail(BRN_ERR_INVALID_ARG, "attention: sequence length N = %d unsupported (1 <= N <= 144)", N);
+        if (batch < 1 || heads < 1 || (long long)batch * heads > 0x7fffffffLL)
+            fail(BRN_ERR_INVALID_ARG, "attention: batch %d, heads %d unsupported (batch >= 1, heads >= 1, batch * heads < 2^31)", batch, heads);
+        if (n_bias < 0) fail(BRN_ERR_INVALID_ARG, "attention: n_bias %d is negative (n_bias >= 0)", n_bias);
+        if ((bias == nullptr) != (n_bias == 0)) fail(BRN_ERR_INVALID_ARG, "attention: bias must be NULL exactly when n_bias == 0 (n_bias %d)", n_bias);
+        if (n_bias > 0 && batch % n_bias) fail(BRN_ERR_INVALID_ARG, "attention: batch %d is not a multiple of n_bias %d (batch %% n_bias == 0)", batch, n_bias);
+        if (!(scale >= 0.f) || !std::isfinite(scale)) fail(BRN_ERR_INVALID_ARG, "attention: scale must be finite and >= 0 (0 = head_dim^-0.5)");
+        const size_t n = (size_t)batch * heads * N * head_dim, nb = (size_t)n_bias * heads * N * N;
+        const uintptr_t y0 = reinterpret_cast<uintptr_t>(y), y1 = y0 + n * sizeof(float);
+        auto overlaps = [&](const float* a, size_t na) { const uintptr_t a0 = reinterpret_cast<uintptr_t>(a); return a && a0 < y1 && y0 < a0 + na * sizeof(float); };
+        if (overlaps(q, n) || overlaps(k, n) || overlaps(v, n) || overlaps(bias, nb)) fail(BRN_ERR_INVALID_ARG, "attention: y must not alias an input");
+        if (loc == BRN_MEM_DEVICE)              // (host buffers are staged into allocations of the library's own)
+            for (const float* a : {q, k, v, (const float*)y})
+                if (reinterpret_cast<uintptr_t>(a) & 15) fail(BRN_ERR_INVALID_ARG, "attention: device q, k, v and y must be 16-byte aligned");
+        ensure_device(device);
+        Staging st(stream, loc);
+        AttentionBiasParams p{};
+        p.q = st.in(q, n); p.k = st.in(k, n); p.v = st.in(v, n);
+        p.bias = bias ? st.in(bias, nb) : nullptr;
+        p.y = st.out(y, n);
+        p.batch = batch; p.heads = heads; p.N = N; p.n_bias = n_bias;
+        p.scale = scale > 0.f ? scale : 1.0f / sqrtf((float)head_dim);
+        // modes bf16 / f16: q, k, v are rounded to the 16-bit type as the kernel loads them; every other mode runs the exact fp32-MFMA
+        // kernel between its own GEMMs (as window-7 attention does)
+        p.s16 = op_s16(g_op);
+        BRN_HIP(launch_attention_bias(p, (hipStream_t)stream));
         st.finish();
     });
 }

@@ -85,6 +85,37 @@ def window_attention(x, heads, shift, qkv_w, qkv_b, proj_w, proj_b, rel_table, w
     return y
 
 
+def attention(q, k, v, bias=None, n_bias=None, scale=None, device=0):
+    """y[b,h] = softmax(scale * (q[b,h] k[b,h]^T + bias[b % n_bias, h])) v[b,h]: q, k, v [batch, heads, N, 32]; bias [n_bias, heads, N, N]
+    (added to the UNSCALED scores) or None.  n_bias None = bias.shape[0]; scale None = head_dim^-0.5.  The limits are the library's
+    (include/birefnet_hip.h brn_attention_forward): nothing is checked here."""
+    batch, heads, N, hd = (int(s) for s in q.shape)
+    pq, loc, keep, _ = T.as_arg(q)
+    pk, kloc, kkeep, _ = T.as_arg(k, (batch, heads, N, hd))
+    pv, vloc, vkeep, _ = T.as_arg(v, (batch, heads, N, hd))
+    pb, bloc, bkeep, _ = T.as_arg(bias) if bias is not None else (None, loc, None, None)
+    if not (kloc == vloc == bloc == loc):
+        raise ValueError("q, k, v and bias must live on the same side")
+    if n_bias is None:
+        n_bias = int(bias.shape[0]) if bias is not None else 0
+    y = T.alloc_like(keep, (batch, heads, N, hd))
+    _ffi.check(_ffi.lib.brn_attention_forward(pq, pk, pv, batch, heads, N, hd, pb, int(n_bias), float(scale) if scale is not None else 0.0,
+                                              T.ptr_of(y), loc, T.device_of(keep, device), T.stream_of(keep)))
+    return y
+
+
+def attention_with_bias(q, k, v, scaled_bias):
+    """flash_attention_with_bias(&q, &k, &v, &scaled_bias, false) (swin.rs:252): scaled_bias [1 or batch, heads, N, N] is the bias
+    already divided by the softmax scale (swin.rs:250)."""
+    return attention(q, k, v, scaled_bias)
+
+
+def attention_with_repeating_bias(q, k, v, scaled_bias, n_windows):
+    """flash_attention_with_repeating_bias(&q, &k, &v, &scaled_combined, n_windows, false) (swin.rs:243): scaled_bias
+    [n_windows, heads, N, N], batch entry b reads pattern b % n_windows (swin.rs:291-294)."""
+    return attention(q, k, v, scaled_bias, n_bias=int(n_windows))
+
+
 def patch_merging(x, H, W, norm_g, norm_b, reduction_w, device=0):
     """PatchMerging::forward (swin.rs:491-527): x [B,H*W,C] -> [B, ceil(H/2)*ceil(W/2), 2C]."""
     B, L, Cc = (int(v) for v in x.shape)

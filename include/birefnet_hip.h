@@ -246,6 +246,28 @@ brn_status brn_window_attention_forward(const float* x, int B, int H, int W, int
                                         int shift, const float* qkv_w, const float* qkv_b,
                                         const float* proj_w, const float* proj_b, const float* rel_table,
                                         float* y, brn_mem loc, int device_ordinal, void* stream);
+/* candle_mps_flash_attention::flash_attention_with_bias / flash_attention_with_repeating_bias as WindowAttention::forward
+ * calls them (swin.rs:243, 252; examples/test_flash_bias.rs):
+ *   y[b,h] = softmax_rows( scale * (q[b,h] k[b,h]^T + bias[b % n_bias, h]) ) v[b,h]
+ * q, k, v, y: [batch, heads, N, head_dim] contiguous; bias: [n_bias, heads, N, N] contiguous or NULL (n_bias 0).
+ * The bias is added to the UNSCALED scores, as MFA does; swin.rs:233-250 pre-multiplies it by 1/scale for that reason.
+ * scale 0 = 1/sqrt(head_dim).  n_bias 1 = one bias for every batch entry (W-MSA);
+ * n_bias = n_windows with batch % n_bias == 0 = the repeating form (SW-MSA, the index of swin.rs:291-294).
+ * Limits (each violation is BRN_ERR_INVALID_ARG, checked before the device): head_dim == 32; 1 <= N <= 144; batch >= 1, heads >= 1
+ * (batch * heads < 2^31); n_bias >= 0, bias NULL exactly when n_bias == 0, batch % n_bias == 0 when n_bias > 0; scale finite and >= 0;
+ * q, k, v, y not NULL; y does not overlap an input; BRN_MEM_DEVICE q, k, v, y 16-byte aligned.  All five buffers live where `loc`
+ * says; the stream and synchronisation conventions at the top of this header apply.
+ * Arithmetic follows brn_set_op_compute on the calling thread.  BRN_F32: v_mfma_f32_16x16x4_f32, exact fmaf chains.  BRN_F32_SPLIT3 /
+ * BRN_F32_SPLIT2 / BRN_F32_HALF2: the SAME fp32 kernel, bit-identical results (exact fp32 attention between the mode's own GEMMs, as
+ * window-7 attention in those modes).  BRN_BF16 / BRN_F16: q, k, v are rounded to the 16-bit type at the edge (round to nearest
+ * even), q k^T and P v run on the 16-bit matrix instructions with fp32 accumulation, and the softmax numerators are rounded to the
+ * 16-bit type for P v; the bias, the scores, the row maximum, the row sum (taken from the unrounded numerators) and y stay fp32.
+ * Softmax subtracts the row maximum first; the result for a batch entry does not depend on `batch`.
+ * Not provided: the causal flag of the MFA calls (the reference always passes false); long sequences and head_dim 64 / 128 (the LLM
+ * shapes of examples/bench_flash_attn.rs:77-84); the [batch, seq, heads, head_dim] layout of the bias-free flash_attention. */
+brn_status brn_attention_forward(const float* q, const float* k, const float* v, int batch, int heads, int N, int head_dim,
+                                 const float* bias, int n_bias, float scale,
+                                 float* y, brn_mem loc, int device_ordinal, void* stream);
 /* PatchMerging::forward (swin.rs:491-527): x [B,H*W,C] -> [B, ceil(H/2)*ceil(W/2), 2C]. */
 brn_status brn_patch_merging_forward(const float* x, int B, int H, int W, int C, const float* norm_g,
                                      const float* norm_b, const float* reduction_w, float* y, brn_mem loc,

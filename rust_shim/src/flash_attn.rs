@@ -1,0 +1,45 @@
+//! The two attention calls `WindowAttention::forward` makes behind its `flash-attn` feature (src/swin.rs:243, 252), over
+//! `brn_attention_forward`: the narrow seam.  A `hip` feature beside `flash-attn` at swin.rs:226-258 keeps candle's `WindowAttention`
+//! (qkv, cached_bias, mask, proj) and swaps only these calls:
+//!
+//!   #[cfg(feature = "hip")]
+//!   use candle_birefnet_hip::flash_attn::{flash_attention_with_bias, flash_attention_with_repeating_bias};
+//!
+//! Same arguments, same pre-scaled bias (the bias is added to the UNSCALED scores, swin.rs:231-233), same `[batch, heads, N, head_dim]`
+//! result.  Limits are the library's (include/birefnet_hip.h): head_dim 32, N <= 144, no causal mask.
+use candle_core::{Result, Tensor};
+
+use crate::hip_ffi as ffi;
+
+/// y[b,h] = softmax(scale * (q k^T + bias[b % n_bias, h])) v, scale = head_dim^-0.5; tensors travel as host buffers
+fn attention(q: &Tensor, k: &Tensor, v: &Tensor, bias: &Tensor, n_bias: usize, causal: bool) -> Result<Tensor> {
+    if causal {
+        candle_core::bail!("flash attention on the hip backend has no causal mask (the reference always passes false, swin.rs:243, 252)")
+    }
+    let (batch, heads, n, head_dim) = q.dims4()?;
+    if k.dims4()? != (batch, heads, n, head_dim) || v.dims4()? != (batch, heads, n, head_dim) {
+        candle_core::bail!("q, k and v must share the shape [batch, heads, N, head_dim]")
+    }
+    let (nb, bh, bn0, bn1) = bias.dims4()?;
+    if nb != n_bias || bh != heads || bn0 != n || bn1 != n {
+        candle_core::bail!("bias must be [{n_bias}, {heads}, {n}, {n}], got {:?}", bias.dims())
+    }
+    let (qh, kh, vh, bhost) = (ffi::to_host(q)?, ffi::to_host(k)?, ffi::to_host(v)?, ffi::to_host(bias)?);
+    let mut out = vec![0f32; batch * heads * n * head_dim];
+    ffi::check(unsafe {
+        ffi::brn_attention_forward(qh.as_ptr(), kh.as_ptr(), vh.as_ptr(), batch as i32, heads as i32, n as i32, head_dim as i32, bhost.as_ptr(),
+                                   n_bias as i32, 0.0, out.as_mut_ptr(), ffi::BRN_MEM_HOST, 0, std::ptr::null_mut())
+    })?;
+    Tensor::from_vec(out, (batch, heads, n, head_dim), q.device())
+}
+
+/// `candle_mps_flash_attention::flash_attention_with_bias(&q, &k, &v, &scaled_bias, false)` (swin.rs:252): bias `[1 or batch, heads, N, N]`
+pub fn flash_attention_with_bias(q: &Tensor, k: &Tensor, v: &Tensor, bias: &Tensor, causal: bool) -> Result<Tensor> {
+    attention(q, k, v, bias, bias.dim(0)?, causal)
+}
+
+/// `candle_mps_flash_attention::flash_attention_with_repeating_bias(&q, &k, &v, &scaled_combined, n_windows, false)` (swin.rs:243): bias
+/// `[n_windows, heads, N, N]`, batch entry b reads pattern b % n_windows (the window order of swin.rs:291-294)
+pub fn flash_attention_with_repeating_bias(q: &Tensor, k: &Tensor, v: &Tensor, bias: &Tensor, n_windows: usize, causal: bool) -> Result<Tensor> {
+    attention(q, k, v, bias, n_windows, causal)
+}

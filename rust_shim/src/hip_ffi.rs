@@ -118,6 +118,9 @@ extern "C" {
                                         shift: c_int, qkv_w: *const c_float, qkv_b: *const c_float, proj_w: *const c_float,
                                         proj_b: *const c_float, rel_table: *const c_float, y: *mut c_float, loc: c_int,
                                         device_ordinal: c_int, stream: *mut c_void) -> c_int;
+    pub fn brn_attention_forward(q: *const c_float, k: *const c_float, v: *const c_float, batch: c_int, heads: c_int, n: c_int, head_dim: c_int,
+                                 bias: *const c_float, n_bias: c_int, scale: c_float, y: *mut c_float, loc: c_int, device_ordinal: c_int,
+                                 stream: *mut c_void) -> c_int;
     pub fn brn_patch_merging_forward(x: *const c_float, b: c_int, h: c_int, w: c_int, c: c_int, norm_g: *const c_float,
                                      norm_b: *const c_float, reduction_w: *const c_float, y: *mut c_float, loc: c_int,
                                      device_ordinal: c_int, stream: *mut c_void) -> c_int;

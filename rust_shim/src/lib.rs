@@ -11,6 +11,7 @@ pub mod decoder;
 pub mod aspp;
 pub mod birefnet;
 pub mod swin;
+pub mod flash_attn;
 
 pub use birefnet::BiRefNet;
 pub use deform_conv::DeformableConv2d;
