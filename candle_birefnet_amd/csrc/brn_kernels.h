@@ -171,6 +171,20 @@ struct AttentionBiasParams {
 };
 hipError_t launch_attention_bias(const AttentionBiasParams& p, hipStream_t s);
 
+// q/k/v attention for long sequences, online softmax over K / V tiles (kernels/flash_attention.hip; brn_flash_attention_forward):
+// y[b,h] = softmax_rows(scale * q[b,h] k[b,h]^T [causal: key j <= query i]) v[b,h], head_dim 32 / 64 / 128, 1 <= seq_q, seq_kv <= 65536
+struct FlashAttentionParams {
+    const float* q; const float* k; const float* v;   // 16-byte aligned; head_dim contiguous
+    float* y;             // q's shape and strides
+    int batch, heads, seq_q, seq_kv, head_dim;
+    long q_sb, q_sh, q_ss;       // element strides of q and y: batch entry, head, sequence position (multiples of head_dim)
+    long kv_sb, kv_sh, kv_ss;    // element strides of k and v
+    int causal;           // 1: key j takes part in query i's row exactly when j <= i (seq_q == seq_kv)
+    float scale;          // > 0 (the entry replaces 0 by head_dim^-0.5)
+    int s16;              // 0: fp32 MFMA kernel; 1 / 2: q, k, v and the softmax numerators rounded to bf16 / fp16 on the 16-bit matrix instructions
+};
+hipError_t launch_flash_attention(const FlashAttentionParams& p, hipStream_t s);
+
 // ---- data movement / elementwise (HBM-bound) ------------------------------------------------------------
 // bilinear, align_corners=true, channels-last window -> window; optional accumulate (y += )
 hipError_t launch_resize_nhwc(const float* x, int B, int Hin, int Win, int C, int ldx, int x_coff,

@@ -270,6 +270,52 @@ brn_status brn_attention_forward(const float* q, const float* k, const float* v,
     });
 }
 
+brn_status brn_flash_attention_forward(const float* q, const float* k, const float* v, int batch, int seq_q, int seq_kv, int heads, int head_dim,
+                                       int layout, int causal, float scale, float* y, brn_mem loc, int device, void* stream) {
+    return guarded([&] {
+        if (!q || !k || !v || !y) fail(BRN_ERR_INVALID_ARG, "flash attention: null q, k, v or y");
+        if (!(head_dim == 32 || head_dim == 64 || head_dim == 128))
+            fail(BRN_ERR_INVALID_ARG, "flash attention: head_dim %d unsupported (head_dim must be 32, 64 or 128)", head_dim);
+        if (seq_q < 1 || seq_q > 65536 || seq_kv < 1 || seq_kv > 65536)
+            fail(BRN_ERR_INVALID_ARG, "flash attention: seq_q %d, seq_kv %d unsupported (1 <= seq_q, seq_kv <= 65536)", seq_q, seq_kv);
+        if (batch < 1 || heads < 1) fail(BRN_ERR_INVALID_ARG, "flash attention: batch %d, heads %d unsupported (batch >= 1, heads >= 1)", batch, heads);
+        if ((long long)batch * heads * ((seq_q + 15) / 16) > 0x7fffffffLL)
+            fail(BRN_ERR_INVALID_ARG, "flash attention: batch %d, heads %d, seq_q %d too large (batch * heads * ceil(seq_q / 16) < 2^31)", batch, heads, seq_q);
+        if (layout != BRN_ATTN_BSHD && layout != BRN_ATTN_BHSD) fail(BRN_ERR_INVALID_ARG, "flash attention: layout %d unknown (layout must be 0 = BSHD or 1 = BHSD)", layout);
+        if (causal != 0 && causal != 1) fail(BRN_ERR_INVALID_ARG, "flash attention: causal %d (causal must be 0 or 1)", causal);
+        if (causal && seq_q != seq_kv) fail(BRN_ERR_INVALID_ARG, "flash attention: causal requires seq_q == seq_kv (seq_q %d, seq_kv %d)", seq_q, seq_kv);
+        if (!(scale >= 0.f) || !std::isfinite(scale)) fail(BRN_ERR_INVALID_ARG, "flash attention: scale must be finite and >= 0 (0 = head_dim^-0.5)");
+        const size_t nq = (size_t)batch * heads * seq_q * head_dim, nkv = (size_t)batch * heads * seq_kv * head_dim;
+        const uintptr_t y0 = reinterpret_cast<uintptr_t>(y), y1 = y0 + nq * sizeof(float);
+        auto overlaps = [&](const float* a, size_t na) { const uintptr_t a0 = reinterpret_cast<uintptr_t>(a); return a0 < y1 && y0 < a0 + na * sizeof(float); };
+        if (overlaps(q, nq) || overlaps(k, nkv) || overlaps(v, nkv)) fail(BRN_ERR_INVALID_ARG, "flash attention: y must not overlap an input");
+        if (loc == BRN_MEM_DEVICE)              // (host buffers are staged into allocations of the library's own)
+            for (const float* a : {q, k, v, (const float*)y})
+                if (reinterpret_cast<uintptr_t>(a) & 15) fail(BRN_ERR_INVALID_ARG, "flash attention: device q, k, v and y must be 16-byte aligned");
+        ensure_device(device);
+        Staging st(stream, loc);
+        FlashAttentionParams p{};
+        p.q = st.in(q, nq); p.k = st.in(k, nkv); p.v = st.in(v, nkv);
+        p.y = st.out(y, nq);
+        p.batch = batch; p.heads = heads; p.seq_q = seq_q; p.seq_kv = seq_kv; p.head_dim = head_dim;
+        // one kernel for both layouts: element strides of (batch entry, head, sequence position)
+        const long d = head_dim;
+        if (layout == BRN_ATTN_BSHD) {
+            p.q_ss = heads * d; p.q_sh = d; p.q_sb = seq_q * p.q_ss;
+            p.kv_ss = heads * d; p.kv_sh = d; p.kv_sb = seq_kv * p.kv_ss;
+        } else {
+            p.q_ss = d; p.q_sh = seq_q * d; p.q_sb = heads * p.q_sh;
+            p.kv_ss = d; p.kv_sh = seq_kv * d; p.kv_sb = heads * p.kv_sh;
+        }
+        p.causal = causal;
+        p.scale = scale > 0.f ? scale : 1.0f / sqrtf((float)head_dim);
+        // modes bf16 / f16: q, k, v are rounded to the 16-bit type as the kernel loads them; every other mode runs the exact fp32-MFMA kernel
+        p.s16 = op_s16(g_op);
+        BRN_HIP(launch_flash_attention(p, (hipStream_t)stream));
+        st.finish();
+    });
+}
+
 brn_status brn_patch_merging_forward(const float* x, int B, int H, int W, int C, const float* ng, const float* nb,
                                      const float* rw, float* y, brn_mem loc, int device, void* stream) {
     return guarded([&] {

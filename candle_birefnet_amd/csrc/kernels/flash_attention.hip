@@ -1,0 +1,362 @@
+// flash_attention.hip — q/k/v attention for long sequences (brn_flash_attention_forward):
+//   y[b,h] = softmax_rows( scale * q[b,h] k[b,h]^T  [causal: key j takes part in query i's row exactly when j <= i] ) v[b,h]
+// the plain flash_attention(&q, &k, &v, causal) of the reference's flash-attn dependency (examples/bench_flash_attn.rs:39-53), head_dim
+// 32 / 64 / 128, 1 <= seq <= 65536, q and k/v of different lengths, in either the [batch, seq, heads, head_dim] or the
+// [batch, heads, seq, head_dim] layout: the kernels take element strides (batch entry, head, sequence position; head_dim contiguous).
+// It is the sibling of kernels/attention_bias.hip, which holds a whole score row of <= 144 keys in registers; here the row never exists.
+// The file is self-contained (unnamed namespace), so nothing in the other attention kernels moves.
+//
+// One workgroup = one (batch entry, head, tile of FA_BQ = 64 queries) = 4 waves; one wave = 16 queries.  K and V are walked in tiles of
+// FA_T = 64 keys staged in LDS (single-buffered; the NEXT tile's global loads are issued into registers before the current tile is
+// computed, so they fly under the MFMAs and are written to LDS after the barrier that ends the tile).  Per wave and tile, MFMA
+// formulation as in attention_bias.hip (all tiles 16x16; C/D map: col = lane & 15, row = 4 (lane >> 4) + reg):
+//   S^T[key][query] = K . Q^T            4 key sub-tiles of 16; a lane's 4 registers of a sub-tile are 4 consecutive keys of ITS query
+//   online softmax                       scores * (scale * log2 e); excluded keys -> -3e38; tile maximum in-lane then across the 4 lane
+//                                        groups (shfl_xor 16, 32); m_new = max(m, tile max); alpha = exp2(m - m_new) rescales the
+//                                        running sum l and the O accumulators; numerators exp2(s - m_new); l += the lane's UNROUNDED
+//                                        numerators (a lane's l is a partial sum over its keys: alpha is the same in the 4 lanes of
+//                                        a query, so the 4 partials are added once, after the last tile)
+//   O^T[d][query] += V^T . P^T           B = P^T straight from the S^T accumulator registers, A = V^T from LDS
+// m, l and O^T (head_dim / 16 accumulators of 4 registers) live in registers for the whole walk.  There is no split over keys between
+// workgroups, no atomics, nothing shared between workgroups: an output row depends only on its own (batch entry, head), and the bits
+// depend neither on `batch` nor on the grid.  Every loop bound is a function of the arguments.
+// Ragged edges: K / V rows past seq_kv are ZEROS in LDS (their address is clamped to the last real row, the value replaced) and their
+// scores are excluded; a pad query computes on the last real row and is never stored; every global address is clamped into the
+// (batch entry, head) it belongs to.  Causal: tiles wholly above the workgroup's diagonal are not walked; in the others the keys after
+// a lane's query are excluded.  Key 0 is visible to every query, so after the first tile every m is a real score: alpha never sees
+// (-3e38) - (-3e38) with a non-zero l behind it, and exp2(excluded - m) is exactly 0 — an excluded key is in neither the maximum nor
+// the sum.
+#include "../brn_kernels.h"
+#include "split_planes.h"
+#include <type_traits>
+
+namespace brn {
+namespace {
+
+constexpr int FA_BQ = 64;            // queries per workgroup: 4 waves x 16
+constexpr int FA_T = 64;             // keys per K / V tile
+constexpr int FA_THREADS = 256;
+constexpr int FA_VT_LD = 72;         // 16-bit kernel: elements per LDS row of V^T (36 dwords: conflict-free 8-byte reads, 2-way 4-byte writes)
+constexpr float FA_LOG2E = 1.4426950408889634f;
+constexpr float FA_NEG = -3.0e38f;
+
+template <typename E> using fa_vec8 = E __attribute__((ext_vector_type(8)));
+template <typename E> using fa_vec4 = E __attribute__((ext_vector_type(4)));
+template <typename E> using fa_vec2 = E __attribute__((ext_vector_type(2)));
+
+// which (batch entry, head, query tile) this workgroup owns, where its operands start and how many K / V tiles it walks
+struct FaBlock {
+    const float* q; const float* k; const float* v; float* y;
+    int q0;               // first query of the tile
+    int nkt;              // K / V tiles to walk: all of them, or (causal) those that reach the tile's last query
+};
+__device__ __forceinline__ FaBlock fa_block(const FlashAttentionParams& p) {
+    const int nqt = (p.seq_q + FA_BQ - 1) / FA_BQ;
+    // not causal: the query tiles of a (batch entry, head) are neighbours in the grid (they walk the same K and V).  Causal: tile qt walks
+    // qt + 1 K / V tiles, so the grid is ordered by query tile, last (longest) first: the launch ends on the short workgroups
+    int bh, qt;
+    if (p.causal) {
+        const unsigned nbh = (unsigned)(p.batch * p.heads);
+        qt = nqt - 1 - (int)(blockIdx.x / nbh); bh = (int)(blockIdx.x % nbh);
+    } else {
+        bh = (int)(blockIdx.x / (unsigned)nqt); qt = (int)(blockIdx.x - (unsigned)bh * (unsigned)nqt);
+    }
+    const int b = bh / p.heads, h = bh - b * p.heads;
+    FaBlock r;
+    r.q = p.q + b * p.q_sb + h * p.q_sh;
+    r.y = p.y + b * p.q_sb + h * p.q_sh;
+    r.k = p.k + b * p.kv_sb + h * p.kv_sh;
+    r.v = p.v + b * p.kv_sb + h * p.kv_sh;
+    r.q0 = qt * FA_BQ;
+    r.nkt = (p.seq_kv + FA_T - 1) / FA_T;
+    if (p.causal) r.nkt = min(r.nkt, min(r.q0 + FA_BQ - 1, p.seq_q - 1) / FA_T + 1);
+    return r;
+}
+
+// One tile of the online softmax.  st: the lane's raw scores of keys key0 + 16 s + 4 g + r (s = sub-tile, r = register) of its query;
+// limit: the lane's first excluded key (seq_kv, or query + 1 under the causal mask); mask: whether this tile can hold an excluded key
+// for some lane of the wave (wave-uniform).  Leaves the numerators in st, updates m and l, returns alpha.
+__device__ __forceinline__ float fa_softmax_tile(f32x4 (&st)[FA_T / 16], float sc2, bool mask, int key0, int g, int limit, float& m, float& l) {
+    float mx = FA_NEG;
+#pragma unroll
+    for (int s = 0; s < FA_T / 16; ++s) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) st[s][r] *= sc2;
+        if (mask) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) st[s][r] = (key0 + s * 16 + g * 4 + r < limit) ? st[s][r] : FA_NEG;
+        }
+        mx = fmaxf(fmaxf(mx, fmaxf(st[s][0], st[s][1])), fmaxf(st[s][2], st[s][3]));
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 16));
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    const float mn = fmaxf(m, mx);
+    const float alpha = __builtin_amdgcn_exp2f(m - mn);
+    float sum = 0.f;
+#pragma unroll
+    for (int s = 0; s < FA_T / 16; ++s) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float e = __builtin_amdgcn_exp2f(st[s][r] - mn);
+            st[s][r] = e;
+            sum += e;
+        }
+    }
+    m = mn;
+    l = l * alpha + sum;
+    return alpha;
+}
+// whether the tile at key0 can hold an excluded key for a lane of this wave (rows: the wave's first query row, clamped)
+__device__ __forceinline__ bool fa_tile_masks(const FlashAttentionParams& p, int key0, int wave_row0) {
+    const int lim = p.causal ? min(p.seq_kv, wave_row0 + 1) : p.seq_kv;
+    return key0 + FA_T > lim;
+}
+// lane holds O^T[d = 16 dt + 4 g + r][query]: one 16-byte store per d tile into the query's row of y
+template <int ND>
+__device__ __forceinline__ void fa_store(float* yrow, int g, const f32x4 (&o)[ND], float l) {
+    l += __shfl_xor(l, 16);
+    l += __shfl_xor(l, 32);
+    const float inv = 1.0f / l;
+    if (yrow) {
+#pragma unroll
+        for (int dt = 0; dt < ND; ++dt) *reinterpret_cast<f32x4*>(yrow + dt * 16 + g * 4) = o[dt] * inv;
+    }
+}
+
+// ---- fp32: v_mfma_f32_16x16x4_f32, an exact fmaf chain per score and per output ----
+// LDS: Ks, Vs [64][D + 4] floats (D 128: 66 KB).  Staging item = (key, 4-wide d chunk), D / 16 items of K and of V per thread.
+template <int D>
+__global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const FlashAttentionParams p) {
+    constexpr int LD = D + 4, NI = D / 16, ND = D / 16, NC = D / 32;
+    __shared__ __attribute__((aligned(16))) float Ks[FA_T * LD];
+    __shared__ __attribute__((aligned(16))) float Vs[FA_T * LD];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int li = lane & 15, g = lane >> 4;
+    const FaBlock blk = fa_block(p);
+
+    const int query = blk.q0 + wave * 16 + li, qrow = min(query, p.seq_q - 1);
+    const int wave_row0 = min(blk.q0 + wave * 16, p.seq_q - 1);
+    const int limit = p.causal ? min(p.seq_kv, qrow + 1) : p.seq_kv;
+    // Q fragment: chunk c of 32 d's -> d = 32 c + 8 g .. + 7 of the query's row (the MFMA k order is a permutation of d; K uses the same)
+    f32x4 qv[2 * NC];
+    {
+        const float* qp = blk.q + qrow * p.q_ss + g * 8;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            qv[2 * c] = *reinterpret_cast<const f32x4*>(qp + c * 32);
+            qv[2 * c + 1] = *reinterpret_cast<const f32x4*>(qp + c * 32 + 4);
+        }
+    }
+    f32x4 kr[NI], vr[NI];
+    auto load_tile = [&](int key0) {
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const int idx = tid + i * FA_THREADS, t = key0 + idx / (D / 4), c4 = (idx % (D / 4)) * 4;
+            const long src = min(t, p.seq_kv - 1) * p.kv_ss + c4;
+            kr[i] = *reinterpret_cast<const f32x4*>(blk.k + src);
+            vr[i] = *reinterpret_cast<const f32x4*>(blk.v + src);
+            if (t >= p.seq_kv) { kr[i] = f32x4{0.f, 0.f, 0.f, 0.f}; vr[i] = kr[i]; }
+        }
+    };
+    f32x4 o[ND];
+#pragma unroll
+    for (int dt = 0; dt < ND; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float m = FA_NEG, l = 0.f;
+    const float sc2 = p.scale * FA_LOG2E;
+
+    load_tile(0);
+    for (int kt = 0; kt < blk.nkt; ++kt) {
+        __syncthreads();                                   // every wave is done reading the previous tile
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const int idx = tid + i * FA_THREADS, t = idx / (D / 4), c4 = (idx % (D / 4)) * 4;
+            *reinterpret_cast<f32x4*>(Ks + t * LD + c4) = kr[i];
+            *reinterpret_cast<f32x4*>(Vs + t * LD + c4) = vr[i];
+        }
+        __syncthreads();
+        if (kt + 1 < blk.nkt) load_tile((kt + 1) * FA_T);
+        // S^T = K . Q^T
+        f32x4 st[FA_T / 16];
+#pragma unroll
+        for (int s = 0; s < FA_T / 16; ++s) {
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                const float* kp = Ks + (s * 16 + li) * LD + c * 32 + g * 8;
+                const f32x4 k0 = *reinterpret_cast<const f32x4*>(kp);
+                const f32x4 k1 = *reinterpret_cast<const f32x4*>(kp + 4);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(k0[e], qv[2 * c][e], acc, 0, 0, 0);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(k1[e], qv[2 * c + 1][e], acc, 0, 0, 0);
+            }
+            st[s] = acc;
+        }
+        const float alpha = fa_softmax_tile(st, sc2, fa_tile_masks(p, kt * FA_T, wave_row0), kt * FA_T, g, limit, m, l);
+#pragma unroll
+        for (int dt = 0; dt < ND; ++dt) o[dt] *= alpha;
+        // O^T += V^T . P^T
+#pragma unroll
+        for (int s = 0; s < FA_T / 16; ++s) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float* vp = Vs + (s * 16 + g * 4 + r) * LD + li;
+#pragma unroll
+                for (int dt = 0; dt < ND; ++dt) o[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(vp[dt * 16], st[s][r], o[dt], 0, 0, 0);
+            }
+        }
+    }
+    fa_store<ND>(query < p.seq_q ? blk.y + query * p.q_ss : nullptr, g, o, l);
+}
+
+// ---- 16-bit: q, k, v rounded to E (round to nearest even) as they are loaded; v_mfma_f32_16x16x32_{bf16,f16} with fp32 accumulation.
+// Scores, m, l (of the UNROUNDED numerators) and O are fp32; the numerators are rounded to E for P . V.
+// LDS: Kp[key][D] (16-byte chunk c of a row stored at c ^ fa_kswz(key): conflict-free ds_read_b128 of the A operand) and Vt[d][72 keys]
+// (V transposed: the A operand of O^T = V^T P^T is 8 keys of one d): D 128 = 16 + 18 KB.  An MFMA of P . V contracts sub-tiles
+// (2t, 2t+1): lane group g's k slots are keys 16 (2t) + 4g + 0..3 and 16 (2t+1) + 4g + 0..3 — the keys whose numerators the lane holds.
+// Staging item = (key pair, 4-wide d chunk): thread -> (d chunk low 2 bits, key pair, d chunk high bits), so a quad of lanes reads 64
+// contiguous bytes of a row and the 4-byte transposed V writes of a wave fall 2-way on the 32 banks. ----
+template <int D>
+__device__ __forceinline__ int fa_kswz(int key) {
+    if constexpr (D == 32) return (0x78 >> (2 * ((key >> 2) & 3))) & 3;      // 4 chunks per row, 4 rows per bank cycle (attention_bias.hip)
+    else if constexpr (D == 64) return (key >> 1) & 7;                        // 8 chunks per row, 2 rows per bank cycle
+    else return key & 15;                                                     // 16 chunks per row = one bank cycle
+}
+template <bool F16, typename V>
+__device__ __forceinline__ f32x4 fa_mfma(const V a, const V b, const f32x4 c) {
+    if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+    else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+template <typename E, int D>
+__global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const FlashAttentionParams p) {
+    constexpr bool F16 = std::is_same<E, _Float16>::value;
+    constexpr int NP = D / 32, ND = D / 16;       // staging passes = MFMA k steps of a score tile; d tiles of O^T
+    typedef fa_vec8<E> ex8;
+    typedef fa_vec4<E> ex4;
+    typedef fa_vec2<E> ex2;
+    __shared__ __attribute__((aligned(16))) E Kp[FA_T * D];
+    __shared__ __attribute__((aligned(16))) E Vt[D * FA_VT_LD];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int li = lane & 15, g = lane >> 4;
+    const FaBlock blk = fa_block(p);
+
+    const int query = blk.q0 + wave * 16 + li, qrow = min(query, p.seq_q - 1);
+    const int wave_row0 = min(blk.q0 + wave * 16, p.seq_q - 1);
+    const int limit = p.causal ? min(p.seq_kv, qrow + 1) : p.seq_kv;
+    // Q fragment of MFMA k step c: d = 32 c + 8 g .. + 7 of the query's row
+    ex8 qf[NP];
+    {
+        const float* qp = blk.q + qrow * p.q_ss + g * 8;
+#pragma unroll
+        for (int c = 0; c < NP; ++c) {
+            const f32x4 q0 = *reinterpret_cast<const f32x4*>(qp + c * 32), q1 = *reinterpret_cast<const f32x4*>(qp + c * 32 + 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { qf[c][e] = (E)q0[e]; qf[c][4 + e] = (E)q1[e]; }
+        }
+    }
+    // staging: keys (2 tp, 2 tp + 1) of the tile, d = c4 .. c4 + 3 with c4 = 16 (hi + 2 pass) + 4 lo
+    const int s_lo = tid & 3, s_tp = (tid >> 2) & 31, s_hi = tid >> 7;
+    f32x4 kr[NP][2], vr[NP][2];
+    auto load_tile = [&](int key0) {
+#pragma unroll
+        for (int ps = 0; ps < NP; ++ps) {
+            const int c4 = (s_hi + 2 * ps) * 16 + s_lo * 4;
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int t = key0 + s_tp * 2 + u;
+                const long src = min(t, p.seq_kv - 1) * p.kv_ss + c4;
+                kr[ps][u] = *reinterpret_cast<const f32x4*>(blk.k + src);
+                vr[ps][u] = *reinterpret_cast<const f32x4*>(blk.v + src);
+                if (t >= p.seq_kv) { kr[ps][u] = f32x4{0.f, 0.f, 0.f, 0.f}; vr[ps][u] = kr[ps][u]; }
+            }
+        }
+    };
+    f32x4 o[ND];
+#pragma unroll
+    for (int dt = 0; dt < ND; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float m = FA_NEG, l = 0.f;
+    const float sc2 = p.scale * FA_LOG2E;
+
+    load_tile(0);
+    for (int kt = 0; kt < blk.nkt; ++kt) {
+        __syncthreads();                                   // every wave is done reading the previous tile
+#pragma unroll
+        for (int ps = 0; ps < NP; ++ps) {
+            const int c4 = (s_hi + 2 * ps) * 16 + s_lo * 4;
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int t = s_tp * 2 + u;
+                ex4 h;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) h[e] = (E)kr[ps][u][e];
+                *reinterpret_cast<ex4*>(Kp + t * D + (((c4 >> 3) ^ fa_kswz<D>(t)) << 3) + (c4 & 4)) = h;
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                ex2 h;
+                h[0] = (E)vr[ps][0][e]; h[1] = (E)vr[ps][1][e];
+                *reinterpret_cast<ex2*>(Vt + (c4 + e) * FA_VT_LD + s_tp * 2) = h;      // keys (2tp, 2tp+1) of row d = c4 + e
+            }
+        }
+        __syncthreads();
+        if (kt + 1 < blk.nkt) load_tile((kt + 1) * FA_T);
+        // S^T = K . Q^T
+        f32x4 st[FA_T / 16];
+#pragma unroll
+        for (int s = 0; s < FA_T / 16; ++s) {
+            const int key = s * 16 + li;
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int c = 0; c < NP; ++c) {
+                const ex8 kf = *reinterpret_cast<const ex8*>(Kp + key * D + (((c * 4 + g) ^ fa_kswz<D>(key)) << 3));
+                acc = fa_mfma<F16>(kf, qf[c], acc);
+            }
+            st[s] = acc;
+        }
+        const float alpha = fa_softmax_tile(st, sc2, fa_tile_masks(p, kt * FA_T, wave_row0), kt * FA_T, g, limit, m, l);
+#pragma unroll
+        for (int dt = 0; dt < ND; ++dt) o[dt] *= alpha;
+        // O^T += V^T . P^T: k step t = key sub-tiles (2t, 2t+1)
+#pragma unroll
+        for (int t = 0; t < FA_T / 32; ++t) {
+            ex8 pf;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { pf[e] = (E)st[2 * t][e]; pf[4 + e] = (E)st[2 * t + 1][e]; }
+#pragma unroll
+            for (int dt = 0; dt < ND; ++dt) {
+                const E* vrow = Vt + (dt * 16 + li) * FA_VT_LD + t * 32 + g * 4;
+                const ex4 lo = *reinterpret_cast<const ex4*>(vrow), hi = *reinterpret_cast<const ex4*>(vrow + 16);
+                ex8 vf;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { vf[e] = lo[e]; vf[4 + e] = hi[e]; }
+                o[dt] = fa_mfma<F16>(vf, pf, o[dt]);
+            }
+        }
+    }
+    fa_store<ND>(query < p.seq_q ? blk.y + query * p.q_ss : nullptr, g, o, l);
+}
+
+template <int D>
+void fa_launch(const FlashAttentionParams& p, dim3 grid, hipStream_t s) {
+    const dim3 block(FA_THREADS);
+    if (p.s16 == 0) hipLaunchKernelGGL(flash_attention_f32_kernel<D>, grid, block, 0, s, p);
+    else if (p.s16 == 1) hipLaunchKernelGGL((flash_attention_s16_kernel<__bf16, D>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((flash_attention_s16_kernel<_Float16, D>), grid, block, 0, s, p);
+}
+
+}  // namespace
+
+hipError_t launch_flash_attention(const FlashAttentionParams& p, hipStream_t s) {
+    if (!(p.head_dim == 32 || p.head_dim == 64 || p.head_dim == 128) || p.seq_q < 1 || p.seq_kv < 1 || p.seq_q > 65536 || p.seq_kv > 65536 ||
+        p.batch < 1 || p.heads < 1 || (p.causal && p.seq_q != p.seq_kv) || p.s16 < 0 || p.s16 > 2 || !(p.scale > 0.f))
+        return hipErrorInvalidValue;
+    const long nwg = (long)p.batch * p.heads * ((p.seq_q + FA_BQ - 1) / FA_BQ);
+    if (nwg > 0x7fffffffL) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)nwg);
+    if (p.head_dim == 32) fa_launch<32>(p, grid, s);
+    else if (p.head_dim == 64) fa_launch<64>(p, grid, s);
+    else fa_launch<128>(p, grid, s);
+    return hipGetLastError();
+}
+
+}  // namespace brn

@@ -116,6 +116,35 @@ def attention_with_repeating_bias(q, k, v, scaled_bias, n_windows):
     return attention(q, k, v, scaled_bias, n_bias=int(n_windows))
 
 
+_ATTN_LAYOUT = {"bshd": _ffi.BRN_ATTN_BSHD, "bhsd": _ffi.BRN_ATTN_BHSD}
+
+
+def flash_attention(q, k, v, causal=False, scale=None, layout="bshd", device=0):
+    """flash_attention(&q, &k, &v, causal) (examples/bench_flash_attn.rs:39-53): y = softmax(scale * q k^T [causal: key j <= query i]) v per
+    (batch entry, head).  layout "bshd": q [batch, seq_q, heads, head_dim], k, v [batch, seq_kv, heads, head_dim] (flash_attention's own);
+    "bhsd": [batch, heads, seq, head_dim] (ops.attention's).  y has q's shape.  scale None = head_dim^-0.5.  The limits are the library's
+    (include/birefnet_hip.h brn_flash_attention_forward): nothing is checked here."""
+    lay = _ATTN_LAYOUT[layout]
+    if lay == _ffi.BRN_ATTN_BSHD:
+        batch, seq_q, heads, hd = (int(s) for s in q.shape)
+        seq_kv = int(k.shape[1])
+        kv_shape = (batch, seq_kv, heads, hd)
+    else:
+        batch, heads, seq_q, hd = (int(s) for s in q.shape)
+        seq_kv = int(k.shape[2])
+        kv_shape = (batch, heads, seq_kv, hd)
+    pq, loc, keep, _ = T.as_arg(q)
+    pk, kloc, kkeep, _ = T.as_arg(k, kv_shape)
+    pv, vloc, vkeep, _ = T.as_arg(v, kv_shape)
+    if not (kloc == vloc == loc):
+        raise ValueError("q, k and v must live on the same side")
+    y = T.alloc_like(keep, tuple(int(s) for s in q.shape))
+    _ffi.check(_ffi.lib.brn_flash_attention_forward(pq, pk, pv, batch, seq_q, seq_kv, heads, hd, lay, int(bool(causal)),
+                                                    float(scale) if scale is not None else 0.0, T.ptr_of(y), loc, T.device_of(keep, device),
+                                                    T.stream_of(keep)))
+    return y
+
+
 def patch_merging(x, H, W, norm_g, norm_b, reduction_w, device=0):
     """PatchMerging::forward (swin.rs:491-527): x [B,H*W,C] -> [B, ceil(H/2)*ceil(W/2), 2C]."""
     B, L, Cc = (int(v) for v in x.shape)

@@ -263,11 +263,40 @@ brn_status brn_window_attention_forward(const float* x, int B, int H, int W, int
  * even), q k^T and P v run on the 16-bit matrix instructions with fp32 accumulation, and the softmax numerators are rounded to the
  * 16-bit type for P v; the bias, the scores, the row maximum, the row sum (taken from the unrounded numerators) and y stay fp32.
  * Softmax subtracts the row maximum first; the result for a batch entry does not depend on `batch`.
- * Not provided: the causal flag of the MFA calls (the reference always passes false); long sequences and head_dim 64 / 128 (the LLM
- * shapes of examples/bench_flash_attn.rs:77-84); the [batch, seq, heads, head_dim] layout of the bias-free flash_attention. */
+ * Not provided HERE, provided by brn_flash_attention_forward below (without a bias): the causal flag of the MFA calls (the reference
+ * always passes false to these two); long sequences and head_dim 64 / 128 (the LLM shapes of examples/bench_flash_attn.rs:77-84); the
+ * [batch, seq, heads, head_dim] layout of the bias-free flash_attention. */
 brn_status brn_attention_forward(const float* q, const float* k, const float* v, int batch, int heads, int N, int head_dim,
                                  const float* bias, int n_bias, float scale,
                                  float* y, brn_mem loc, int device_ordinal, void* stream);
+/* candle_mps_flash_attention::flash_attention(&q, &k, &v, causal), the third call of the reference's flash-attn dependency
+ * (examples/bench_flash_attn.rs:39-53, sequences of 512 .. 8192, head_dim 64 / 128):
+ *   y[b,h] = softmax_rows( scale * q[b,h] k[b,h]^T  [causal mask] ) v[b,h]
+ * layout BRN_ATTN_BSHD: q, y [batch, seq_q, heads, head_dim] and k, v [batch, seq_kv, heads, head_dim] (flash_attention's layout);
+ * layout BRN_ATTN_BHSD: [batch, heads, seq, head_dim] (brn_attention_forward's layout; bench_flash_attn.rs:19-21 before its transposes).
+ * All four buffers are contiguous; one kernel serves both layouts through element strides.  scale 0 = 1/sqrt(head_dim).
+ * causal 1: key j takes part in query i's row exactly when j <= i.  A masked key is left out of the row maximum and of the row sum (a
+ * real exclusion, not an added -100); it requires seq_q == seq_kv.
+ * Limits (each violation is BRN_ERR_INVALID_ARG with a message naming the limit, checked before the device): head_dim 32, 64 or 128;
+ * 1 <= seq_q, seq_kv <= 65536; batch >= 1, heads >= 1; batch * heads * ceil(seq_q / 16) < 2^31; layout 0 or 1; causal 0 or 1; causal
+ * requires seq_q == seq_kv; scale finite and >= 0; q, k, v, y not NULL; y overlaps no input; BRN_MEM_DEVICE q, k, v, y 16-byte aligned.
+ * All four buffers live where `loc` says; the stream and synchronisation conventions at the top of this header apply.
+ * The softmax is computed online: K and V are walked in tiles of 64 keys with a running row maximum, a running row sum and the output
+ * accumulators in registers, rescaled whenever a tile raises the maximum; the [seq_q, seq_kv] score matrix never exists in memory.
+ * Nothing is split over keys between workgroups and there are no atomics: an output row depends only on its own (batch entry, head),
+ * its bits depend neither on `batch` nor on the launch grid, and a repeated call repeats its bits.
+ * Arithmetic follows brn_set_op_compute on the calling thread, by the rule of brn_attention_forward.  BRN_BF16 / BRN_F16: q, k, v are
+ * rounded to the 16-bit type at the edge (round to nearest even), q k^T and P v run on the 16-bit matrix instructions
+ * (v_mfma_f32_16x16x32_{bf16,f16}) with fp32 accumulation, and the softmax numerators are rounded to the 16-bit type for P v; the
+ * scores, the running maximum, the running sum (taken from the unrounded numerators) and y stay fp32.  Every other mode runs ONE exact
+ * fp32 kernel (v_mfma_f32_16x16x4_f32): bit-identical results across BRN_F32, BRN_F32_SPLIT3, BRN_F32_SPLIT2 and BRN_F32_HALF2.
+ * Not provided: a bias together with long sequences (brn_attention_forward has the bias, up to N = 144); a causal mask with
+ * seq_q != seq_kv; head dims other than 32 / 64 / 128. */
+typedef enum { BRN_ATTN_BSHD = 0, BRN_ATTN_BHSD = 1 } brn_attn_layout;
+brn_status brn_flash_attention_forward(const float* q, const float* k, const float* v,
+                                       int batch, int seq_q, int seq_kv, int heads, int head_dim,
+                                       int layout, int causal, float scale,
+                                       float* y, brn_mem loc, int device_ordinal, void* stream);
 /* PatchMerging::forward (swin.rs:491-527): x [B,H*W,C] -> [B, ceil(H/2)*ceil(W/2), 2C]. */
 brn_status brn_patch_merging_forward(const float* x, int B, int H, int W, int C, const float* norm_g,
                                      const float* norm_b, const float* reduction_w, float* y, brn_mem loc,
