@@ -64,6 +64,22 @@ struct Staging {
     }
 };
 
+// argument checks the q/k/v attention entries share (brn_ops.cpp); each entry words its own message
+// whether the na floats at a (null: none) and the ny floats at y share a byte
+inline bool floats_overlap(const float* a, size_t na, const float* y, size_t ny) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), y0 = reinterpret_cast<uintptr_t>(y);
+    return a && a0 < y0 + ny * sizeof(float) && y0 < a0 + na * sizeof(float);
+}
+// device buffers are read and written with 16-byte accesses (host buffers are staged into allocations of the library's own)
+inline bool all_aligned16(std::initializer_list<const void*> ptrs) {
+    for (const void* p : ptrs)
+        if (reinterpret_cast<uintptr_t>(p) & 15) return false;
+    return true;
+}
+// a softmax scale argument is finite and >= 0; 0 selects head_dim^-0.5
+inline bool scale_arg_ok(float scale) { return scale >= 0.f && std::isfinite(scale); }
+inline float scale_or_default(float scale, int head_dim) { return scale > 0.f ? scale : 1.0f / sqrtf((float)head_dim); }
+
 // run a graph fragment with a private arena: plan (dry), allocate, run
 inline void with_arena(hipStream_t s, const std::function<void(Ctx&)>& fn, int bf16 = 0) {   // bf16: 0 fp32 maps, 1 bf16, 2 fp16 (Ctx::bf16)
     Arena a;

@@ -15,6 +15,9 @@ namespace {
 // brn_set_op_compute: thread-local by contract of the ABI (default BRN_F32).  Every entry reads it once and passes it down.
 thread_local WeightBuild g_op;
 inline int op_s16(WeightBuild wb, bool on = true) { return on && wb.planes == BUILD_BF16 ? (wb.f16 ? 2 : 1) : 0; }   // Ctx::bf16 of the entry's maps
+// the q/k/v attention entries: in modes bf16 / f16 q, k, v are rounded to the 16-bit type as the kernel loads them; every other mode runs
+// the exact fp32-MFMA kernel between its own GEMMs (as window-7 attention does)
+inline int attention_op_s16() { return op_s16(g_op); }
 
 // compute modes BRN_BF16 / BRN_F16 at op level: x is rounded to the 16-bit storage type at the edge, as the producing kernel of the
 // model would have written it; what the entry returns stays fp32 at this boundary
@@ -246,14 +249,11 @@ brn_status brn_attention_forward(const float* q, const float* k, const float* v,
         if (n_bias < 0) fail(BRN_ERR_INVALID_ARG, "attention: n_bias %d is negative (n_bias >= 0)", n_bias);
         if ((bias == nullptr) != (n_bias == 0)) fail(BRN_ERR_INVALID_ARG, "attention: bias must be NULL exactly when n_bias == 0 (n_bias %d)", n_bias);
         if (n_bias > 0 && batch % n_bias) fail(BRN_ERR_INVALID_ARG, "attention: batch %d is not a multiple of n_bias %d (batch %% n_bias == 0)", batch, n_bias);
-        if (!(scale >= 0.f) || !std::isfinite(scale)) fail(BRN_ERR_INVALID_ARG, "attention: scale must be finite and >= 0 (0 = head_dim^-0.5)");
+        if (!scale_arg_ok(scale)) fail(BRN_ERR_INVALID_ARG, "attention: scale must be finite and >= 0 (0 = head_dim^-0.5)");
         const size_t n = (size_t)batch * heads * N * head_dim, nb = (size_t)n_bias * heads * N * N;
-        const uintptr_t y0 = reinterpret_cast<uintptr_t>(y), y1 = y0 + n * sizeof(float);
-        auto overlaps = [&](const float* a, size_t na) { const uintptr_t a0 = reinterpret_cast<uintptr_t>(a); return a && a0 < y1 && y0 < a0 + na * sizeof(float); };
-        if (overlaps(q, n) || overlaps(k, n) || overlaps(v, n) || overlaps(bias, nb)) fail(BRN_ERR_INVALID_ARG, "attention: y must not alias an input");
-        if (loc == BRN_MEM_DEVICE)              // (host buffers are staged into allocations of the library's own)
-            for (const float* a : {q, k, v, (const float*)y})
-                if (reinterpret_cast<uintptr_t>(a) & 15) fail(BRN_ERR_INVALID_ARG, "attention: device q, k, v and y must be 16-byte aligned");
+        if (floats_overlap(q, n, y, n) || floats_overlap(k, n, y, n) || floats_overlap(v, n, y, n) || floats_overlap(bias, nb, y, n))
+            fail(BRN_ERR_INVALID_ARG, "attention: y must not alias an input");
+        if (loc == BRN_MEM_DEVICE && !all_aligned16({q, k, v, y})) fail(BRN_ERR_INVALID_ARG, "attention: device q, k, v and y must be 16-byte aligned");
         ensure_device(device);
         Staging st(stream, loc);
         AttentionBiasParams p{};
@@ -261,10 +261,8 @@ brn_status brn_attention_forward(const float* q, const float* k, const float* v,
         p.bias = bias ? st.in(bias, nb) : nullptr;
         p.y = st.out(y, n);
         p.batch = batch; p.heads = heads; p.N = N; p.n_bias = n_bias;
-        p.scale = scale > 0.f ? scale : 1.0f / sqrtf((float)head_dim);
-        // modes bf16 / f16: q, k, v are rounded to the 16-bit type as the kernel loads them; every other mode runs the exact fp32-MFMA
-        // kernel between its own GEMMs (as window-7 attention does)
-        p.s16 = op_s16(g_op);
+        p.scale = scale_or_default(scale, head_dim);
+        p.s16 = attention_op_s16();
         BRN_HIP(launch_attention_bias(p, (hipStream_t)stream));
         st.finish();
     });
@@ -284,14 +282,11 @@ brn_status brn_flash_attention_forward(const float* q, const float* k, const flo
         if (layout != BRN_ATTN_BSHD && layout != BRN_ATTN_BHSD) fail(BRN_ERR_INVALID_ARG, "flash attention: layout %d unknown (layout must be 0 = BSHD or 1 = BHSD)", layout);
         if (causal != 0 && causal != 1) fail(BRN_ERR_INVALID_ARG, "flash attention: causal %d (causal must be 0 or 1)", causal);
         if (causal && seq_q != seq_kv) fail(BRN_ERR_INVALID_ARG, "flash attention: causal requires seq_q == seq_kv (seq_q %d, seq_kv %d)", seq_q, seq_kv);
-        if (!(scale >= 0.f) || !std::isfinite(scale)) fail(BRN_ERR_INVALID_ARG, "flash attention: scale must be finite and >= 0 (0 = head_dim^-0.5)");
+        if (!scale_arg_ok(scale)) fail(BRN_ERR_INVALID_ARG, "flash attention: scale must be finite and >= 0 (0 = head_dim^-0.5)");
         const size_t nq = (size_t)batch * heads * seq_q * head_dim, nkv = (size_t)batch * heads * seq_kv * head_dim;
-        const uintptr_t y0 = reinterpret_cast<uintptr_t>(y), y1 = y0 + nq * sizeof(float);
-        auto overlaps = [&](const float* a, size_t na) { const uintptr_t a0 = reinterpret_cast<uintptr_t>(a); return a0 < y1 && y0 < a0 + na * sizeof(float); };
-        if (overlaps(q, nq) || overlaps(k, nkv) || overlaps(v, nkv)) fail(BRN_ERR_INVALID_ARG, "flash attention: y must not overlap an input");
-        if (loc == BRN_MEM_DEVICE)              // (host buffers are staged into allocations of the library's own)
-            for (const float* a : {q, k, v, (const float*)y})
-                if (reinterpret_cast<uintptr_t>(a) & 15) fail(BRN_ERR_INVALID_ARG, "flash attention: device q, k, v and y must be 16-byte aligned");
+        if (floats_overlap(q, nq, y, nq) || floats_overlap(k, nkv, y, nq) || floats_overlap(v, nkv, y, nq))
+            fail(BRN_ERR_INVALID_ARG, "flash attention: y must not overlap an input");
+        if (loc == BRN_MEM_DEVICE && !all_aligned16({q, k, v, y})) fail(BRN_ERR_INVALID_ARG, "flash attention: device q, k, v and y must be 16-byte aligned");
         ensure_device(device);
         Staging st(stream, loc);
         FlashAttentionParams p{};
@@ -308,9 +303,8 @@ brn_status brn_flash_attention_forward(const float* q, const float* k, const flo
             p.kv_ss = d; p.kv_sh = seq_kv * d; p.kv_sb = heads * p.kv_sh;
         }
         p.causal = causal;
-        p.scale = scale > 0.f ? scale : 1.0f / sqrtf((float)head_dim);
-        // modes bf16 / f16: q, k, v are rounded to the 16-bit type as the kernel loads them; every other mode runs the exact fp32-MFMA kernel
-        p.s16 = op_s16(g_op);
+        p.scale = scale_or_default(scale, head_dim);
+        p.s16 = attention_op_s16();
         BRN_HIP(launch_flash_attention(p, (hipStream_t)stream));
         st.finish();
     });

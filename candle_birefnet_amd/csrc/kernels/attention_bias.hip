@@ -2,22 +2,19 @@
 //   y[b,h] = softmax_rows( scale * (q[b,h] k[b,h]^T + bias[b % n_bias, h]) ) v[b,h]
 // the op candle's WindowAttention::forward hands to flash_attention_with_bias / flash_attention_with_repeating_bias (swin.rs:243, 252).
 // It is the sibling of kernels/window_attention.hip for callers that bring their own q, k, v and bias: no window geometry, no
-// relative-position table, no mask logic — the bias is a tensor that is read.  The file is self-contained (its helpers restate the few
-// lines it shares with window_attention.hip, in an unnamed namespace), so nothing in the window kernels moves.
+// relative-position table, no mask logic — the bias is a tensor that is read.
 //
 // One workgroup = one (batch entry, head); one wave = one 16-query tile, so a workgroup has ceil(N / 16) waves (1 .. 9).
-// MFMA formulation as in window_attention.hip (all tiles 16x16; C/D map: col = lane & 15, row = 4 (lane >> 4) + reg):
+// MFMA formulation, tile map and LDS images: kernels/attention_mfma.h.  What is particular here:
 //   S^T[key][query] = bias^T + K . Q^T   the accumulator is LOADED from the bias tile (C operand): the bias is added before the scale, so
 //                                        it costs no vector add; a lane's 4 registers are 4 consecutive keys of its query's bias row
-//   softmax over keys                    in-lane over the tile registers, then across the 4 lane groups (shfl_xor 16, 32); exp2 with
-//                                        scale * log2(e) folded into one multiply; the row maximum is subtracted first
-//   O^T[d][query] = V^T . P^T            B = P^T straight from the S^T accumulator registers, A = V^T from LDS
+//   softmax over keys                    exp2 with scale * log2(e) folded into one multiply; the row maximum is subtracted first
 // Ragged N: N is rounded up to nt = ceil(N / 16) tiles inside the kernel.  K / V rows past N are ZEROS in LDS (never read from memory),
 // their scores are forced to -3e38 after the scale so that they leave the row maximum and the row sum, a pad query computes on the
 // last real row and is never stored, and every global address is clamped to the (batch entry, head) it belongs to.
 // Nothing is shared between workgroups and there are no atomics: the result for a batch entry does not depend on `batch`.
 #include "../brn_kernels.h"
-#include "split_planes.h"
+#include "attention_mfma.h"
 #include <type_traits>
 
 namespace brn {
@@ -28,12 +25,6 @@ constexpr int AB_NMAX = 144;         // longest sequence: 9 tiles of 16
 constexpr int AB_NT = 9;
 constexpr int AB_KV_LD = 36;         // fp32 kernel: floats per LDS row of K and V
 constexpr int AB_VT_LD = 148;        // 16-bit kernel: elements per LDS row of V^T
-constexpr float AB_LOG2E = 1.4426950408889634f;
-constexpr float AB_NEG = -3.0e38f;
-
-template <typename E> using ab_vec8 = E __attribute__((ext_vector_type(8)));
-template <typename E> using ab_vec4 = E __attribute__((ext_vector_type(4)));
-template <typename E> using ab_vec2 = E __attribute__((ext_vector_type(2)));
 
 // which (batch entry, head) this workgroup owns and where its operands start
 struct AbBlock {
@@ -70,44 +61,35 @@ __device__ __forceinline__ void ab_load_bias(const float* bias, int qrow, int g,
 }
 // scores -> un-normalised probabilities in place (exp2 units), returns the row sum.  Lane group g holds keys 16 kt + 4 g + r.
 __device__ __forceinline__ float ab_softmax(f32x4 (&st)[AB_NT], int g, int N, int nt, float scale) {
-    const float sc2 = scale * AB_LOG2E;
+    const float sc2 = scale * ATT_LOG2E;
     const int nlast = N - (nt - 1) * 16;            // real keys of the last tile: 1 .. 16
-    float mx = AB_NEG;
+    float mx = ATT_NEG;
 #pragma unroll
     for (int kt = 0; kt < AB_NT; ++kt) {
         if (kt < nt) {
+            att_scale4(st[kt], sc2);
+            // pad keys leave the softmax (att_exclude4(st[kt], g * 4, nlast), spelled out: through the helper the whole row loop compiled
+            // to other code, with up to 6 VGPRs more)
+            if (kt == nt - 1) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) st[kt][r] *= sc2;
-            if (kt == nt - 1) {                     // pad keys leave the softmax
-#pragma unroll
-                for (int r = 0; r < 4; ++r) st[kt][r] = (g * 4 + r < nlast) ? st[kt][r] : AB_NEG;
+                for (int r = 0; r < 4; ++r) st[kt][r] = (g * 4 + r < nlast) ? st[kt][r] : ATT_NEG;
             }
-            mx = fmaxf(fmaxf(mx, fmaxf(st[kt][0], st[kt][1])), fmaxf(st[kt][2], st[kt][3]));
+            mx = att_max4(mx, st[kt]);
         }
     }
-    mx = fmaxf(mx, __shfl_xor(mx, 16));
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    mx = att_group_max(mx);
     float sum = 0.f;
 #pragma unroll
     for (int kt = 0; kt < AB_NT; ++kt) {
-        if (kt < nt) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float e = __builtin_amdgcn_exp2f(st[kt][r] - mx);
-                st[kt][r] = e;
-                sum += e;
-            }
-        }
+        if (kt < nt) att_exp2_sum4(st[kt], mx, sum);
     }
-    sum += __shfl_xor(sum, 16);
-    sum += __shfl_xor(sum, 32);
-    return sum;
+    return att_group_sum(sum);
 }
-// lane holds O^T[d = 16 dt + 4 g + r][query]: two 16-byte stores into the query's row of y
+// the two d tiles of a query's row of y
 __device__ __forceinline__ void ab_store(float* y, int query, int g, const f32x4 o0, const f32x4 o1, const float inv) {
-    float* op = y + (long)query * AB_HD + g * 4;
-    *reinterpret_cast<f32x4*>(op) = o0 * inv;
-    *reinterpret_cast<f32x4*>(op + 16) = o1 * inv;
+    float* yg = y + (long)query * AB_HD + g * 4;
+    att_store_o(yg, 0, o0, inv);
+    att_store_o(yg, 1, o1, inv);
 }
 
 // ---- fp32: v_mfma_f32_16x16x4_f32, an exact fmaf chain per score and per output ----
@@ -143,17 +125,7 @@ __global__ void __launch_bounds__(AB_NT * 64) attention_bias_f32_kernel(const At
     // S^T = bias^T + K . Q^T
 #pragma unroll
     for (int kt = 0; kt < AB_NT; ++kt) {
-        if (kt < nt) {
-            const float* kp = Ks + (kt * 16 + li) * AB_KV_LD + g * 8;
-            const f32x4 k0 = *reinterpret_cast<const f32x4*>(kp);
-            const f32x4 k1 = *reinterpret_cast<const f32x4*>(kp + 4);
-            f32x4 acc = st[kt];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(k0[e], q0[e], acc, 0, 0, 0);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(k1[e], q1[e], acc, 0, 0, 0);
-            st[kt] = acc;
-        }
+        if (kt < nt) st[kt] = att_score_f32(Ks + (kt * 16 + li) * AB_KV_LD + g * 8, q0, q1, st[kt]);
         if (kt % 3 == 2) __builtin_amdgcn_sched_barrier(0);   // bound the scheduler's hoisting (register pressure)
     }
     const float sum = ab_softmax(st, g, N, nt, p.scale);
@@ -165,8 +137,8 @@ __global__ void __launch_bounds__(AB_NT * 64) attention_bias_f32_kernel(const At
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float* vp = Vs + (kt * 16 + g * 4 + r) * AB_KV_LD + li;
-                o0 = __builtin_amdgcn_mfma_f32_16x16x4f32(vp[0], st[kt][r], o0, 0, 0, 0);
-                o1 = __builtin_amdgcn_mfma_f32_16x16x4f32(vp[16], st[kt][r], o1, 0, 0, 0);
+                o0 = att_pv_f32(vp, 0, st[kt][r], o0);
+                o1 = att_pv_f32(vp, 1, st[kt][r], o1);
             }
         }
         if (kt % 2 == 1) __builtin_amdgcn_sched_barrier(0);
@@ -176,22 +148,13 @@ __global__ void __launch_bounds__(AB_NT * 64) attention_bias_f32_kernel(const At
 
 // ---- 16-bit: q, k, v rounded to E (round to nearest even) as they are loaded; v_mfma_f32_16x16x32_{bf16,f16} with fp32 accumulation.
 // The bias, the scores, the row maximum and the row sum (of the UNROUNDED probabilities) are fp32; the probabilities are rounded to E for
-// P . V.  LDS: Kp[key][32 d] (64-byte rows, 16-byte chunk c stored at c ^ kswz(key): conflict-free ds_read_b128 of the A operand) and
-// Vt[d][148 keys] (V transposed: the A operand of O^T = V^T P^T is 8 keys of one d) = 18.2 KB.  An MFMA of P . V contracts key tiles
-// (2t, 2t+1): lane group g's k slots are keys 16 (2t) + 4g + 0..3 and 16 (2t+1) + 4g + 0..3 — the keys whose probabilities the lane
-// already holds.  Both images are zero-filled up to the even tile count, so a tile past nt contributes 0 x 0. ----
-__device__ __forceinline__ int ab_kswz(int key) { return (0x78 >> (2 * ((key >> 2) & 3))) & 3; }
-template <bool F16, typename V>
-__device__ __forceinline__ f32x4 ab_mfma(const V a, const V b, const f32x4 c) {
-    if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
+// P . V.  LDS: Kp[key][32 d] and Vt[d][148 keys] (kernels/attention_mfma.h) = 18.2 KB.  Both images are zero-filled up to the even tile
+// count, so a tile past nt contributes 0 x 0. ----
 template <typename E, bool BVEC>
 __global__ void __launch_bounds__(AB_NT * 64) attention_bias_s16_kernel(const AttentionBiasParams p) {
     constexpr bool F16 = std::is_same<E, _Float16>::value;
-    typedef ab_vec8<E> ex8;
-    typedef ab_vec4<E> ex4;
-    typedef ab_vec2<E> ex2;
+    typedef vec8<E> ex8;
+    typedef vec4<E> ex4;
     __shared__ __attribute__((aligned(16))) E Kp[AB_NMAX * AB_HD];
     __shared__ __attribute__((aligned(16))) E Vt[AB_HD * AB_VT_LD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nthr = blockDim.x;
@@ -224,28 +187,21 @@ __global__ void __launch_bounds__(AB_NT * 64) attention_bias_s16_kernel(const At
             ex4 h;
 #pragma unroll
             for (int e = 0; e < 4; ++e) h[e] = (E)kv[u][e];
-            *reinterpret_cast<ex4*>(Kp + t * AB_HD + (((c4 >> 3) ^ ab_kswz(t)) << 3) + (c4 & 4)) = h;
+            *reinterpret_cast<ex4*>(att_k_chunk<AB_HD>(Kp + t * AB_HD, t, c4 >> 3) + (c4 & 4)) = h;
         }
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            ex2 h;
-            h[0] = (E)vv[0][e]; h[1] = (E)vv[1][e];
-            *reinterpret_cast<ex2*>(Vt + (c4 + e) * AB_VT_LD + tp * 2) = h;      // keys (2tp, 2tp+1) of row d = c4 + e
-        }
+        for (int e = 0; e < 4; ++e) att_vt_store(Vt + (c4 + e) * AB_VT_LD, tp, (E)vv[0][e], (E)vv[1][e]);
     }
     __syncthreads();
     if (wave >= nt) return;
 
-    ex8 qf;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { qf[e] = (E)q0[e]; qf[4 + e] = (E)q1[e]; }
+    const ex8 qf = att_round8<E>(q0, q1);
     // S^T = bias^T + K . Q^T: head_dim 32 is ONE MFMA k
 #pragma unroll
     for (int kt = 0; kt < AB_NT; ++kt) {
         if (kt < nt) {
             const int key = kt * 16 + li;
-            const ex8 kf = *reinterpret_cast<const ex8*>(Kp + key * AB_HD + ((g ^ ab_kswz(key)) << 3));
-            st[kt] = ab_mfma<F16>(kf, qf, st[kt]);
+            st[kt] = att_mfma<F16>(att_k_frag<AB_HD>(Kp + key * AB_HD, key, g), qf, st[kt]);
         }
     }
     const float sum = ab_softmax(st, g, N, nt, p.scale);
@@ -256,6 +212,7 @@ __global__ void __launch_bounds__(AB_NT * 64) attention_bias_s16_kernel(const At
         if (2 * t < nt) {
             const bool hi_tile = 2 * t + 1 < AB_NT;                  // compile-time per t after unrolling
             const bool hi_real = 2 * t + 1 < nt;
+            // (att_p_step and att_round8 with a run-time tile count, spelled out: through a helper the tile tests compile to other scalar code)
             ex8 pf;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -264,15 +221,9 @@ __global__ void __launch_bounds__(AB_NT * 64) attention_bias_s16_kernel(const At
             }
 #pragma unroll
             for (int dt = 0; dt < 2; ++dt) {
-                const E* vrow = Vt + (dt * 16 + li) * AB_VT_LD + g * 4;
-                const ex4 lo = *reinterpret_cast<const ex4*>(vrow + (2 * t) * 16);
-                ex4 hi = {(E)0.f, (E)0.f, (E)0.f, (E)0.f};
-                if (hi_tile) hi = *reinterpret_cast<const ex4*>(vrow + (hi_tile ? 2 * t + 1 : 0) * 16);
-                ex8 vf;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { vf[e] = lo[e]; vf[4 + e] = hi[e]; }
-                if (dt == 0) o0 = ab_mfma<F16>(vf, pf, o0);
-                else o1 = ab_mfma<F16>(vf, pf, o1);
+                const ex8 vf = att_vt_frag(Vt + (dt * 16 + li) * AB_VT_LD + g * 4, t, hi_tile);
+                if (dt == 0) o0 = att_mfma<F16>(vf, pf, o0);
+                else o1 = att_mfma<F16>(vf, pf, o1);
             }
         }
     }

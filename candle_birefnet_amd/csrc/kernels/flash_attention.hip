@@ -4,19 +4,18 @@
 // 32 / 64 / 128, 1 <= seq <= 65536, q and k/v of different lengths, in either the [batch, seq, heads, head_dim] or the
 // [batch, heads, seq, head_dim] layout: the kernels take element strides (batch entry, head, sequence position; head_dim contiguous).
 // It is the sibling of kernels/attention_bias.hip, which holds a whole score row of <= 144 keys in registers; here the row never exists.
-// The file is self-contained (unnamed namespace), so nothing in the other attention kernels moves.
 //
 // One workgroup = one (batch entry, head, tile of FA_BQ = 64 queries) = 4 waves; one wave = 16 queries.  K and V are walked in tiles of
 // FA_T = 64 keys staged in LDS (single-buffered; the NEXT tile's global loads are issued into registers before the current tile is
-// computed, so they fly under the MFMAs and are written to LDS after the barrier that ends the tile).  Per wave and tile, MFMA
-// formulation as in attention_bias.hip (all tiles 16x16; C/D map: col = lane & 15, row = 4 (lane >> 4) + reg):
-//   S^T[key][query] = K . Q^T            4 key sub-tiles of 16; a lane's 4 registers of a sub-tile are 4 consecutive keys of ITS query
+// computed, so they fly under the MFMAs and are written to LDS after the barrier that ends the tile).  Per wave and tile, the MFMA
+// formulation, tile map and LDS images of kernels/attention_mfma.h:
+//   S^T[key][query] = K . Q^T            4 key sub-tiles of 16
 //   online softmax                       scores * (scale * log2 e); excluded keys -> -3e38; tile maximum in-lane then across the 4 lane
 //                                        groups (shfl_xor 16, 32); m_new = max(m, tile max); alpha = exp2(m - m_new) rescales the
 //                                        running sum l and the O accumulators; numerators exp2(s - m_new); l += the lane's UNROUNDED
 //                                        numerators (a lane's l is a partial sum over its keys: alpha is the same in the 4 lanes of
 //                                        a query, so the 4 partials are added once, after the last tile)
-//   O^T[d][query] += V^T . P^T           B = P^T straight from the S^T accumulator registers, A = V^T from LDS
+//   O^T[d][query] += V^T . P^T
 // m, l and O^T (head_dim / 16 accumulators of 4 registers) live in registers for the whole walk.  There is no split over keys between
 // workgroups, no atomics, nothing shared between workgroups: an output row depends only on its own (batch entry, head), and the bits
 // depend neither on `batch` nor on the grid.  Every loop bound is a function of the arguments.
@@ -27,7 +26,7 @@
 // (-3e38) - (-3e38) with a non-zero l behind it, and exp2(excluded - m) is exactly 0 — an excluded key is in neither the maximum nor
 // the sum.
 #include "../brn_kernels.h"
-#include "split_planes.h"
+#include "attention_mfma.h"
 #include <type_traits>
 
 namespace brn {
@@ -37,12 +36,6 @@ constexpr int FA_BQ = 64;            // queries per workgroup: 4 waves x 16
 constexpr int FA_T = 64;             // keys per K / V tile
 constexpr int FA_THREADS = 256;
 constexpr int FA_VT_LD = 72;         // 16-bit kernel: elements per LDS row of V^T (36 dwords: conflict-free 8-byte reads, 2-way 4-byte writes)
-constexpr float FA_LOG2E = 1.4426950408889634f;
-constexpr float FA_NEG = -3.0e38f;
-
-template <typename E> using fa_vec8 = E __attribute__((ext_vector_type(8)));
-template <typename E> using fa_vec4 = E __attribute__((ext_vector_type(4)));
-template <typename E> using fa_vec2 = E __attribute__((ext_vector_type(2)));
 
 // which (batch entry, head, query tile) this workgroup owns, where its operands start and how many K / V tiles it walks
 struct FaBlock {
@@ -77,31 +70,18 @@ __device__ __forceinline__ FaBlock fa_block(const FlashAttentionParams& p) {
 // limit: the lane's first excluded key (seq_kv, or query + 1 under the causal mask); mask: whether this tile can hold an excluded key
 // for some lane of the wave (wave-uniform).  Leaves the numerators in st, updates m and l, returns alpha.
 __device__ __forceinline__ float fa_softmax_tile(f32x4 (&st)[FA_T / 16], float sc2, bool mask, int key0, int g, int limit, float& m, float& l) {
-    float mx = FA_NEG;
+    float mx = ATT_NEG;
 #pragma unroll
     for (int s = 0; s < FA_T / 16; ++s) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) st[s][r] *= sc2;
-        if (mask) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) st[s][r] = (key0 + s * 16 + g * 4 + r < limit) ? st[s][r] : FA_NEG;
-        }
-        mx = fmaxf(fmaxf(mx, fmaxf(st[s][0], st[s][1])), fmaxf(st[s][2], st[s][3]));
+        att_scale4(st[s], sc2);
+        if (mask) att_exclude4(st[s], key0 + s * 16 + g * 4, limit);
+        mx = att_max4(mx, st[s]);
     }
-    mx = fmaxf(mx, __shfl_xor(mx, 16));
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-    const float mn = fmaxf(m, mx);
+    const float mn = fmaxf(m, att_group_max(mx));
     const float alpha = __builtin_amdgcn_exp2f(m - mn);
     float sum = 0.f;
 #pragma unroll
-    for (int s = 0; s < FA_T / 16; ++s) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float e = __builtin_amdgcn_exp2f(st[s][r] - mn);
-            st[s][r] = e;
-            sum += e;
-        }
-    }
+    for (int s = 0; s < FA_T / 16; ++s) att_exp2_sum4(st[s], mn, sum);
     m = mn;
     l = l * alpha + sum;
     return alpha;
@@ -111,15 +91,13 @@ __device__ __forceinline__ bool fa_tile_masks(const FlashAttentionParams& p, int
     const int lim = p.causal ? min(p.seq_kv, wave_row0 + 1) : p.seq_kv;
     return key0 + FA_T > lim;
 }
-// lane holds O^T[d = 16 dt + 4 g + r][query]: one 16-byte store per d tile into the query's row of y
+// the 4 partial sums of a query are added, and the query's row of y (null: a pad query) is stored
 template <int ND>
-__device__ __forceinline__ void fa_store(float* yrow, int g, const f32x4 (&o)[ND], float l) {
-    l += __shfl_xor(l, 16);
-    l += __shfl_xor(l, 32);
-    const float inv = 1.0f / l;
+__device__ __forceinline__ void fa_finish(float* yrow, int g, const f32x4 (&o)[ND], float l) {
+    const float inv = 1.0f / att_group_sum(l);
     if (yrow) {
 #pragma unroll
-        for (int dt = 0; dt < ND; ++dt) *reinterpret_cast<f32x4*>(yrow + dt * 16 + g * 4) = o[dt] * inv;
+        for (int dt = 0; dt < ND; ++dt) att_store_o(yrow + g * 4, dt, o[dt], inv);
     }
 }
 
@@ -161,8 +139,8 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
     f32x4 o[ND];
 #pragma unroll
     for (int dt = 0; dt < ND; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float m = FA_NEG, l = 0.f;
-    const float sc2 = p.scale * FA_LOG2E;
+    float m = ATT_NEG, l = 0.f;
+    const float sc2 = p.scale * ATT_LOG2E;
 
     load_tile(0);
     for (int kt = 0; kt < blk.nkt; ++kt) {
@@ -181,15 +159,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
         for (int s = 0; s < FA_T / 16; ++s) {
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                const float* kp = Ks + (s * 16 + li) * LD + c * 32 + g * 8;
-                const f32x4 k0 = *reinterpret_cast<const f32x4*>(kp);
-                const f32x4 k1 = *reinterpret_cast<const f32x4*>(kp + 4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(k0[e], qv[2 * c][e], acc, 0, 0, 0);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(k1[e], qv[2 * c + 1][e], acc, 0, 0, 0);
-            }
+            for (int c = 0; c < NC; ++c) acc = att_score_f32(Ks + (s * 16 + li) * LD + c * 32 + g * 8, qv[2 * c], qv[2 * c + 1], acc);
             st[s] = acc;
         }
         const float alpha = fa_softmax_tile(st, sc2, fa_tile_masks(p, kt * FA_T, wave_row0), kt * FA_T, g, limit, m, l);
@@ -202,38 +172,24 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
             for (int r = 0; r < 4; ++r) {
                 const float* vp = Vs + (s * 16 + g * 4 + r) * LD + li;
 #pragma unroll
-                for (int dt = 0; dt < ND; ++dt) o[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(vp[dt * 16], st[s][r], o[dt], 0, 0, 0);
+                for (int dt = 0; dt < ND; ++dt) o[dt] = att_pv_f32(vp, dt, st[s][r], o[dt]);
             }
         }
     }
-    fa_store<ND>(query < p.seq_q ? blk.y + query * p.q_ss : nullptr, g, o, l);
+    fa_finish<ND>(query < p.seq_q ? blk.y + query * p.q_ss : nullptr, g, o, l);
 }
 
 // ---- 16-bit: q, k, v rounded to E (round to nearest even) as they are loaded; v_mfma_f32_16x16x32_{bf16,f16} with fp32 accumulation.
 // Scores, m, l (of the UNROUNDED numerators) and O are fp32; the numerators are rounded to E for P . V.
-// LDS: Kp[key][D] (16-byte chunk c of a row stored at c ^ fa_kswz(key): conflict-free ds_read_b128 of the A operand) and Vt[d][72 keys]
-// (V transposed: the A operand of O^T = V^T P^T is 8 keys of one d): D 128 = 16 + 18 KB.  An MFMA of P . V contracts sub-tiles
-// (2t, 2t+1): lane group g's k slots are keys 16 (2t) + 4g + 0..3 and 16 (2t+1) + 4g + 0..3 — the keys whose numerators the lane holds.
+// LDS: Kp[key][D] and Vt[d][72 keys] (kernels/attention_mfma.h): D 128 = 16 + 18 KB.
 // Staging item = (key pair, 4-wide d chunk): thread -> (d chunk low 2 bits, key pair, d chunk high bits), so a quad of lanes reads 64
 // contiguous bytes of a row and the 4-byte transposed V writes of a wave fall 2-way on the 32 banks. ----
-template <int D>
-__device__ __forceinline__ int fa_kswz(int key) {
-    if constexpr (D == 32) return (0x78 >> (2 * ((key >> 2) & 3))) & 3;      // 4 chunks per row, 4 rows per bank cycle (attention_bias.hip)
-    else if constexpr (D == 64) return (key >> 1) & 7;                        // 8 chunks per row, 2 rows per bank cycle
-    else return key & 15;                                                     // 16 chunks per row = one bank cycle
-}
-template <bool F16, typename V>
-__device__ __forceinline__ f32x4 fa_mfma(const V a, const V b, const f32x4 c) {
-    if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 template <typename E, int D>
 __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const FlashAttentionParams p) {
     constexpr bool F16 = std::is_same<E, _Float16>::value;
     constexpr int NP = D / 32, ND = D / 16;       // staging passes = MFMA k steps of a score tile; d tiles of O^T
-    typedef fa_vec8<E> ex8;
-    typedef fa_vec4<E> ex4;
-    typedef fa_vec2<E> ex2;
+    typedef vec8<E> ex8;
+    typedef vec4<E> ex4;
     __shared__ __attribute__((aligned(16))) E Kp[FA_T * D];
     __shared__ __attribute__((aligned(16))) E Vt[D * FA_VT_LD];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -248,11 +204,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
     {
         const float* qp = blk.q + qrow * p.q_ss + g * 8;
 #pragma unroll
-        for (int c = 0; c < NP; ++c) {
-            const f32x4 q0 = *reinterpret_cast<const f32x4*>(qp + c * 32), q1 = *reinterpret_cast<const f32x4*>(qp + c * 32 + 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { qf[c][e] = (E)q0[e]; qf[c][4 + e] = (E)q1[e]; }
-        }
+        for (int c = 0; c < NP; ++c) qf[c] = att_round8<E>(*reinterpret_cast<const f32x4*>(qp + c * 32), *reinterpret_cast<const f32x4*>(qp + c * 32 + 4));
     }
     // staging: keys (2 tp, 2 tp + 1) of the tile, d = c4 .. c4 + 3 with c4 = 16 (hi + 2 pass) + 4 lo
     const int s_lo = tid & 3, s_tp = (tid >> 2) & 31, s_hi = tid >> 7;
@@ -274,8 +226,8 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
     f32x4 o[ND];
 #pragma unroll
     for (int dt = 0; dt < ND; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float m = FA_NEG, l = 0.f;
-    const float sc2 = p.scale * FA_LOG2E;
+    float m = ATT_NEG, l = 0.f;
+    const float sc2 = p.scale * ATT_LOG2E;
 
     load_tile(0);
     for (int kt = 0; kt < blk.nkt; ++kt) {
@@ -289,14 +241,10 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
                 ex4 h;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) h[e] = (E)kr[ps][u][e];
-                *reinterpret_cast<ex4*>(Kp + t * D + (((c4 >> 3) ^ fa_kswz<D>(t)) << 3) + (c4 & 4)) = h;
+                *reinterpret_cast<ex4*>(att_k_chunk<D>(Kp + t * D, t, c4 >> 3) + (c4 & 4)) = h;
             }
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                ex2 h;
-                h[0] = (E)vr[ps][0][e]; h[1] = (E)vr[ps][1][e];
-                *reinterpret_cast<ex2*>(Vt + (c4 + e) * FA_VT_LD + s_tp * 2) = h;      // keys (2tp, 2tp+1) of row d = c4 + e
-            }
+            for (int e = 0; e < 4; ++e) att_vt_store(Vt + (c4 + e) * FA_VT_LD, s_tp, (E)vr[ps][0][e], (E)vr[ps][1][e]);
         }
         __syncthreads();
         if (kt + 1 < blk.nkt) load_tile((kt + 1) * FA_T);
@@ -307,10 +255,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
             const int key = s * 16 + li;
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int c = 0; c < NP; ++c) {
-                const ex8 kf = *reinterpret_cast<const ex8*>(Kp + key * D + (((c * 4 + g) ^ fa_kswz<D>(key)) << 3));
-                acc = fa_mfma<F16>(kf, qf[c], acc);
-            }
+            for (int c = 0; c < NP; ++c) acc = att_mfma<F16>(att_k_frag<D>(Kp + key * D, key, c * 4 + g), qf[c], acc);
             st[s] = acc;
         }
         const float alpha = fa_softmax_tile(st, sc2, fa_tile_masks(p, kt * FA_T, wave_row0), kt * FA_T, g, limit, m, l);
@@ -319,21 +264,12 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
         // O^T += V^T . P^T: k step t = key sub-tiles (2t, 2t+1)
 #pragma unroll
         for (int t = 0; t < FA_T / 32; ++t) {
-            ex8 pf;
+            const ex8 pf = att_round8<E>(st[2 * t], st[2 * t + 1]);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) { pf[e] = (E)st[2 * t][e]; pf[4 + e] = (E)st[2 * t + 1][e]; }
-#pragma unroll
-            for (int dt = 0; dt < ND; ++dt) {
-                const E* vrow = Vt + (dt * 16 + li) * FA_VT_LD + t * 32 + g * 4;
-                const ex4 lo = *reinterpret_cast<const ex4*>(vrow), hi = *reinterpret_cast<const ex4*>(vrow + 16);
-                ex8 vf;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { vf[e] = lo[e]; vf[4 + e] = hi[e]; }
-                o[dt] = fa_mfma<F16>(vf, pf, o[dt]);
-            }
+            for (int dt = 0; dt < ND; ++dt) o[dt] = att_mfma<F16>(att_vt_frag(Vt + (dt * 16 + li) * FA_VT_LD + g * 4, t), pf, o[dt]);
         }
     }
-    fa_store<ND>(query < p.seq_q ? blk.y + query * p.q_ss : nullptr, g, o, l);
+    fa_finish<ND>(query < p.seq_q ? blk.y + query * p.q_ss : nullptr, g, o, l);
 }
 
 template <int D>

@@ -10,18 +10,12 @@
 //   transpose/reshape, window_reverse, roll_2d(+shift), narrow (swin.rs:306-307, 387-401) -> index math on store
 // so none of the reference's ~8 full-tensor copies per block and no [B_,h,144,144] score tensor ever touch HBM.
 //
-// MFMA formulation (all tiles 16x16, k-step 4; C/D map: col = lane&15, row = 4*(lane>>4) + reg):
-//   S^T[key][query] = K . Q^T   A = K fragment (row = key),  B = Q^T (col = query); lane group g = lane>>4
-//                               contracts d = 8g + s at step s (both operands use the same permutation), so a
-//                               lane's 8 q (or k) values are 8 consecutive floats of one row.
+// MFMA formulation, tile map and LDS images: kernels/attention_mfma.h (S^T = K . Q^T, softmax in-lane over 36 registers and across
+// the 4 lane groups, O^T = V^T . P^T with P^T straight from the S^T accumulators).  What is particular here:
 //   bias                        = this head's 529-entry table column in LDS, indexed arithmetically (no [h,144,144] tensor)
-//   softmax over keys           = over the rows of S^T for a fixed column -> in-lane over 36 registers, then
-//                               across the 4 lane groups (shfl_xor 16, 32).
-//   O^T[d][query] = V^T . P^T   B = P^T taken straight from the S^T accumulator registers (lane group g holds keys
-//                               4g..4g+3 of a 16-key tile; step r contracts key 4g + r), A = V^T read from LDS with
-//                               the same key permutation.  No transpose, no LDS round trip for P.
+//   mask                        = the SW-MSA region ids of the window's tokens, compared per score
 #include "../brn_kernels.h"
-#include "split_planes.h"
+#include "attention_mfma.h"
 #include "window_geometry.h"
 #include "window_attention_select.h"
 #include <cstdlib>
@@ -67,41 +61,12 @@ __device__ __forceinline__ int att_qbase(int qi, int qj) { return (qi + WSZ - 1)
 template <int WSZ = WS>
 __device__ __forceinline__ int att_qrev(int qi, int qj) { return (2 * WSZ - 1) * (2 * WSZ - 1) - 1 - att_qbase<WSZ>(qi, qj); }
 
-// ---- split and bf16 kernels: 16-bit operands (E = __bf16 or _Float16), LDS images Kp[key][32 d] and Vt[d][VT_LD keys] ----
-template <typename E> using vec8 = E __attribute__((ext_vector_type(8)));
-template <typename E> using vec4 = E __attribute__((ext_vector_type(4)));
+// ---- split and bf16 kernels: 16-bit operands (E = __bf16 or _Float16), LDS images Kp[key][32 d] and Vt[d][VT_LD keys] of
+// kernels/attention_mfma.h (the split kernel's row = plane * NTOK + key: NTOK % 16 == 0, so the plane does not change the swizzle) ----
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 // every global load goes out unconditionally from a clamped address: a pad token (src < 0) reads row 0 and is replaced afterwards
 template <typename E>
 __device__ __forceinline__ const E* att_row_ptr(const E* qkv, int src, int C3) { return qkv + (long)max(src, 0) * C3; }
-// Kp: the 16-byte chunk c (d = 8c .. 8c+7) of row `key` is stored at c ^ kswz(key) = c ^ perm[(key >> 2) & 3], perm = {0,2,3,1}
-// (the split kernel passes row = plane * NTOK + key: NTOK % 16 == 0, so the plane does not change the swizzle)
-__device__ __forceinline__ int kswz(int key) { return (0x78 >> (2 * ((key >> 2) & 3))) & 3; }
-// A operand of S^T = K Q^T: d = 8g .. 8g+7 of row `key` (conflict-free ds_read_b128)
-template <typename E>
-__device__ __forceinline__ vec8<E> att_k_frag(const E* Kp, int key, int g) { return *reinterpret_cast<const vec8<E>*>(Kp + key * HD + ((g ^ kswz(key)) << 3)); }
-// A operand of O^T = V^T P^T at k-step t (key tiles 2t, 2t+1; the 10th tile does not exist: zeros); vrow = Vt + d * VT_LD + 4g
-template <typename E>
-__device__ __forceinline__ vec8<E> att_vt_frag(const E* vrow, int t) {
-    const vec4<E> lo = *reinterpret_cast<const vec4<E>*>(vrow + (2 * t) * 16);
-    vec4<E> hi = {(E)0.f, (E)0.f, (E)0.f, (E)0.f};
-    if (2 * t + 1 < 9) hi = *reinterpret_cast<const vec4<E>*>(vrow + (2 * t + 1) * 16);
-    vec8<E> vf;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { vf[e] = lo[e]; vf[4 + e] = hi[e]; }
-    return vf;
-}
-// B operand of the same k-step: the lane's 8 softmax numerators, straight out of the S^T accumulators
-__device__ __forceinline__ void att_p_step(const f32x4 (&st)[9], int t, float (&r)[8]) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { r[e] = st[2 * t][e]; r[4 + e] = (2 * t + 1 < 9) ? st[(2 * t + 1 < 9) ? 2 * t + 1 : 0][e] : 0.f; }
-}
-template <bool F16, typename V>
-__device__ __forceinline__ f32x4 att_mfma(const V a, const V b, const f32x4 c) {
-    if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 // H (mode f32_half2): the two planes are fp16 planes of the scaled operands (kernels/split_planes.h, split_pair_h) — q (with its head_dim^-0.5), k
 // and v scaled by 8, the un-normalised probabilities (in (0, 1]) by 2048 — on v_mfma_f32_16x16x32_f16; the scores and the output are
 // un-scaled exactly.  ~2^-22 relative per product instead of 2^-16.
@@ -222,8 +187,7 @@ __global__ void __launch_bounds__(NWV * 64) window_attention_f32_kernel(const Wi
     // one per score — and the softmax runs on exp2.  Window 7 keeps the plain table and the per-score index.
     constexpr int TABN = (2 * WS - 1) * (2 * WS - 1);
     constexpr bool REV = WS == 12;
-    constexpr float LOG2E = 1.4426950408889634f;
-    for (int i = tid; i < TABN; i += NTHR) tab_s[i] = REV ? LOG2E * p.rel_table[head * TABN + (TABN - 1 - i)] : p.rel_table[head * TABN + i];
+    for (int i = tid; i < TABN; i += NTHR) tab_s[i] = REV ? ATT_LOG2E * p.rel_table[head * TABN + (TABN - 1 - i)] : p.rel_table[head * TABN + i];
     const bool has_mask = att_has_mask<WS>(p, wr, wc);
     __syncthreads();
 
@@ -258,27 +222,17 @@ __global__ void __launch_bounds__(NWV * 64) window_attention_f32_kernel(const Wi
         const int qt_ = qtok < NTOK ? qtok : NTOK - 1;            // (dummy queries of the last tile compute on a valid row, never stored)
         const int qbase = att_qbase<WS>(qt_ / WS, qt_ % WS);
         // Q fragment: d = 8g .. 8g+7 of query row qtok, scaled before the product (swin.rs:278)
-        float qf[8];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { qf[e] = qn0[e] * p.scale; qf[4 + e] = qn1[e] * p.scale; }
+        const f32x4 qf0 = qn0 * p.scale, qf1 = qn1 * p.scale;
         if (qt + NWV < NT16) load_q(qt + NWV, qn0, qn1);
         // S^T = K . Q^T : 9 key tiles
         f32x4 st[NT16];
 #pragma unroll
         for (int kt = 0; kt < NT16; ++kt) {
-            const float* kp = Ks + (kt * 16 + li) * KV_LD + g * 8;
-            const f32x4 k0 = *reinterpret_cast<const f32x4*>(kp);
-            const f32x4 k1 = *reinterpret_cast<const f32x4*>(kp + 4);
-            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(k0[e], qf[e], acc, 0, 0, 0);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(k1[e], qf[4 + e], acc, 0, 0, 0);
-            st[kt] = acc;
+            st[kt] = att_score_f32(Ks + (kt * 16 + li) * KV_LD + g * 8, qf0, qf1, f32x4{0.f, 0.f, 0.f, 0.f});
             if (kt % 3 == 2) __builtin_amdgcn_sched_barrier(0);   // bound the scheduler's hoisting (register pressure)
         }
         // + relative position bias (swin.rs:284-285), + SW-MSA mask (swin.rs:288-297, value -100 swin.rs:651)
-        float mx = -3.0e38f;
+        float mx = ATT_NEG;
         if constexpr (REV) {
             const int qrev = att_qrev<WS>(qt_ / WS, qt_ % WS);
 #pragma unroll
@@ -286,13 +240,13 @@ __global__ void __launch_bounds__(NWV * 64) window_attention_f32_kernel(const Wi
                 const int key0 = kt * 16 + g * 4;
                 const float* tb = tab_s + qrev + key0 + (WS - 1) * (key0 / WS);
 #pragma unroll
-                for (int r = 0; r < 4; ++r) st[kt][r] = fmaf(st[kt][r], LOG2E, tb[r]);
+                for (int r = 0; r < 4; ++r) st[kt][r] = fmaf(st[kt][r], ATT_LOG2E, tb[r]);
             }
             if (has_mask) {
 #pragma unroll
                 for (int kt = 0; kt < NT16; ++kt) {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) st[kt][r] += (rid_s[kt * 16 + g * 4 + r] != qrid) ? -100.0f * LOG2E : 0.0f;
+                    for (int r = 0; r < 4; ++r) st[kt][r] += (rid_s[kt * 16 + g * 4 + r] != qrid) ? -100.0f * ATT_LOG2E : 0.0f;
                 }
             }
 #pragma unroll
@@ -306,14 +260,13 @@ __global__ void __launch_bounds__(NWV * 64) window_attention_f32_kernel(const Wi
                     const int kk = key < NTOK ? key : 0;
                     float s = st[kt][r] + tab_s[max(0, qbase - kk - (WS - 1) * (kk / WS))];
                     if (p.shift > 0) s += (rid_s[key] != qrid) ? -100.0f : 0.0f;
-                    if (NTOK % 16 != 0 && key >= NTOK) s = -3.0e38f;
+                    if (NTOK % 16 != 0 && key >= NTOK) s = ATT_NEG;
                     st[kt][r] = s;
                     mx = fmaxf(mx, s);
                 }
             }
         }
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        mx = att_group_max(mx);
         float sum = 0.f;
 #pragma unroll
         for (int kt = 0; kt < NT16; ++kt) {
@@ -324,8 +277,7 @@ __global__ void __launch_bounds__(NWV * 64) window_attention_f32_kernel(const Wi
                 sum += e;
             }
         }
-        sum += __shfl_xor(sum, 16);
-        sum += __shfl_xor(sum, 32);
+        sum = att_group_sum(sum);
         // O^T = V^T . P^T : two d tiles
         f32x4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -333,8 +285,8 @@ __global__ void __launch_bounds__(NWV * 64) window_attention_f32_kernel(const Wi
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float* vp = Vs + (kt * 16 + g * 4 + r) * KV_LD + li;
-                o0 = __builtin_amdgcn_mfma_f32_16x16x4f32(vp[0], st[kt][r], o0, 0, 0, 0);
-                o1 = __builtin_amdgcn_mfma_f32_16x16x4f32(vp[16], st[kt][r], o1, 0, 0, 0);
+                o0 = att_pv_f32(vp, 0, st[kt][r], o0);
+                o1 = att_pv_f32(vp, 1, st[kt][r], o1);
             }
             if (kt % 2 == 1) __builtin_amdgcn_sched_barrier(0);
         }
@@ -464,7 +416,7 @@ __global__ void __launch_bounds__(ATT_THREADS) __attribute__((amdgpu_waves_per_e
                 bf16x4 sp[2];
                 split4h<false>(kv[u], 0xffffffffu, ATT_H_QKV, sp);
 #pragma unroll
-                for (int pl = 0; pl < 2; ++pl) *reinterpret_cast<bf16x4*>(Kp + (pl * NTOK + tp * 2 + u) * HD + (((c4 >> 3) ^ kswz(tp * 2 + u)) << 3) + (c4 & 4)) = sp[pl];
+                for (int pl = 0; pl < 2; ++pl) *reinterpret_cast<bf16x4*>(att_k_chunk<HD>(Kp + (pl * NTOK + tp * 2 + u) * HD, tp * 2 + u, c4 >> 3) + (c4 & 4)) = sp[pl];
             }
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -482,7 +434,7 @@ __global__ void __launch_bounds__(ATT_THREADS) __attribute__((amdgpu_waves_per_e
                     bf16x4 h;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) h[e] = (__bf16)r[e];
-                    *reinterpret_cast<bf16x4*>(Kp + (pl * NTOK + tp * 2 + u) * HD + (((c4 >> 3) ^ kswz(tp * 2 + u)) << 3) + (c4 & 4)) = h;
+                    *reinterpret_cast<bf16x4*>(att_k_chunk<HD>(Kp + (pl * NTOK + tp * 2 + u) * HD, tp * 2 + u, c4 >> 3) + (c4 & 4)) = h;
                     if (pl + 1 < NP) {
 #pragma unroll
                         for (int e = 0; e < 4; ++e) r[e] -= (float)h[e];
@@ -494,10 +446,9 @@ __global__ void __launch_bounds__(ATT_THREADS) __attribute__((amdgpu_waves_per_e
             for (int pl = 0; pl < NP; ++pl) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    bf16x2 h;
-                    h[0] = (__bf16)r0[e]; h[1] = (__bf16)r1[e];
-                    *reinterpret_cast<bf16x2*>(Vt + (pl * HD + c4 + e) * VT_LD + tp * 2) = h;   // keys (2tp, 2tp+1) of row d = c4+e
-                    if (pl + 1 < NP) { r0[e] -= (float)h[0]; r1[e] -= (float)h[1]; }
+                    const __bf16 h0 = (__bf16)r0[e], h1 = (__bf16)r1[e];
+                    att_vt_store(Vt + (pl * HD + c4 + e) * VT_LD, tp, h0, h1);
+                    if (pl + 1 < NP) { r0[e] -= (float)h0; r1[e] -= (float)h1; }
                 }
             }
         }
@@ -533,11 +484,11 @@ __global__ void __launch_bounds__(ATT_THREADS) __attribute__((amdgpu_waves_per_e
         for (int kt = 0; kt < 9; ++kt) {
             bf16x8 kf[NP];
 #pragma unroll
-            for (int pl = 0; pl < NP; ++pl) kf[pl] = att_k_frag(Kp, pl * NTOK + kt * 16 + li, g);
+            for (int pl = 0; pl < NP; ++pl) kf[pl] = att_k_frag<HD>(Kp + (pl * NTOK + kt * 16 + li) * HD, kt * 16 + li, g);
             st[kt] = att_plane_mfma<NP, H>(kf, qf, f32x4{0.f, 0.f, 0.f, 0.f});
             if (kt % 3 == 2) __builtin_amdgcn_sched_barrier(0);
         }
-        float mx = -3.0e38f;
+        float mx = ATT_NEG;
 #pragma unroll
         for (int kt = 0; kt < 9; ++kt) {
 #pragma unroll
@@ -549,8 +500,7 @@ __global__ void __launch_bounds__(ATT_THREADS) __attribute__((amdgpu_waves_per_e
                 mx = fmaxf(mx, sv);
             }
         }
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        mx = att_group_max(mx);
         float sum = 0.f;
 #pragma unroll
         for (int kt = 0; kt < 9; ++kt) {
@@ -561,8 +511,7 @@ __global__ void __launch_bounds__(ATT_THREADS) __attribute__((amdgpu_waves_per_e
                 sum += e;
             }
         }
-        sum += __shfl_xor(sum, 16);
-        sum += __shfl_xor(sum, 32);
+        sum = att_group_sum(sum);
         // O^T = V^T P^T: 5 k-steps of 32 keys (key tiles 2t, 2t+1; the 10th tile does not exist: zero operands)
         f32x4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -575,7 +524,7 @@ __global__ void __launch_bounds__(ATT_THREADS) __attribute__((amdgpu_waves_per_e
             for (int dt = 0; dt < 2; ++dt) {
                 bf16x8 vf[NP];
 #pragma unroll
-                for (int pl = 0; pl < NP; ++pl) vf[pl] = att_vt_frag(Vt + (pl * HD + dt * 16 + li) * VT_LD + g * 4, t);
+                for (int pl = 0; pl < NP; ++pl) vf[pl] = att_vt_frag(Vt + (pl * HD + dt * 16 + li) * VT_LD + g * 4, t, 2 * t + 1 < 9);
                 if (dt == 0) o0 = att_plane_mfma<NP, H>(vf, pf, o0);
                 else o1 = att_plane_mfma<NP, H>(vf, pf, o1);
             }
@@ -615,12 +564,10 @@ template <int ATT_BF16_HPW, bool F16 = false>
 __global__ void __launch_bounds__(ATT_BF16_HPW * ATT_THREADS) __attribute__((amdgpu_waves_per_eu(5, 8))) window_attention_bf16_kernel(const WindowAttnParams pa, const WindowAttnParams pb, const WindowOrder ord) {
     using E = std::conditional_t<F16, _Float16, __bf16>;
     typedef vec8<E> ex8;
-    typedef E ex2 __attribute__((ext_vector_type(2)));
     const AttBlock blk = att_block(ord);
     const bool second = blk.win.geom != 0;
     const WindowAttnParams& p = second ? pb : pa;
     constexpr int TABN = (2 * WS - 1) * (2 * WS - 1);                 // 529
-    constexpr float LOG2E = 1.4426950408889634f;
     __shared__ __attribute__((aligned(16))) E Kp_[ATT_BF16_HPW][NTOK * HD];
     __shared__ __attribute__((aligned(16))) E Vt_[ATT_BF16_HPW][HD * VT_LD];
     // a head's bias table REVERSED and in log2 units: rev[j] = log2(e) * table[528 - j].  The 4 keys 16 kt + 4 g + {0..3} of a lane
@@ -689,7 +636,7 @@ __global__ void __launch_bounds__(ATT_BF16_HPW * ATT_THREADS) __attribute__((amd
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         const int i = tid + j * NTHR;
-        if (i < NTAB) { const int hh = i / TABN; rev_[hh][i - hh * TABN] = LOG2E * tbw[j]; }
+        if (i < NTAB) { const int hh = i / TABN; rev_[hh][i - hh * TABN] = ATT_LOG2E * tbw[j]; }
     }
 #pragma unroll
     for (int u = 0; u < 3; ++u)
@@ -707,19 +654,16 @@ __global__ void __launch_bounds__(ATT_BF16_HPW * ATT_THREADS) __attribute__((amd
                     vv[it][u] = bias8_s16<E>(p.qkv_bias + 2 * C + hd + c8);
                 }
             }
+            // (att_k_chunk, spelled out: through the helper this kernel's staging addresses compiled to other vector code)
 #pragma unroll
-            for (int u = 0; u < 2; ++u) *reinterpret_cast<ex8*>(Kp_[hh] + (tp * 2 + u) * HD + (((c8 >> 3) ^ kswz(tp * 2 + u)) << 3)) = kv[it][u];
+            for (int u = 0; u < 2; ++u) *reinterpret_cast<ex8*>(Kp_[hh] + (tp * 2 + u) * HD + (((c8 >> 3) ^ att_kswz<HD>(tp * 2 + u)) << 3)) = kv[it][u];
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                ex2 h;
-                h[0] = vv[it][0][e]; h[1] = vv[it][1][e];
-                *reinterpret_cast<ex2*>(Vt_[hh] + (c8 + e) * VT_LD + tp * 2) = h;
-            }
+            for (int e = 0; e < 8; ++e) att_vt_store(Vt_[hh] + (c8 + e) * VT_LD, tp, vv[it][0][e], vv[it][1][e]);
         }
     }
     __syncthreads();
 
-    const float scale2 = p.scale * LOG2E;
+    const float scale2 = p.scale * ATT_LOG2E;
     ex8 ones8;
 #pragma unroll
     for (int e = 0; e < 8; ++e) ones8[e] = (E)1.0f;
@@ -743,10 +687,10 @@ __global__ void __launch_bounds__(ATT_BF16_HPW * ATT_THREADS) __attribute__((amd
         f32x4 st[9];
 #pragma unroll
         for (int kt = 0; kt < 9; ++kt) {
-            st[kt] = att_mfma<F16>(att_k_frag(Kp, kt * 16 + li, g), qf[u], f32x4{0.f, 0.f, 0.f, 0.f});
+            st[kt] = att_mfma<F16>(att_k_frag<HD>(Kp + (kt * 16 + li) * HD, kt * 16 + li, g), qf[u], f32x4{0.f, 0.f, 0.f, 0.f});
             if (kt % 3 == 2) __builtin_amdgcn_sched_barrier(0);
         }
-        float mx = -3.0e38f;
+        float mx = ATT_NEG;
         unsigned tbq = (unsigned)(unsigned long)(lds_cfloat*)(rev_s + qrev);
         asm volatile("" : "+v"(tbq));
 #pragma unroll
@@ -764,13 +708,12 @@ __global__ void __launch_bounds__(ATT_BF16_HPW * ATT_THREADS) __attribute__((amd
                 const unsigned xr = *reinterpret_cast<const unsigned*>(rid_s + kt * 16 + g * 4) ^ qrid4;
                 const unsigned x = ((xr + 0x7f7f7f7fu) >> 7) & 0x01010101u;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) st[kt][r] = fmaf((float)((x >> (8 * r)) & 0xffu), -100.0f * LOG2E, st[kt][r]);
+                for (int r = 0; r < 4; ++r) st[kt][r] = fmaf((float)((x >> (8 * r)) & 0xffu), -100.0f * ATT_LOG2E, st[kt][r]);
             }
         }
 #pragma unroll
         for (int kt = 0; kt < 9; ++kt) mx = max3f(max3f(mx, st[kt][0], st[kt][1]), st[kt][2], st[kt][3]);
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        mx = att_group_max(mx);
 #pragma unroll
         for (int kt = 0; kt < 9; ++kt) {
 #pragma unroll
@@ -788,7 +731,7 @@ __global__ void __launch_bounds__(ATT_BF16_HPW * ATT_THREADS) __attribute__((amd
             for (int e = 0; e < 8; ++e) pf[e] = (E)pr[e];
 #pragma unroll
             for (int dt = 0; dt < 2; ++dt) {
-                const ex8 vf = att_vt_frag(Vt + (dt * 16 + li) * VT_LD + g * 4, t);
+                const ex8 vf = att_vt_frag(Vt + (dt * 16 + li) * VT_LD + g * 4, t, 2 * t + 1 < 9);
                 if (dt == 0) o0 = att_mfma<F16>(vf, pf, o0);
                 else o1 = att_mfma<F16>(vf, pf, o1);
             }
