@@ -171,8 +171,10 @@ struct AttentionBiasParams {
 };
 hipError_t launch_attention_bias(const AttentionBiasParams& p, hipStream_t s);
 
-// q/k/v attention for long sequences, online softmax over K / V tiles (kernels/flash_attention.hip; brn_flash_attention_forward):
-// y[b,h] = softmax_rows(scale * q[b,h] k[b,h]^T [causal: key j <= query i]) v[b,h], head_dim 32 / 64 / 128, 1 <= seq_q, seq_kv <= 65536
+// q/k/v attention for long sequences, online softmax over K / V tiles (kernels/flash_attention.hip; brn_flash_attention_forward and, with
+// a bias, brn_flash_attention_bias_forward):
+// y[b,h] = softmax_rows(scale * (q[b,h] k[b,h]^T [+ bias[b % n_bias, h]]) [causal: key j <= query i]) v[b,h], head_dim 32 / 64 / 128,
+// 1 <= seq_q, seq_kv <= 65536
 struct FlashAttentionParams {
     const float* q; const float* k; const float* v;   // 16-byte aligned; head_dim contiguous
     float* y;             // q's shape and strides
@@ -182,6 +184,10 @@ struct FlashAttentionParams {
     int causal;           // 1: key j takes part in query i's row exactly when j <= i (seq_q == seq_kv)
     float scale;          // > 0 (the entry replaces 0 by head_dim^-0.5)
     int s16;              // 0: fp32 MFMA kernel; 1 / 2: q, k, v and the softmax numerators rounded to bf16 / fp16 on the 16-bit matrix instructions
+    // brn_flash_attention_bias_forward; all zero = no bias (the bias-free kernels)
+    const float* bias;    // [n_bias, heads, seq_q, seq_kv] fp32, 16-byte aligned, added to the UNSCALED scores (-inf: the key is excluded); or null
+    int n_bias;           // batch entry b reads pattern b % n_bias (batch % n_bias == 0); 0 exactly when bias is null
+    long b_sp, b_sh;      // element strides of bias: pattern, head (heads-major whatever the layout of q / k / v)
 };
 hipError_t launch_flash_attention(const FlashAttentionParams& p, hipStream_t s);
 

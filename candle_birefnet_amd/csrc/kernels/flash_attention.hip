@@ -1,5 +1,5 @@
-// flash_attention.hip — q/k/v attention for long sequences (brn_flash_attention_forward):
-//   y[b,h] = softmax_rows( scale * q[b,h] k[b,h]^T  [causal: key j takes part in query i's row exactly when j <= i] ) v[b,h]
+// flash_attention.hip — q/k/v attention for long sequences (brn_flash_attention_forward, brn_flash_attention_bias_forward):
+//   y[b,h] = softmax_rows( scale * (q[b,h] k[b,h]^T [+ bias[b % n_bias, h]])  [causal: key j takes part in query i's row exactly when j <= i] ) v[b,h]
 // the plain flash_attention(&q, &k, &v, causal) of the reference's flash-attn dependency (examples/bench_flash_attn.rs:39-53), head_dim
 // 32 / 64 / 128, 1 <= seq <= 65536, q and k/v of different lengths, in either the [batch, seq, heads, head_dim] or the
 // [batch, heads, seq, head_dim] layout: the kernels take element strides (batch entry, head, sequence position; head_dim contiguous).
@@ -25,6 +25,11 @@
 // a lane's query are excluded.  Key 0 is visible to every query, so after the first tile every m is a real score: alpha never sees
 // (-3e38) - (-3e38) with a non-zero l behind it, and exp2(excluded - m) is exactly 0 — an excluded key is in neither the maximum nor
 // the sum.
+// BIAS = true (a bias is given): the [seq_q, seq_kv] fp32 slab of the workgroup's (pattern, head) is streamed beside K and V.  A lane's
+// 16 bias values of a tile (fa_load_bias) are issued with that tile's K / V global loads, held in registers under the MFMAs of the tile
+// before, and become the initial accumulators of S^T = K . Q^T: the bias joins the unscaled fp32 scores at no instruction, and an
+// all-zero bias gives the bits of BIAS = false.  A -inf entry excludes its key (exp2(-inf - m) = 0; it never raises m).  BIAS = false is
+// the kernel as it was, instruction for instruction.  No additional LDS.  DESIGN.md 3.2d.
 #include "../brn_kernels.h"
 #include "attention_mfma.h"
 #include <type_traits>
@@ -40,9 +45,11 @@ constexpr int FA_VT_LD = 72;         // 16-bit kernel: elements per LDS row of V
 // which (batch entry, head, query tile) this workgroup owns, where its operands start and how many K / V tiles it walks
 struct FaBlock {
     const float* q; const float* k; const float* v; float* y;
+    const float* bias;    // BIAS: the [seq_q, seq_kv] slab of this (bias pattern = batch entry % n_bias, head)
     int q0;               // first query of the tile
     int nkt;              // K / V tiles to walk: all of them, or (causal) those that reach the tile's last query
 };
+template <bool BIAS>
 __device__ __forceinline__ FaBlock fa_block(const FlashAttentionParams& p) {
     const int nqt = (p.seq_q + FA_BQ - 1) / FA_BQ;
     // not causal: the query tiles of a (batch entry, head) are neighbours in the grid (they walk the same K and V).  Causal: tile qt walks
@@ -60,10 +67,44 @@ __device__ __forceinline__ FaBlock fa_block(const FlashAttentionParams& p) {
     r.y = p.y + b * p.q_sb + h * p.q_sh;
     r.k = p.k + b * p.kv_sb + h * p.kv_sh;
     r.v = p.v + b * p.kv_sb + h * p.kv_sh;
+    r.bias = nullptr;
+    if constexpr (BIAS) r.bias = p.bias + (b % p.n_bias) * p.b_sp + h * p.b_sh;
     r.q0 = qt * FA_BQ;
     r.nkt = (p.seq_kv + FA_T - 1) / FA_T;
     if (p.causal) r.nkt = min(r.nkt, min(r.q0 + FA_BQ - 1, p.seq_q - 1) / FA_T + 1);
     return r;
+}
+
+// The bias values a lane adds to its scores of the K / V tile at key0: for sub-tile s the 4 consecutive floats of keys
+// key0 + 16 s + 4 g + 0..3 in row `row` (= the lane's clamped query * seq_kv, 64-bit) of the slab.  Every address stays inside the slab:
+// seq_kv % 4 == 0 -> one 16-byte load per sub-tile, its first key clamped to seq_kv - 4 (the slab base is 16-byte aligned and row and
+// key are multiples of 4, so the address is; a group of 4 is then wholly real or wholly past seq_kv); otherwise 4-byte loads with each
+// key clamped to seq_kv - 1.  The choice is a function of seq_kv alone (wave-uniform).  What a clamped load returns belongs to an
+// excluded key and is replaced before the maximum.  No address depends on a bias value.
+// A/B switch (make EXTRA_CXXFLAGS=-DFA_BIAS_NONTEMPORAL=1): the 16-byte bias loads as non-temporal loads.  Every bias element is read once by
+// one lane, so it has nothing to gain from the caches; DESIGN.md 3.2d has what the two builds measured.
+#ifndef FA_BIAS_NONTEMPORAL
+#define FA_BIAS_NONTEMPORAL 0
+#endif
+__device__ __forceinline__ void fa_load_bias(f32x4 (&bv)[FA_T / 16], const float* slab, long row, int key0, int g, int seq_kv) {
+    const float* rp = slab + row;
+    if ((seq_kv & 3) == 0) {
+#pragma unroll
+        for (int s = 0; s < FA_T / 16; ++s) {
+            const f32x4* src = reinterpret_cast<const f32x4*>(rp + min(key0 + s * 16 + g * 4, seq_kv - 4));
+#if FA_BIAS_NONTEMPORAL
+            bv[s] = __builtin_nontemporal_load(src);
+#else
+            bv[s] = *src;
+#endif
+        }
+    } else {
+#pragma unroll
+        for (int s = 0; s < FA_T / 16; ++s) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) bv[s][r] = rp[min(key0 + s * 16 + g * 4 + r, seq_kv - 1)];
+        }
+    }
 }
 
 // One tile of the online softmax.  st: the lane's raw scores of keys key0 + 16 s + 4 g + r (s = sub-tile, r = register) of its query;
@@ -92,9 +133,12 @@ __device__ __forceinline__ bool fa_tile_masks(const FlashAttentionParams& p, int
     return key0 + FA_T > lim;
 }
 // the 4 partial sums of a query are added, and the query's row of y (null: a pad query) is stored
-template <int ND>
-__device__ __forceinline__ void fa_finish(float* yrow, int g, const f32x4 (&o)[ND], float l) {
-    const float inv = 1.0f / att_group_sum(l);
+// BIAS: a row whose every visible key has a -inf bias never saw a real score (m is still ATT_NEG) and comes back NaN, also where excluded
+// keys of its tiles left exp2(ATT_NEG - ATT_NEG) = 1 in l
+template <int ND, bool BIAS>
+__device__ __forceinline__ void fa_finish(float* yrow, int g, const f32x4 (&o)[ND], float l, float m) {
+    float inv = 1.0f / att_group_sum(l);
+    if constexpr (BIAS) inv = (m > ATT_NEG) ? inv : __builtin_nanf("");
     if (yrow) {
 #pragma unroll
         for (int dt = 0; dt < ND; ++dt) att_store_o(yrow + g * 4, dt, o[dt], inv);
@@ -103,18 +147,19 @@ __device__ __forceinline__ void fa_finish(float* yrow, int g, const f32x4 (&o)[N
 
 // ---- fp32: v_mfma_f32_16x16x4_f32, an exact fmaf chain per score and per output ----
 // LDS: Ks, Vs [64][D + 4] floats (D 128: 66 KB).  Staging item = (key, 4-wide d chunk), D / 16 items of K and of V per thread.
-template <int D>
+template <int D, bool BIAS>
 __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const FlashAttentionParams p) {
     constexpr int LD = D + 4, NI = D / 16, ND = D / 16, NC = D / 32;
     __shared__ __attribute__((aligned(16))) float Ks[FA_T * LD];
     __shared__ __attribute__((aligned(16))) float Vs[FA_T * LD];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, g = lane >> 4;
-    const FaBlock blk = fa_block(p);
+    const FaBlock blk = fa_block<BIAS>(p);
 
     const int query = blk.q0 + wave * 16 + li, qrow = min(query, p.seq_q - 1);
     const int wave_row0 = min(blk.q0 + wave * 16, p.seq_q - 1);
     const int limit = p.causal ? min(p.seq_kv, qrow + 1) : p.seq_kv;
+    const long brow = (long)qrow * p.seq_kv;       // BIAS: the query's row of the bias slab
     // Q fragment: chunk c of 32 d's -> d = 32 c + 8 g .. + 7 of the query's row (the MFMA k order is a permutation of d; K uses the same)
     f32x4 qv[2 * NC];
     {
@@ -126,6 +171,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
         }
     }
     f32x4 kr[NI], vr[NI];
+    f32x4 bn[FA_T / 16];                                   // BIAS: the bias of the tile in kr / vr, loaded with it
     auto load_tile = [&](int key0) {
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
@@ -135,6 +181,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
             vr[i] = *reinterpret_cast<const f32x4*>(blk.v + src);
             if (t >= p.seq_kv) { kr[i] = f32x4{0.f, 0.f, 0.f, 0.f}; vr[i] = kr[i]; }
         }
+        if constexpr (BIAS) fa_load_bias(bn, blk.bias, brow, key0, g, p.seq_kv);
     };
     f32x4 o[ND];
 #pragma unroll
@@ -152,12 +199,17 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
             *reinterpret_cast<f32x4*>(Vs + t * LD + c4) = vr[i];
         }
         __syncthreads();
-        if (kt + 1 < blk.nkt) load_tile((kt + 1) * FA_T);
-        // S^T = K . Q^T
+        // S^T = K . Q^T (BIAS: + bias, as the initial accumulator: it joins the unscaled scores, and an all-zero bias gives the bias-free bits)
         f32x4 st[FA_T / 16];
+        if constexpr (BIAS) {
+#pragma unroll
+            for (int s = 0; s < FA_T / 16; ++s) st[s] = bn[s];
+        }
+        if (kt + 1 < blk.nkt) load_tile((kt + 1) * FA_T);
 #pragma unroll
         for (int s = 0; s < FA_T / 16; ++s) {
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            if constexpr (BIAS) acc = st[s];
 #pragma unroll
             for (int c = 0; c < NC; ++c) acc = att_score_f32(Ks + (s * 16 + li) * LD + c * 32 + g * 8, qv[2 * c], qv[2 * c + 1], acc);
             st[s] = acc;
@@ -176,7 +228,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
             }
         }
     }
-    fa_finish<ND>(query < p.seq_q ? blk.y + query * p.q_ss : nullptr, g, o, l);
+    fa_finish<ND, BIAS>(query < p.seq_q ? blk.y + query * p.q_ss : nullptr, g, o, l, m);
 }
 
 // ---- 16-bit: q, k, v rounded to E (round to nearest even) as they are loaded; v_mfma_f32_16x16x32_{bf16,f16} with fp32 accumulation.
@@ -184,7 +236,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
 // LDS: Kp[key][D] and Vt[d][72 keys] (kernels/attention_mfma.h): D 128 = 16 + 18 KB.
 // Staging item = (key pair, 4-wide d chunk): thread -> (d chunk low 2 bits, key pair, d chunk high bits), so a quad of lanes reads 64
 // contiguous bytes of a row and the 4-byte transposed V writes of a wave fall 2-way on the 32 banks. ----
-template <typename E, int D>
+template <typename E, int D, bool BIAS>
 __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const FlashAttentionParams p) {
     constexpr bool F16 = std::is_same<E, _Float16>::value;
     constexpr int NP = D / 32, ND = D / 16;       // staging passes = MFMA k steps of a score tile; d tiles of O^T
@@ -194,11 +246,12 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
     __shared__ __attribute__((aligned(16))) E Vt[D * FA_VT_LD];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, g = lane >> 4;
-    const FaBlock blk = fa_block(p);
+    const FaBlock blk = fa_block<BIAS>(p);
 
     const int query = blk.q0 + wave * 16 + li, qrow = min(query, p.seq_q - 1);
     const int wave_row0 = min(blk.q0 + wave * 16, p.seq_q - 1);
     const int limit = p.causal ? min(p.seq_kv, qrow + 1) : p.seq_kv;
+    const long brow = (long)qrow * p.seq_kv;       // BIAS: the query's row of the bias slab
     // Q fragment of MFMA k step c: d = 32 c + 8 g .. + 7 of the query's row
     ex8 qf[NP];
     {
@@ -209,6 +262,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
     // staging: keys (2 tp, 2 tp + 1) of the tile, d = c4 .. c4 + 3 with c4 = 16 (hi + 2 pass) + 4 lo
     const int s_lo = tid & 3, s_tp = (tid >> 2) & 31, s_hi = tid >> 7;
     f32x4 kr[NP][2], vr[NP][2];
+    f32x4 bn[FA_T / 16];                                   // BIAS: the bias of the tile in kr / vr, loaded with it
     auto load_tile = [&](int key0) {
 #pragma unroll
         for (int ps = 0; ps < NP; ++ps) {
@@ -222,6 +276,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
                 if (t >= p.seq_kv) { kr[ps][u] = f32x4{0.f, 0.f, 0.f, 0.f}; vr[ps][u] = kr[ps][u]; }
             }
         }
+        if constexpr (BIAS) fa_load_bias(bn, blk.bias, brow, key0, g, p.seq_kv);
     };
     f32x4 o[ND];
 #pragma unroll
@@ -247,13 +302,18 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
             for (int e = 0; e < 4; ++e) att_vt_store(Vt + (c4 + e) * FA_VT_LD, s_tp, (E)vr[ps][0][e], (E)vr[ps][1][e]);
         }
         __syncthreads();
-        if (kt + 1 < blk.nkt) load_tile((kt + 1) * FA_T);
-        // S^T = K . Q^T
+        // S^T = K . Q^T (BIAS: + bias, as the initial accumulator: it joins the unscaled scores, and an all-zero bias gives the bias-free bits)
         f32x4 st[FA_T / 16];
+        if constexpr (BIAS) {
+#pragma unroll
+            for (int s = 0; s < FA_T / 16; ++s) st[s] = bn[s];
+        }
+        if (kt + 1 < blk.nkt) load_tile((kt + 1) * FA_T);
 #pragma unroll
         for (int s = 0; s < FA_T / 16; ++s) {
             const int key = s * 16 + li;
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            if constexpr (BIAS) acc = st[s];
 #pragma unroll
             for (int c = 0; c < NP; ++c) acc = att_mfma<F16>(att_k_frag<D>(Kp + key * D, key, c * 4 + g), qf[c], acc);
             st[s] = acc;
@@ -269,22 +329,28 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
             for (int dt = 0; dt < ND; ++dt) o[dt] = att_mfma<F16>(att_vt_frag(Vt + (dt * 16 + li) * FA_VT_LD + g * 4, t), pf, o[dt]);
         }
     }
-    fa_finish<ND>(query < p.seq_q ? blk.y + query * p.q_ss : nullptr, g, o, l);
+    fa_finish<ND, BIAS>(query < p.seq_q ? blk.y + query * p.q_ss : nullptr, g, o, l, m);
 }
 
-template <int D>
+template <int D, bool BIAS>
 void fa_launch(const FlashAttentionParams& p, dim3 grid, hipStream_t s) {
     const dim3 block(FA_THREADS);
-    if (p.s16 == 0) hipLaunchKernelGGL(flash_attention_f32_kernel<D>, grid, block, 0, s, p);
-    else if (p.s16 == 1) hipLaunchKernelGGL((flash_attention_s16_kernel<__bf16, D>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((flash_attention_s16_kernel<_Float16, D>), grid, block, 0, s, p);
+    if (p.s16 == 0) hipLaunchKernelGGL((flash_attention_f32_kernel<D, BIAS>), grid, block, 0, s, p);
+    else if (p.s16 == 1) hipLaunchKernelGGL((flash_attention_s16_kernel<__bf16, D, BIAS>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((flash_attention_s16_kernel<_Float16, D, BIAS>), grid, block, 0, s, p);
+}
+template <int D>
+void fa_launch(const FlashAttentionParams& p, dim3 grid, hipStream_t s) {
+    if (p.bias) fa_launch<D, true>(p, grid, s);
+    else fa_launch<D, false>(p, grid, s);
 }
 
 }  // namespace
 
 hipError_t launch_flash_attention(const FlashAttentionParams& p, hipStream_t s) {
     if (!(p.head_dim == 32 || p.head_dim == 64 || p.head_dim == 128) || p.seq_q < 1 || p.seq_kv < 1 || p.seq_q > 65536 || p.seq_kv > 65536 ||
-        p.batch < 1 || p.heads < 1 || (p.causal && p.seq_q != p.seq_kv) || p.s16 < 0 || p.s16 > 2 || !(p.scale > 0.f))
+        p.batch < 1 || p.heads < 1 || (p.causal && p.seq_q != p.seq_kv) || p.s16 < 0 || p.s16 > 2 || !(p.scale > 0.f) ||
+        p.n_bias < 0 || (p.bias == nullptr) != (p.n_bias == 0) || (p.n_bias > 0 && p.batch % p.n_bias))
         return hipErrorInvalidValue;
     const long nwg = (long)p.batch * p.heads * ((p.seq_q + FA_BQ - 1) / FA_BQ);
     if (nwg > 0x7fffffffL) return hipErrorInvalidValue;

@@ -106,24 +106,28 @@ def attention(q, k, v, bias=None, n_bias=None, scale=None, device=0):
 
 def attention_with_bias(q, k, v, scaled_bias):
     """flash_attention_with_bias(&q, &k, &v, &scaled_bias, false) (swin.rs:252): scaled_bias [1 or batch, heads, N, N] is the bias
-    already divided by the softmax scale (swin.rs:250)."""
+    already divided by the softmax scale (swin.rs:250).  N <= 144, head_dim 32; longer sequences, other head dims and the causal flag:
+    flash_attention(..., layout="bhsd", bias=scaled_bias)."""
     return attention(q, k, v, scaled_bias)
 
 
 def attention_with_repeating_bias(q, k, v, scaled_bias, n_windows):
     """flash_attention_with_repeating_bias(&q, &k, &v, &scaled_combined, n_windows, false) (swin.rs:243): scaled_bias
-    [n_windows, heads, N, N], batch entry b reads pattern b % n_windows (swin.rs:291-294)."""
+    [n_windows, heads, N, N], batch entry b reads pattern b % n_windows (swin.rs:291-294).  N <= 144, head_dim 32; the long form is
+    flash_attention(..., layout="bhsd", bias=scaled_bias) with n_bias = scaled_bias.shape[0]."""
     return attention(q, k, v, scaled_bias, n_bias=int(n_windows))
 
 
 _ATTN_LAYOUT = {"bshd": _ffi.BRN_ATTN_BSHD, "bhsd": _ffi.BRN_ATTN_BHSD}
 
 
-def flash_attention(q, k, v, causal=False, scale=None, layout="bshd", device=0):
+def flash_attention(q, k, v, causal=False, scale=None, layout="bshd", device=0, bias=None):
     """flash_attention(&q, &k, &v, causal) (examples/bench_flash_attn.rs:39-53): y = softmax(scale * q k^T [causal: key j <= query i]) v per
     (batch entry, head).  layout "bshd": q [batch, seq_q, heads, head_dim], k, v [batch, seq_kv, heads, head_dim] (flash_attention's own);
-    "bhsd": [batch, heads, seq, head_dim] (ops.attention's).  y has q's shape.  scale None = head_dim^-0.5.  The limits are the library's
-    (include/birefnet_hip.h brn_flash_attention_forward): nothing is checked here."""
+    "bhsd": [batch, heads, seq, head_dim] (ops.attention's).  y has q's shape.  scale None = head_dim^-0.5.
+    bias (a numpy array or a device tensor, like q): [n_bias, heads, seq_q, seq_kv] fp32, heads-major in either layout, added to the
+    UNSCALED scores; batch entry b reads pattern b % n_bias; -inf excludes a key.  Without it brn_flash_attention_forward is called, with
+    it brn_flash_attention_bias_forward.  The limits are the library's (include/birefnet_hip.h): nothing is checked here."""
     lay = _ATTN_LAYOUT[layout]
     if lay == _ffi.BRN_ATTN_BSHD:
         batch, seq_q, heads, hd = (int(s) for s in q.shape)
@@ -138,10 +142,19 @@ def flash_attention(q, k, v, causal=False, scale=None, layout="bshd", device=0):
     pv, vloc, vkeep, _ = T.as_arg(v, kv_shape)
     if not (kloc == vloc == loc):
         raise ValueError("q, k and v must live on the same side")
+    sc = float(scale) if scale is not None else 0.0
+    if bias is None:
+        y = T.alloc_like(keep, tuple(int(s) for s in q.shape))
+        _ffi.check(_ffi.lib.brn_flash_attention_forward(pq, pk, pv, batch, seq_q, seq_kv, heads, hd, lay, int(bool(causal)), sc, T.ptr_of(y), loc,
+                                                        T.device_of(keep, device), T.stream_of(keep)))
+        return y
+    n_bias = int(bias.shape[0])
+    pb, bloc, bkeep, _ = T.as_arg(bias, (n_bias, heads, seq_q, seq_kv))
+    if bloc != loc:
+        raise ValueError("q, k, v and bias must live on the same side")
     y = T.alloc_like(keep, tuple(int(s) for s in q.shape))
-    _ffi.check(_ffi.lib.brn_flash_attention_forward(pq, pk, pv, batch, seq_q, seq_kv, heads, hd, lay, int(bool(causal)),
-                                                    float(scale) if scale is not None else 0.0, T.ptr_of(y), loc, T.device_of(keep, device),
-                                                    T.stream_of(keep)))
+    _ffi.check(_ffi.lib.brn_flash_attention_bias_forward(pq, pk, pv, batch, seq_q, seq_kv, heads, hd, lay, int(bool(causal)), pb, n_bias, sc,
+                                                         T.ptr_of(y), loc, T.device_of(keep, device), T.stream_of(keep)))
     return y
 
 

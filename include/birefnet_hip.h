@@ -291,12 +291,37 @@ brn_status brn_attention_forward(const float* q, const float* k, const float* v,
  * scores, the running maximum, the running sum (taken from the unrounded numerators) and y stay fp32.  Every other mode runs ONE exact
  * fp32 kernel (v_mfma_f32_16x16x4_f32): bit-identical results across BRN_F32, BRN_F32_SPLIT3, BRN_F32_SPLIT2 and BRN_F32_HALF2.
  * Not provided: a bias together with long sequences (brn_attention_forward has the bias, up to N = 144); a causal mask with
- * seq_q != seq_kv; head dims other than 32 / 64 / 128. */
+ * seq_q != seq_kv; head dims other than 32 / 64 / 128.  The bias together with long sequences is provided by
+ * brn_flash_attention_bias_forward below. */
 typedef enum { BRN_ATTN_BSHD = 0, BRN_ATTN_BHSD = 1 } brn_attn_layout;
 brn_status brn_flash_attention_forward(const float* q, const float* k, const float* v,
                                        int batch, int seq_q, int seq_kv, int heads, int head_dim,
                                        int layout, int causal, float scale,
                                        float* y, brn_mem loc, int device_ordinal, void* stream);
+/* flash_attention_with_bias / flash_attention_with_repeating_bias without the length limit of brn_attention_forward, and with their
+ * causal flag: brn_flash_attention_forward plus an additive bias,
+ *   y[b,h] = softmax_rows( scale * (q[b,h] k[b,h]^T + bias[b % n_bias, h])  [causal mask] ) v[b,h]
+ * (Swin windows of 16 / 24 = N 256 / 576, relative-position or ALiBi-style biases on LLM shapes, key-padding masks).
+ * bias: [n_bias, heads, seq_q, seq_kv] contiguous fp32, heads-major WHATEVER `layout` says for q / k / v / y (as MFA's bias is).  It is
+ * added to the UNSCALED scores (the convention of brn_attention_forward and of swin.rs:231-233).  n_bias 1 = one bias for every batch
+ * entry; n_bias > 1 with batch % n_bias == 0 = the repeating form; n_bias 0 with bias NULL runs the bias-free kernels and returns the
+ * bits of brn_flash_attention_forward.  q, k, v, y, layout, causal, scale, loc, the stream rules and the arithmetic by
+ * brn_set_op_compute are exactly those of brn_flash_attention_forward.  The bias stays fp32 in every mode: it joins the fp32 scores (as
+ * the initial accumulator of q k^T) and is never rounded to the 16-bit type; an all-zero bias returns the bits of the bias-free entry.
+ * A bias entry may be -inf: that key is excluded, it contributes exactly 0 to the row sum and to the output.  A row whose every visible
+ * key is -inf comes back NaN.  +inf and NaN entries give unspecified values in their own row and nothing worse: no address depends on a
+ * bias value.
+ * Limits (each violation is BRN_ERR_INVALID_ARG with the prefix "flash attention bias:" and a message naming the limit, checked before
+ * the device): every limit of brn_flash_attention_forward; n_bias >= 0; bias must be NULL exactly when n_bias == 0; batch % n_bias == 0;
+ * y overlaps neither an input nor the bias; a BRN_MEM_DEVICE bias is 16-byte aligned.
+ * The invariants of the bias-free entry hold: no split over keys, no atomics; an output row depends only on its own (batch entry, head)
+ * and its bias pattern; the bits depend neither on `batch` nor on the launch grid, and a repeated call repeats its bits.
+ * Not provided: a bias broadcast over heads; 16-bit bias storage; a causal mask with seq_q != seq_kv. */
+brn_status brn_flash_attention_bias_forward(const float* q, const float* k, const float* v,
+                                            int batch, int seq_q, int seq_kv, int heads, int head_dim,
+                                            int layout, int causal,
+                                            const float* bias, int n_bias, float scale,
+                                            float* y, brn_mem loc, int device_ordinal, void* stream);
 /* PatchMerging::forward (swin.rs:491-527): x [B,H*W,C] -> [B, ceil(H/2)*ceil(W/2), 2C]. */
 brn_status brn_patch_merging_forward(const float* x, int B, int H, int W, int C, const float* norm_g,
                                      const float* norm_b, const float* reduction_w, float* y, brn_mem loc,

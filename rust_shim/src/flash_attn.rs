@@ -1,6 +1,7 @@
 //! The three attention calls of the reference's `flash-attn` dependency over the library's two attention entry points: the narrow seam.
 //!
-//! `WindowAttention::forward` makes two of them behind its `flash-attn` feature (src/swin.rs:243, 252), served by `brn_attention_forward`.
+//! `WindowAttention::forward` makes two of them behind its `flash-attn` feature (src/swin.rs:243, 252), served by `brn_attention_forward`
+//! (N <= 144, head_dim 32, not causal: the Swin windows of 7 and 12) and by `brn_flash_attention_bias_forward` (everything else).
 //! A `hip` feature beside `flash-attn` at swin.rs:226-258 keeps candle's `WindowAttention` (qkv, cached_bias, mask, proj) and swaps only
 //! these calls:
 //!
@@ -8,7 +9,8 @@
 //!   use candle_birefnet_hip::flash_attn::{flash_attention_with_bias, flash_attention_with_repeating_bias};
 //!
 //! Same arguments, same pre-scaled bias (the bias is added to the UNSCALED scores, swin.rs:231-233), same `[batch, heads, N, head_dim]`
-//! result.  Limits are the library's (include/birefnet_hip.h): head_dim 32, N <= 144, no causal mask.
+//! result.  Limits are the library's (include/birefnet_hip.h): head_dim 32 / 64 / 128, N up to 65536 (windows of 16 and 24 are N = 256
+//! and 576), the `causal` flag honoured, -inf bias entries exclude their key; the bias is fp32, one slab per head (no broadcast over heads).
 //!
 //! The third is the plain `flash_attention(&q, &k, &v, causal)` of examples/bench_flash_attn.rs:39-53 on `[batch, seq, heads, head_dim]`
 //! tensors, served by `brn_flash_attention_forward`: head_dim 32 / 64 / 128, sequences up to 65536, q and k/v of different lengths, the
@@ -19,9 +21,6 @@ use crate::hip_ffi as ffi;
 
 /// y[b,h] = softmax(scale * (q k^T + bias[b % n_bias, h])) v, scale = head_dim^-0.5; tensors travel as host buffers
 fn attention(q: &Tensor, k: &Tensor, v: &Tensor, bias: &Tensor, n_bias: usize, causal: bool) -> Result<Tensor> {
-    if causal {
-        candle_core::bail!("flash attention on the hip backend has no causal mask (the reference always passes false, swin.rs:243, 252)")
-    }
     let (batch, heads, n, head_dim) = q.dims4()?;
     if k.dims4()? != (batch, heads, n, head_dim) || v.dims4()? != (batch, heads, n, head_dim) {
         candle_core::bail!("q, k and v must share the shape [batch, heads, N, head_dim]")
@@ -32,9 +31,16 @@ fn attention(q: &Tensor, k: &Tensor, v: &Tensor, bias: &Tensor, n_bias: usize, c
     }
     let (qh, kh, vh, bhost) = (ffi::to_host(q)?, ffi::to_host(k)?, ffi::to_host(v)?, ffi::to_host(bias)?);
     let mut out = vec![0f32; batch * heads * n * head_dim];
+    // the short op holds a whole score row in registers (the windows of 7 and 12); everything else walks K / V tiles with the bias beside them
     ffi::check(unsafe {
-        ffi::brn_attention_forward(qh.as_ptr(), kh.as_ptr(), vh.as_ptr(), batch as i32, heads as i32, n as i32, head_dim as i32, bhost.as_ptr(),
-                                   n_bias as i32, 0.0, out.as_mut_ptr(), ffi::BRN_MEM_HOST, 0, std::ptr::null_mut())
+        if n <= 144 && head_dim == 32 && !causal {
+            ffi::brn_attention_forward(qh.as_ptr(), kh.as_ptr(), vh.as_ptr(), batch as i32, heads as i32, n as i32, head_dim as i32, bhost.as_ptr(),
+                                       n_bias as i32, 0.0, out.as_mut_ptr(), ffi::BRN_MEM_HOST, 0, std::ptr::null_mut())
+        } else {
+            ffi::brn_flash_attention_bias_forward(qh.as_ptr(), kh.as_ptr(), vh.as_ptr(), batch as i32, n as i32, n as i32, heads as i32,
+                                                  head_dim as i32, ffi::BRN_ATTN_BHSD, causal as i32, bhost.as_ptr(), n_bias as i32, 0.0,
+                                                  out.as_mut_ptr(), ffi::BRN_MEM_HOST, 0, std::ptr::null_mut())
+        }
     })?;
     Tensor::from_vec(out, (batch, heads, n, head_dim), q.device())
 }

@@ -8,7 +8,14 @@ Beside each non-causal row, in the same process and on the same values, the unfu
 in torch — (q * scale) @ k^T, softmax over the last dim, @ v on [batch, heads, seq, head_dim] tensors — timed the same way; in the
 16-bit modes torch gets tensors of that dtype.  It is the yardstick the reference example itself uses (it has no causal form).
 
-  python tools/bench_flash_attention.py [--row N] [--mode f32|bf16|f16] [--json PATH]"""
+--bias times brn_flash_attention_bias_forward instead: per row, in the same process and on the same values, the bias-free call, the
+call with one standard-normal x sqrt(head_dim) bias for every batch entry (n_bias = 1, [1, heads, seq, seq] fp32) and torch's unfused
+attention with `+ bias` before the softmax (fp32 bias in every mode, as the fused call has it; non-causal rows only).  Two more rows, the
+Swin windows of 16 and 24 ((64, 256, 6, 32) and (16, 576, 6, 32)), come with it; they and the window-12 row also get the repeating
+form, n_bias = n_windows = batch.  Per record: ms with and without the bias, their difference, and that difference set against
+bias bytes / 8 TB/s — the share of the HBM roof the bias stream reaches (non-causal: every bias byte is read exactly once).
+
+  python tools/bench_flash_attention.py [--bias] [--row N] [--mode f32|bf16|f16] [--json PATH]"""
 import argparse
 import json
 import os
@@ -18,6 +25,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 ROWS = [(484, 144, 6, 32), (1, 144, 484 * 6, 32), (1, 512, 32, 128), (1, 1024, 32, 128), (1, 2048, 32, 128), (1, 4096, 32, 128),
         (1, 8192, 32, 128), (4, 2048, 8, 64)]                      # batch, seq, heads, head_dim
+BIAS_ROWS = ROWS + [(64, 256, 6, 32), (16, 576, 6, 32)]          # + Swin windows of 16 and 24 (Swin-384 / SwinV2 geometries)
+SWIN_ROWS = [(484, 144, 6, 32), (64, 256, 6, 32), (16, 576, 6, 32)]
+HBM_BYTES_PER_S = 8.0e12
 MODES = ["f32", "bf16", "f16"]
 WARMUP, TIMED = 5, 20
 
@@ -81,9 +91,66 @@ def bench(row, mode):
     return out
 
 
+def standard_attention_bias(q, k, v, bias):
+    """standard_attention with the bias of swin.rs:278-303, on the unscaled scores: softmax(scale * (q k^T + bias)) v"""
+    import torch
+    scale = 1.0 / (q.shape[-1] ** 0.5)
+    attn = ((q @ k.transpose(-2, -1)) + bias) * scale
+    attn = torch.softmax(attn, dim=-1)
+    return attn.to(v.dtype) @ v
+
+
+def bench_bias(row, mode):
+    import torch
+    from candle_birefnet_amd import ops
+    batch, seq, heads, hd = row
+    g = torch.Generator(device="cuda").manual_seed(1)
+    q, k, v = (torch.randn(batch, heads, seq, hd, device="cuda", generator=g) for _ in range(3))
+    qf, kf, vf = (a.transpose(1, 2).contiguous() for a in (q, k, v))
+    forms = [1] + ([batch] if row in SWIN_ROWS else [])
+    flop = 4.0 * batch * heads * seq * seq * hd
+    out = []
+    ops.set_compute(mode)
+    try:
+        for causal in (False, True):
+            free, _, _ = _time(lambda: ops.flash_attention(qf, kf, vf, causal=causal))
+            for n_bias in forms:
+                bias = torch.randn(n_bias, heads, seq, seq, device="cuda", generator=g) * hd ** 0.5
+                med, best, y = _time(lambda: ops.flash_attention(qf, kf, vf, causal=causal, bias=bias))
+                assert bool(torch.isfinite(y).all())
+                f = flop / 2 if causal else flop
+                nbytes = 4.0 * batch * heads * seq * seq               # every (batch entry, head) streams its own [seq, seq] slab once
+                roof = nbytes / HBM_BYTES_PER_S * 1e3
+                rec = {"batch": batch, "seq": seq, "heads": heads, "head_dim": hd, "mode": mode, "causal": int(causal), "n_bias": n_bias,
+                       "ms_bias_median": round(med, 4), "ms_bias_fastest": round(best, 4), "ms_free_median": round(free, 4),
+                       "ms_added": round(med - free, 4), "tflops_bias": round(f / med / 1e9, 2), "bias_stream_bytes": int(nbytes),
+                       "bias_roof_ms": None, "hbm_roof_share": None, "torch_bias_ms_median": None, "fused_not_slower_than_torch": None}
+                if not causal:
+                    rec["bias_roof_ms"] = round(roof, 4)
+                    rec["hbm_roof_share"] = round(roof / (med - free), 3) if med > free else None
+                    dt = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}[mode]
+                    qt, kt, vt = (a.to(dt) for a in (q, k, v))
+                    bt = bias if n_bias == 1 else bias.repeat(batch // n_bias, 1, 1, 1)
+                    tmed, _, yt = _time(lambda: standard_attention_bias(qt, kt, vt, bt))
+                    rec["torch_bias_ms_median"] = round(tmed, 4)
+                    rec["fused_not_slower_than_torch"] = bool(med <= tmed)
+                    rec["max_abs_diff_vs_torch"] = float((y.transpose(1, 2) - yt.float()).abs().max())
+                    del qt, kt, vt, yt, bt
+                out.append(rec)
+                print(f"{batch:4d} x {seq:5d} x {heads:4d} x {hd:3d} {mode:4s} causal {int(causal)} n_bias {n_bias:3d}: bias {med:9.4f} ms, free {free:9.4f} ms, "
+                      f"added {med - free:8.4f} ms" + (f" (bias bytes at 8 TB/s {roof:8.4f} ms)   | torch + bias {rec['torch_bias_ms_median']:9.4f} ms"
+                                                      f"{'' if rec['fused_not_slower_than_torch'] else '   SLOWER THAN TORCH'}" if not causal else ""), flush=True)
+                del bias, y
+    finally:
+        ops.set_compute("f32")
+    torch.cuda.empty_cache()
+    return out
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("--row", type=int, choices=range(len(ROWS)))
+    ap.add_argument("--bias", action="store_true", help="time brn_flash_attention_bias_forward beside the bias-free call and torch + bias")
+    ap.add_argument("--row", type=int, choices=range(len(BIAS_ROWS)))
     ap.add_argument("--mode", choices=MODES)
     ap.add_argument("--json", help="write the records to this file")
     a = ap.parse_args()
@@ -91,10 +158,13 @@ if __name__ == "__main__":
     if cb.device_count() < 1:
         sys.exit("no HIP device: nothing is measured")
     recs = []
-    for row in (ROWS if a.row is None else [ROWS[a.row]]):
+    rows = BIAS_ROWS if a.bias else ROWS
+    if a.row is not None and a.row >= len(rows):
+        sys.exit(f"--row {a.row}: only {len(rows)} rows without --bias")
+    for row in (rows if a.row is None else [rows[a.row]]):
         for mode in (MODES if a.mode is None else [a.mode]):
-            recs += bench(row, mode)
+            recs += bench_bias(row, mode) if a.bias else bench(row, mode)
     if a.json:
         with open(a.json, "w") as f:
-            json.dump({"tool": "tools/bench_flash_attention.py", "warmup": WARMUP, "timed": TIMED, "rows": recs}, f, indent=1)
+            json.dump({"tool": "tools/bench_flash_attention.py" + (" --bias" if a.bias else ""), "warmup": WARMUP, "timed": TIMED, "rows": recs}, f, indent=1)
             f.write("\n")
