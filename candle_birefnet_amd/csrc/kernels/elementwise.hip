@@ -37,6 +37,15 @@ template <> __device__ __forceinline__ void st4<_Float16>(_Float16* p, f32x4 v) 
     *reinterpret_cast<f16x4_e*>(p) = h;
 }
 
+// Keeps an fp32 result in its registers until st4 rounds it.  Left alone, hipcc folds the last fma of the 4-wide resize and the fp16
+// rounding into v_fma_mixlo/hi_f16 (one rounding), while the 16-byte form rounds the fp32 result (two roundings): the same map then
+// held different fp16 bits depending on the alignment of its window (tests/test_elementwise_kernels_gpu.py, both_kernels_agree).
+template <class T> __device__ __forceinline__ void keep_f32(f32x4&) {}
+template <> __device__ __forceinline__ void keep_f32<_Float16>(f32x4& v) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { float t = v[e]; asm("" : "+v"(t)); v[e] = t; }
+}
+
 static inline dim3 grid1d(size_t n, int block) {
     size_t g = (n + block - 1) / block;
     if (g > 65535u * 32u) g = 65535u * 32u;   // kernels grid-stride
@@ -79,6 +88,7 @@ __global__ void resize_nhwc_kernel(const T* __restrict__ x, int B, int Hin, int 
         f32x4 r = top + (bot - top) * ly;
         T* yp = y + (((size_t)b * Hout + oy) * Wout + ox) * ldy + y_coff + c4 * 4;
         if (ACC) r = ld4<T>(yp) + r;
+        keep_f32<T>(r);
         st4<T>(yp, r);
     }
 }
