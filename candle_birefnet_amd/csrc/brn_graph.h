@@ -58,6 +58,14 @@ inline void join_branches(Ctx& c, unsigned mask) {
         if (c.pending & mask & (1u << k)) BRN_HIP(hipStreamWaitEvent(c.stream, c.br->join_ev[k], 0));
     c.pending &= ~mask;
 }
+// ---- the generic window route (brn_window_generic.cpp) ---------------------------------------------------------------------
+// The attention of one map for a window side other than 12 and 7, between the qkv GEMM and the projection: qkv [B, H, W, 3C] -> att
+// [B, H, W, C] (both in the mode's storage type) as pack, bias build, flash attention with bias, scatter.  It lives outside the graph
+// files, which link against nothing but the launches of their own (tests/test_graph_trace_cpu.py), and registers itself here when the
+// library is loaded; null = not linked in.  Allocates from c.arena and releases to its own mark; in a dry run it only allocates.
+using WindowGenericRoute = void (*)(Ctx& c, const SwinBlockW& blk, const float* qkv, float* att, int B, int H, int W, int C, int window, int shift);
+extern WindowGenericRoute g_window_generic_route;      // defined in brn_graph_swin.cpp
+
 constexpr int AUX_IPT = 3, AUX_LAT = 4;
 constexpr unsigned AUX_ASPP_MASK = 7u;
 struct ArenaHold { Arena& a; explicit ArenaHold(Arena& a_) : a(a_) { ++a.hold; } ~ArenaHold() { --a.hold; } };

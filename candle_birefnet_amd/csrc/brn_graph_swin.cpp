@@ -4,6 +4,8 @@
 
 namespace brn {
 
+WindowGenericRoute g_window_generic_route = nullptr;    // set by brn_window_generic.cpp's registrar (brn_graph.h)
+
 void swin_stage_dims(int H, int W, int patch, int hs[4], int ws[4]) {
     int h = (H + patch - 1) / patch, w = (W + patch - 1) / patch;   // PatchEmbed pads to a multiple (swin.rs:696-702)
     for (int i = 0; i < 4; ++i) {
@@ -25,7 +27,17 @@ static bool swin_attention_multi(Ctx& c, const SwinBlockW& blk, const float* xn,
     const int ldp = p2 ? C * p2 / 2 : C;                                // row stride (floats) of a P-layout [M][C] buffer
     float* att = c.act_alloc((size_t)M * ldp);
     run_gemm(c, blk.qkv, GemmIO(xn, M, ldp).to(qkv, 3 * C).planes(p2, 0));   // swin.rs:217 (pad rows are synthesised by the kernel)
-    if (!c.dry) {
+    if (window != 12 && window != 7) {
+        // no fused kernel for this window side: the generic route, map by map (it plans its own buffers, so it runs in a dry run too).
+        // stage_pl needs window 12, so qkv and att are plain matrices here
+        if (p2) fail(BRN_ERR_INVALID_ARG, "window_size %d: the generic window route takes no plane layout", window);
+        if (!g_window_generic_route) fail(BRN_ERR_INVALID_ARG, "window_size %d needs the generic window route", window);
+        size_t off = 0;
+        for (int k = 0; k < nin; ++k) {
+            g_window_generic_route(c, blk, c.at(qkv, off * 3 * C), c.at(att, off * C), B, hs[k], wsz[k], C, window, shift);
+            off += (size_t)B * hs[k] * wsz[k];
+        }
+    } else if (!c.dry) {
         // one launch for all maps of the pass (full + half scale): fewer ramps and tails than one launch per geometry
         WindowAttnParams ps[2]{};
         size_t off = 0;

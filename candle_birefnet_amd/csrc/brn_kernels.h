@@ -191,6 +191,24 @@ struct FlashAttentionParams {
 };
 hipError_t launch_flash_attention(const FlashAttentionParams& p, hipStream_t s);
 
+// the index kernels of the generic window route (kernels/window_generic.hip; geometry: kernels/window_generic_geometry.h), window sides
+// 2 .. 32 other than the fused kernels' 12 and 7.  One struct for the three; each launcher reads the fields its kernel needs
+struct WindowGenericParams {
+    int B, H, W, C, heads;   // token map [B, H, W, C], C == heads * 32
+    int ws, shift;           // window side; 0 or ws / 2
+    int s16;                 // storage type of qkv and att: 0 fp32, 1 bf16, 2 fp16
+    // window_pack: qkv [B, H, W, 3C] (storage type) -> q, k, v [slots, heads, ws^2, 32] fp32; pad positions from qkv_bias [3C]
+    const float* qkv; const float* qkv_bias;
+    float* q; float* k; float* v;
+    // window_bias_build: rel_table [heads][(2 ws - 1)^2] -> bias [wgen_bias_patterns, heads, ws^2, ws^2] fp32, pre-divided by scale
+    const float* rel_table; float* bias; float scale;
+    // window_scatter: y [slots, heads, ws^2, 32] fp32 -> att [B, H, W, ld_att] (storage type), heads-major in the first C columns
+    const float* y; float* att; int ld_att;
+};
+hipError_t launch_window_pack(const WindowGenericParams& p, hipStream_t s);
+hipError_t launch_window_bias_build(const WindowGenericParams& p, hipStream_t s);
+hipError_t launch_window_scatter(const WindowGenericParams& p, hipStream_t s);
+
 // ---- data movement / elementwise (HBM-bound) ------------------------------------------------------------
 // bilinear, align_corners=true, channels-last window -> window; optional accumulate (y += )
 hipError_t launch_resize_nhwc(const float* x, int B, int Hin, int Win, int C, int ldx, int x_coff,

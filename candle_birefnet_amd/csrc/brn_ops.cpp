@@ -208,8 +208,10 @@ brn_status brn_window_attention_forward(const float* x, int B, int H, int W, int
                                         const float* rel_table, float* y, brn_mem loc, int device, void* stream) {
     return guarded([&] {
         if (!x || !qkv_w || !qkv_b || !proj_w || !proj_b || !rel_table || !y) fail(BRN_ERR_INVALID_ARG, "null argument");
-        if (!(window_size == 12 || window_size == 7) || heads < 1 || C != heads * 32 || !(shift == 0 || shift == window_size / 2))
-            fail(BRN_ERR_INVALID_ARG, "window attention needs window_size 12 or 7, head_dim 32, shift 0 or window_size / 2");
+        if (window_size < 2 || window_size > 32) fail(BRN_ERR_INVALID_ARG, "window attention: window_size %d unsupported (2 <= window_size <= 32)", window_size);
+        if (!(shift == 0 || shift == window_size / 2))
+            fail(BRN_ERR_INVALID_ARG, "window attention: shift %d unsupported (shift must be 0 or window_size / 2 = %d; 2 <= window_size <= 32)", shift, window_size / 2);
+        if (B < 1 || H < 1 || W < 1 || heads < 1 || C != heads * 32) fail(BRN_ERR_INVALID_ARG, "window attention needs B, H, W >= 1 and head_dim 32 (C == heads * 32)");
         ensure_device(device);
         DeviceOwner own;
         // reuse the model's weight builder through a one-block table

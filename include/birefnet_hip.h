@@ -195,9 +195,12 @@ brn_status brn_model_last_kernel_stats(brn_model* m, int n, int* launches, float
 const char* brn_kernel_family_name(int f);
 
 /* ---- stand-alone SwinTransformer: SwinTransformer::new / forward (swin.rs:725-797) -------------------- */
-/* Any SwinConfig (swin_t / swin_s / swin_b / swin_l: window 7 or 12) and any input size.  The handle is built for the arithmetic that
- * brn_set_op_compute selected on the creating thread (default BRN_F32): window 12 uses the mode's own attention kernel, window 7 the
- * fp32-MFMA attention kernel in every mode (on bf16 matrices in mode BRN_BF16). */
+/* Any SwinConfig (swin_t / swin_s / swin_b / swin_l, or one of these with another window_size, 2 .. 32; head_dim 32) and any input size.
+ * The handle is built for the arithmetic that brn_set_op_compute selected on the creating thread (default BRN_F32): window 12 uses the
+ * mode's own attention kernel, window 7 the fp32-MFMA attention kernel in every mode (on bf16 matrices in mode BRN_BF16), every other
+ * window_size the generic route of brn_window_attention_forward (pack, flash attention with bias, scatter).  The same range holds for
+ * the window_size of brn_model_create, brn_model_create_from_safetensors and brn_decoder_create; outside it they answer
+ * BRN_ERR_INVALID_ARG with a message naming window_size and the range. */
 brn_status brn_swin_create(const brn_config* cfg /* swin_* fields */, const brn_named_tensor* weights,
                            size_t n_weights, const char* prefix, int device_ordinal, brn_swin** out);
 void brn_swin_destroy(brn_swin* s);
@@ -240,8 +243,18 @@ brn_status brn_upsample_bilinear2d(const float* x, int B, int C, int H, int W, i
  * pad -> roll(-shift) -> window_partition -> WindowAttention::forward (qkv, q*scale, q@k^T + rel-pos bias
  * (+ SW-MSA mask), softmax, @v, proj) -> window_reverse -> roll(+shift) -> crop.
  * x [B,H,W,C] is the norm1 output; y [B,H,W,C].  rel_table is relative_position_bias_table [(2ws-1)^2, heads].
- * head_dim must be 32; window_size 12 (Swin-B / L, swin.rs:55-80; every compute mode) or 7 (Swin-T / S, swin.rs:27-52); shift 0 or
- * window_size / 2. */
+ * head_dim must be 32; 2 <= window_size <= 32; shift 0 or window_size / 2 (anything else is BRN_ERR_INVALID_ARG with a message naming
+ * window_size and the range).
+ * window_size 12 (Swin-B / L, swin.rs:55-80) runs the mode's own fused attention kernel and 7 (Swin-T / S, swin.rs:27-52) the fused
+ * fp32-MFMA kernel, exactly as before the wider range existed.  Every other window_size takes the generic route: qkv GEMM -> pack (roll,
+ * pad and partition as index math, q / k / v to [windows, heads, N, 32]) -> the kernel of brn_flash_attention_bias_forward with the
+ * relative-position bias (+ the -100 region mask of swin.rs:603-655 for the windows of the last window row / column, the only ones whose
+ * mask is not zero) pre-divided by the scale -> scatter (window reverse, roll back, crop) -> proj GEMM.  The reference's semantics hold
+ * on that route: the map is padded after norm1, so a pad token's q / k / v is the qkv bias (rounded to the 16-bit type in BRN_BF16 /
+ * BRN_F16) and it takes part as a key; shift 0 has no mask even on a padded canvas; a map smaller than the window is one padded window.
+ * Its attention arithmetic is that of brn_flash_attention_bias_forward in the same compute mode: one exact fp32 kernel for BRN_F32 and
+ * the three plane modes (so these differ only by their two GEMMs), the 16-bit kernel for BRN_BF16 / BRN_F16.  A repeated call repeats
+ * its bits. */
 brn_status brn_window_attention_forward(const float* x, int B, int H, int W, int C, int heads, int window_size,
                                         int shift, const float* qkv_w, const float* qkv_b,
                                         const float* proj_w, const float* proj_b, const float* rel_table,

@@ -11,6 +11,7 @@
 //! Same arguments, same pre-scaled bias (the bias is added to the UNSCALED scores, swin.rs:231-233), same `[batch, heads, N, head_dim]`
 //! result.  Limits are the library's (include/birefnet_hip.h): head_dim 32 / 64 / 128, N up to 65536 (windows of 16 and 24 are N = 256
 //! and 576), the `causal` flag honoured, -inf bias entries exclude their key; the bias is fp32, one slab per head (no broadcast over heads).
+//! (A whole Swin block with such a window needs no seam: `crate::swin` and `brn_window_attention_forward` take window_size 2 ..= 32.)
 //!
 //! The third is the plain `flash_attention(&q, &k, &v, causal)` of examples/bench_flash_attn.rs:39-53 on `[batch, seq, heads, head_dim]`
 //! tensors, served by `brn_flash_attention_forward`: head_dim 32 / 64 / 128, sequences up to 65536, q and k/v of different lengths, the

@@ -4,7 +4,10 @@ use candle_nn::VarBuilder;
 
 use crate::hip_ffi as ffi;
 
-/// Configuration for Swin Transformer — the reference's struct, field for field (swin.rs:14-23)
+/// Configuration for Swin Transformer — the reference's struct, field for field (swin.rs:14-23).
+/// `window_size` is a free field there and here: the library takes 2 ..= 32 (head_dim 32).  12 and 7 run fused attention kernels, every
+/// other side the generic route (pack -> flash attention with bias -> scatter); outside the range `SwinTransformer::new` is an `Err`
+/// naming `window_size` and the range.
 #[derive(Clone, Debug)]
 pub struct SwinConfig {
     pub embed_dim: usize,
