@@ -118,6 +118,18 @@ ComputeMode compute_mode(int dt);
 void run_model(Model* m, const float* x, int B, int H, int W, brn_mem in_loc, float* out, brn_mem out_loc, void* stream, int apply_sigmoid);
 void swin_entry(const SwinW& w, int device, const float* x, int B, int H, int W, brn_mem in_loc, float* const outs[4], brn_mem out_loc,
                 void* stream, int bf16 = 0);
+
+// brn_deform_offsets.cpp, behind brn_deform_conv2d_offsets_forward (brn_ops.cpp) alone: the weight of the route the geometry selects, then
+// the route between the channels-last map X [B, H, W, Cp] and Y [B, Ho, Wo, O] (both in the storage type s16) inside the entry's arena
+struct DeformOffsetsPlan {
+    DeformOffsetsParams geo;       // geometry and the device pointers of offset / mask (x, col, om: filled by the route)
+    bool fused = false;            // route 1 (gather loaders) or route 2 (column matrix + dense GEMM)
+    int Cp = 0, s16 = 0;           // channels of X (granule-padded); storage type of X and Y (Ctx::bf16)
+    GemmW g;                       // fused: a GEMM_DEFORM_NHWC conv weight; columns: the dense [O][kh kw Cp] weight
+};
+bool deform_offsets_fused_eligible(const DeformOffsetsParams& a);
+DeformOffsetsPlan deform_offsets_prepare(DeviceOwner& own, WeightBuild op, const DeformOffsetsParams& a, const float* w, const float* bias, int O);
+void deform_offsets_route(Ctx& c, const DeformOffsetsPlan& pl, const Map& X, const Map& Y);
 }  // namespace brn
 
 struct brn_model { brn::Model m; };

@@ -111,7 +111,8 @@ static inline int roundup(int x, int m) { return (x + m - 1) / m * m; }
     X(deform_f32,       "BRN_DEFORM_F32_KERNEL", 0,  "1 = the 16-bit modes run deformable convolutions on the fp32-MFMA gather kernel")        \
     X(planes_kernel,    "BRN_PLANES_KERNEL",     0,  "1 = split modes with P-layout A on the LDS-DMA plane kernel (diag build only)")           \
     X(conv_chunk_major, "BRN_CONV_CHUNK_MAJOR",  1,  "0 = tap-major K order of the 16-bit implicit-GEMM conv weights (read when weights are packed)") \
-    X(offmod_pad8,      "BRN_OFFMOD_PAD8",       1,  "0 = the offset / modulator conv's N padded to 4 instead of 8")
+    X(offmod_pad8,      "BRN_OFFMOD_PAD8",       1,  "0 = the offset / modulator conv's N padded to 4 instead of 8")                         \
+    X(deform_col_mb,    "BRN_DEFORM_COL_MB",     256, "MiB the column matrix of brn_deform_conv2d_offsets_forward's column route may take (never below 64 rows)")
 struct Switches {
 #define BRN_X(field, name, dflt, doc) int field = dflt;
     BRN_SWITCHES(BRN_X)

@@ -209,6 +209,25 @@ hipError_t launch_window_pack(const WindowGenericParams& p, hipStream_t s);
 hipError_t launch_window_bias_build(const WindowGenericParams& p, hipStream_t s);
 hipError_t launch_window_scatter(const WindowGenericParams& p, hipStream_t s);
 
+// the two kernels of brn_deform_conv2d_offsets_forward (kernels/deform_im2col.hip; geometry: kernels/deform_sample_geometry.h; host route:
+// brn_deform_offsets.cpp).  One struct for both; each launcher reads the fields its kernel needs
+struct DeformOffsetsParams {
+    int B, C, H, W;                  // the sampled map: C real channels
+    int kh, kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w;
+    int G;                           // offset groups: channel c reads the offsets / mask of group c / (C / G)
+    int Ho, Wo;
+    const float* offset;             // [B, 2 G kh kw, Ho, Wo] fp32 (dy, dx interleaved per (group, tap))
+    const float* mask;               // [B, G kh kw, Ho, Wo] fp32, or null = no modulation
+    // deform_om_pack (G == 1): -> om [B, Ho, Wo, om_ld] fp32 = 2 kh kw offsets | kh kw multipliers (1.0f without a mask) | zero pad columns
+    float* om; int om_ld;
+    // deform_im2col: x [B, H, W, ldx] channels-last in the storage type s16 (0 fp32, 1 bf16, 2 fp16), Cp >= C channels a pixel (multiple of 32,
+    // the pad channels are never read) -> col [rows][kh kw Cp] in the same type = rows [m0, m0 + rows) of the column matrix, K = (tap, channel)
+    const float* x; int ldx, Cp, s16;
+    float* col; int m0, rows;
+};
+hipError_t launch_deform_om_pack(const DeformOffsetsParams& p, hipStream_t s);
+hipError_t launch_deform_im2col(const DeformOffsetsParams& p, hipStream_t s);
+
 // ---- data movement / elementwise (HBM-bound) ------------------------------------------------------------
 // bilinear, align_corners=true, channels-last window -> window; optional accumulate (y += )
 hipError_t launch_resize_nhwc(const float* x, int B, int Hin, int Win, int C, int ldx, int x_coff,

@@ -2,6 +2,7 @@
 // weights per call, in the arithmetic brn_set_op_compute selected on the calling thread.  Weights are always host pointers; x / y /
 // residual follow `loc`.
 #include "brn_api_util.h"
+#include "kernels/deform_sample_geometry.h"
 #include <cmath>
 #include <cstring>
 #include <memory>
@@ -454,6 +455,63 @@ brn_status brn_deform_conv2d_forward(const float* x, int B, int C, int H, int W,
             if (!c.dry && !fused_sig) BRN_HIP(launch_mod_sigmoid2(OM.p, (size_t)B * Ho * Wo, ldom, 2 * kk, 3 * kk, c.stream));
             run_conv(c, reg, X, Y, ConvOpts().offsets(OM, 2 * kk, fused_sig));
         });
+        st.finish();
+    });
+}
+
+// whether the product of the (positive) factors stays below 2^31, without overflowing on the way
+static bool count_below_2_31(std::initializer_list<long long> factors) {
+    long long n = 1;
+    for (long long f : factors) {
+        if (f < 1 || f > 0x7fffffffLL) return false;
+        n *= f;
+        if (n > 0x7fffffffLL) return false;
+    }
+    return true;
+}
+
+brn_status brn_deform_conv2d_offsets_forward(const float* x, int B, int C, int H, int W, const float* offset, const float* mask, const float* w,
+                                             const float* bias, int O, int kh, int kw, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h,
+                                             int dil_w, int offset_groups, float* y, brn_mem loc, int device, void* stream) {
+    return guarded([&] {
+        const char* who = "deform conv offsets";
+        const int G = offset_groups;
+        // every refusal before the device
+        if (!x || !offset || !w || !y) fail(BRN_ERR_INVALID_ARG, "%s: null x, offset, w or y (only mask and bias may be NULL)", who);
+        if (B < 1 || C < 1 || H < 1 || W < 1 || O < 1 || kh < 1 || kw < 1)
+            fail(BRN_ERR_INVALID_ARG, "%s: B %d, C %d, H %d, W %d, O %d, kh %d, kw %d unsupported (every size >= 1)", who, B, C, H, W, O, kh, kw);
+        if (stride_h < 1 || stride_w < 1) fail(BRN_ERR_INVALID_ARG, "%s: stride (%d, %d) unsupported (stride_h, stride_w >= 1)", who, stride_h, stride_w);
+        if (dil_h < 1 || dil_w < 1) fail(BRN_ERR_INVALID_ARG, "%s: dilation (%d, %d) unsupported (dil_h, dil_w >= 1)", who, dil_h, dil_w);
+        if (pad_h < 0 || pad_w < 0) fail(BRN_ERR_INVALID_ARG, "%s: padding (%d, %d) unsupported (pad_h, pad_w >= 0)", who, pad_h, pad_w);
+        if (G < 1 || C % G) fail(BRN_ERR_INVALID_ARG, "%s: offset_groups %d unsupported with C %d (offset_groups >= 1, C %% offset_groups == 0)", who, G, C);
+        if ((long long)H + 2LL * pad_h > 0x7fffffffLL || (long long)W + 2LL * pad_w > 0x7fffffffLL)
+            fail(BRN_ERR_INVALID_ARG, "%s: padded map too large (H + 2 pad_h, W + 2 pad_w < 2^31)", who);
+        const long long Ho = deform_out_size(H, kh, stride_h, pad_h, dil_h), Wo = deform_out_size(W, kw, stride_w, pad_w, dil_w);
+        if (Ho < 1 || Wo < 1)
+            fail(BRN_ERR_INVALID_ARG, "%s: empty output, Ho %lld, Wo %lld (Ho, Wo >= 1: the dilated kernel must fit the padded map)", who, Ho, Wo);
+        if (!count_below_2_31({B, Ho, Wo})) fail(BRN_ERR_INVALID_ARG, "%s: too many output pixels (B * Ho * Wo < 2^31)", who);
+        if (!count_below_2_31({B, C, H, W})) fail(BRN_ERR_INVALID_ARG, "%s: x too large (B * C * H * W < 2^31 elements)", who);
+        if (!count_below_2_31({B, 2, G, kh, kw, Ho, Wo})) fail(BRN_ERR_INVALID_ARG, "%s: offset too large (B * 2 * G * kh * kw * Ho * Wo < 2^31 elements)", who);
+        if (!count_below_2_31({O, C, kh, kw}) || !count_below_2_31({kh, kw, (long long)C + 63}))
+            fail(BRN_ERR_INVALID_ARG, "%s: w too large (O * C * kh * kw and kh * kw * (C + 63) < 2^31 elements)", who);
+        if (!count_below_2_31({B, O, Ho, Wo})) fail(BRN_ERR_INVALID_ARG, "%s: y too large (B * O * Ho * Wo < 2^31 elements)", who);
+        const int taps = kh * kw, ho = (int)Ho, wo = (int)Wo;
+        const size_t nx = (size_t)B * C * H * W, noff = (size_t)B * 2 * G * taps * ho * wo, nmask = noff / 2, ny = (size_t)B * O * ho * wo;
+        if (floats_overlap(x, nx, y, ny) || floats_overlap(offset, noff, y, ny) || floats_overlap(mask, nmask, y, ny) ||
+            (loc == BRN_MEM_HOST && (floats_overlap(w, (size_t)O * C * taps, y, ny) || floats_overlap(bias, (size_t)O, y, ny))))
+            fail(BRN_ERR_INVALID_ARG, "%s: y must not overlap an input", who);
+        ensure_device(device);
+        DeformOffsetsParams a{};
+        a.B = B; a.C = C; a.H = H; a.W = W; a.kh = kh; a.kw = kw; a.stride_h = stride_h; a.stride_w = stride_w; a.pad_h = pad_h; a.pad_w = pad_w;
+        a.dil_h = dil_h; a.dil_w = dil_w; a.G = G; a.Ho = ho; a.Wo = wo;
+        DeviceOwner own;
+        DeformOffsetsPlan plan = deform_offsets_prepare(own, g_op, a, w, bias, O);
+        Staging st(stream, loc);
+        const float* dx = st.in(x, nx);
+        plan.geo.offset = st.in(offset, noff);
+        plan.geo.mask = mask ? st.in(mask, nmask) : nullptr;
+        float* dy = st.out(y, ny);
+        through_nhwc(stream, plan.s16, dx, B, C, plan.Cp, H, W, dy, O, ho, wo, [&](Ctx& c, const Map& X, const Map& Y) { deform_offsets_route(c, plan, X, Y); });
         st.finish();
     });
 }

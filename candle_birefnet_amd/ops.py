@@ -171,6 +171,40 @@ def patch_merging(x, H, W, norm_g, norm_b, reduction_w, device=0):
     return y
 
 
+def _pair(v):
+    return (int(v), int(v)) if isinstance(v, int) else (int(v[0]), int(v[1]))
+
+
+def deform_conv2d(x, offset, weight, bias=None, stride=(1, 1), padding=(0, 0), dilation=(1, 1), mask=None, device=0):
+    """torchvision.ops.deform_conv2d's signature over brn_deform_conv2d_offsets_forward (the reference's DeformConv2dConfig,
+    deform_conv.rs:120-132): x [B,C,H,W], offset [B, 2*G*kh*kw, Ho, Wo] (the caller's, dy / dx interleaved per (group, tap)), weight
+    [O,C,kh,kw], mask [B, G*kh*kw, Ho, Wo] or None (no modulation) -> [B,O,Ho,Wo].  stride / padding / dilation: an int or a (h, w) pair.
+    The number of offset groups G is inferred from offset.shape[1].  The limits are the library's (include/birefnet_hip.h)."""
+    B, Cc, H, W = (int(v) for v in x.shape)
+    O, Ci, kh, kw = (int(v) for v in weight.shape)
+    if Ci != Cc:
+        raise ValueError("channel mismatch (weight groups are not provided)")
+    (sh, sw), (ph, pw), (dh, dw) = _pair(stride), _pair(padding), _pair(dilation)
+    oc = int(offset.shape[1])
+    if oc < 2 * kh * kw or oc % (2 * kh * kw):
+        raise ValueError(f"offset has {oc} channels: not a multiple of 2 * kh * kw = {2 * kh * kw}")
+    G = oc // (2 * kh * kw)
+    Ho, Wo = int(offset.shape[2]), int(offset.shape[3])
+    px, loc, keep, _ = T.as_arg(x)
+    po, oloc, okeep, _ = T.as_arg(offset, (B, oc, Ho, Wo))
+    pm, mloc, mkeep, _ = T.as_arg(mask, (B, G * kh * kw, Ho, Wo)) if mask is not None else (None, loc, None, None)
+    if not (oloc == mloc == loc):
+        raise ValueError("x, offset and mask must live on the same side")
+    if Ho != (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1 or Wo != (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1:
+        raise ValueError(f"offset is {Ho} x {Wo}: not the output size of this geometry")
+    pw_, k1 = T.host_ptr(weight)
+    pb, k2 = T.host_ptr(bias)
+    y = T.alloc_like(keep, (B, O, Ho, Wo))
+    _ffi.check(_ffi.lib.brn_deform_conv2d_offsets_forward(px, B, Cc, H, W, po, pm, pw_, pb, O, kh, kw, sh, sw, ph, pw, dh, dw, G, T.ptr_of(y), loc,
+                                                          T.device_of(keep, device), T.stream_of(keep)))
+    return y
+
+
 def aspp_deformable(x, tensors, mode="reference_cpu", prefix="", out_channels=None, device=0):
     """ASPPDeformable::new(in_channels, out_channels, vb.pp(prefix)) + forward (aspp.rs:236-333) on an NCHW map; `tensors`: name -> host
     array of the module's weights under `prefix` (SURVEY.md App. A <ASPP>; BasicDecBlk builds it with 64 -> 64).  mode: "reference_cpu"

@@ -348,6 +348,33 @@ brn_status brn_deform_conv2d_forward(const float* x, int B, int C, int H, int W,
                                      const float* mod_w, const float* mod_b,
                                      const float* w, const float* bias, int O, int k, int stride, int pad,
                                      int mode, float* y, brn_mem loc, int device_ordinal, void* stream);
+/* The deformable convolution itself, with the CALLER's offsets and mask: torchvision deform_conv2d semantics, the operation
+ * the reference configures through DeformConv2dConfig::new (deform_conv.rs:120-132) and runs as call_deformable_im2col + matmul
+ * (deform_conv.rs:101-215, aspp.rs:58-165).  brn_deform_conv2d_forward is the layer around it (offsets and modulator from its own two convs,
+ * square kernel, one stride / pad, dilation 1, one offset group, always a mask); this entry takes every parameter of the config.
+ *   x [B,C,H,W], offset [B, 2*G*kh*kw, Ho, Wo], mask [B, G*kh*kw, Ho, Wo] or NULL (no modulation: DCNv1, use_mask false), y [B,O,Ho,Wo]
+ *   live where `loc` says; w [O,C,kh,kw] and bias [O] (or NULL) are host pointers.  G = offset_groups.
+ *   Ho = (H + 2 pad_h - dil_h (kh - 1) - 1) / stride_h + 1, Wo likewise.
+ *   Offset channel 2 (g kh kw + t) is dy and the next one dx of tap t = ky kw + kx; input channel c belongs to group c / (C / G).
+ *   Output pixel (oy, ox) samples at (oy stride_h - pad_h + ky dil_h + dy, ox stride_w - pad_w + kx dil_w + dx): bilinear from the floor,
+ *   zero unless the point lies in (-1, H) x (-1, W), corners outside the image contribute zero.  The mask is the multiplier itself (no
+ *   sigmoid is applied).  An infinite, NaN or huge offset makes its sample contribute 0 or NaN and nothing else: no address depends on it.
+ * Arithmetic by brn_set_op_compute, like brn_deform_conv2d_forward: the blend mask x bilinear is fp32 in every mode, the product with w
+ * runs on the mode's matrix path (in BRN_BF16 / BRN_F16 x and w are rounded to the 16-bit type); offsets and mask stay fp32 in every mode.
+ * Two routes, chosen by the geometry alone: with G == 1 and equal stride, pad and dilation on both axes the gather kernels the layer
+ * uses (given the layer's offsets as a tensor and no mask where its modulator is 1, the layer's bits); everything else as a column
+ * matrix (bounded by BRN_DEFORM_COL_MB MiB, walked in chunks of rows) times the mode's dense GEMM.
+ * Limits (each violation is BRN_ERR_INVALID_ARG with the prefix "deform conv offsets:" and a message naming the limit, checked before
+ * the device): x, offset, w, y non-NULL; every size, stride and dilation >= 1, pads >= 0; G >= 1 and C % G == 0; H + 2 pad_h and
+ * W + 2 pad_w < 2^31; Ho, Wo >= 1; B * Ho * Wo and every buffer's element count < 2^31; y overlaps no input.
+ * Not provided: weight groups (torchvision's `groups`; the reference multiplies the columns by one [O, C kh kw] weight, deform_conv.rs:101-215),
+ * 16-bit tensors at the boundary, a backward pass. */
+brn_status brn_deform_conv2d_offsets_forward(const float* x, int B, int C, int H, int W,
+                                             const float* offset, const float* mask,
+                                             const float* w, const float* bias, int O, int kh, int kw,
+                                             int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w,
+                                             int offset_groups,
+                                             float* y, brn_mem loc, int device_ordinal, void* stream);
 
 /* ASPPDeformable::new(in_channels, out_channels, vb.pp(prefix)) + forward (aspp.rs:236-333; BasicDecBlk builds it with
  * (64, None), decoder.rs:107-111): five branches on the map (aspp1 and aspp_deforms.{0,1,2} = DeformConvASPP k 1,1,3,7 -> 256, BN, ReLU;

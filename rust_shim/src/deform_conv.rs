@@ -71,6 +71,43 @@ impl DeformableConv2d {
     }
 }
 
+/// The deformable convolution with the caller's offsets and mask (`brn_deform_conv2d_offsets_forward`): torchvision `deform_conv2d`
+/// semantics, every parameter `DeformConv2dConfig::new` carries (deform_conv.rs:120-132) — per-axis stride, padding and dilation,
+/// offset groups (inferred from `offset`'s channel count), `mask: None` = `use_mask` false.  x [B, C, H, W], offset
+/// [B, 2 G kh kw, Ho, Wo], mask [B, G kh kw, Ho, Wo], weight [O, C, kh, kw], bias [O] -> [B, O, Ho, Wo].
+pub fn deform_conv2d(x: &Tensor, offset: &Tensor, weight: &Tensor, bias: Option<&Tensor>, stride: (usize, usize), padding: (usize, usize),
+                     dilation: (usize, usize), mask: Option<&Tensor>) -> Result<Tensor> {
+    let (b, c, h, w) = x.dims4()?;
+    let (o, ci, kh, kw) = weight.dims4()?;
+    if ci != c {
+        candle_core::bail!("expected a weight over {c} input channels, got {ci} (weight groups are not provided)")
+    }
+    let (ob, oc, ho, wo) = offset.dims4()?;
+    if ob != b || oc == 0 || oc % (2 * kh * kw) != 0 {
+        candle_core::bail!("offset [{ob}, {oc}, {ho}, {wo}] does not fit batch {b} and a {kh} x {kw} kernel")
+    }
+    let g = oc / (2 * kh * kw);
+    if let Some(m) = mask {
+        if m.dims4()? != (b, g * kh * kw, ho, wo) {
+            candle_core::bail!("mask shape {:?} is not [{b}, {}, {ho}, {wo}]", m.dims(), g * kh * kw)
+        }
+    }
+    let xin = ffi::to_host(x)?;
+    let off = ffi::to_host(offset)?;
+    let wgt = ffi::to_host(weight)?;
+    let msk = match mask { Some(m) => Some(ffi::to_host(m)?), None => None };
+    let bs = match bias { Some(t) => Some(ffi::to_host(t)?), None => None };
+    let mut out = vec![0f32; b * o * ho * wo];
+    ffi::check(unsafe {
+        ffi::brn_deform_conv2d_offsets_forward(xin.as_ptr(), b as i32, c as i32, h as i32, w as i32, off.as_ptr(),
+                                               msk.as_ref().map_or(std::ptr::null(), |v| v.as_ptr()), wgt.as_ptr(),
+                                               bs.as_ref().map_or(std::ptr::null(), |v| v.as_ptr()), o as i32, kh as i32, kw as i32, stride.0 as i32,
+                                               stride.1 as i32, padding.0 as i32, padding.1 as i32, dilation.0 as i32, dilation.1 as i32, g as i32,
+                                               out.as_mut_ptr(), ffi::BRN_MEM_HOST, 0, std::ptr::null_mut())
+    })?;
+    Tensor::from_vec(out, (b, o, ho, wo), x.device())
+}
+
 /// deform_conv.rs:218-222
 impl Module for DeformableConv2d {
     fn forward(&self, x: &Tensor) -> Result<Tensor> {

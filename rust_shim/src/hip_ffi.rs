@@ -137,6 +137,11 @@ extern "C" {
                                      offset_b: *const c_float, mod_w: *const c_float, mod_b: *const c_float, wgt: *const c_float,
                                      bias: *const c_float, o: c_int, k: c_int, stride: c_int, pad: c_int, mode: c_int, y: *mut c_float,
                                      loc: c_int, device_ordinal: c_int, stream: *mut c_void) -> c_int;
+    pub fn brn_deform_conv2d_offsets_forward(x: *const c_float, b: c_int, c: c_int, h: c_int, w: c_int, offset: *const c_float,
+                                             mask: *const c_float, wgt: *const c_float, bias: *const c_float, o: c_int, kh: c_int, kw: c_int,
+                                             stride_h: c_int, stride_w: c_int, pad_h: c_int, pad_w: c_int, dil_h: c_int, dil_w: c_int,
+                                             offset_groups: c_int, y: *mut c_float, loc: c_int, device_ordinal: c_int,
+                                             stream: *mut c_void) -> c_int;
     pub fn brn_aspp_deformable_forward(weights: *const BrnNamedTensor, n_weights: usize, prefix: *const c_char, in_channels: c_int,
                                        out_channels: c_int, mode: c_int, x: *const c_float, b: c_int, h: c_int, w: c_int, y: *mut c_float,
                                        loc: c_int, device_ordinal: c_int, stream: *mut c_void) -> c_int;
