@@ -72,7 +72,7 @@ void set_launch_cus(int n);
 GemmPlan plan_gemm_bf16(int M, int N, int K, bool f32_residual = false, bool gelu = false);   // f32_residual: fp32 C with an fp32 residual (proj / fc2)
 hipError_t launch_gemm_bf16(const GemmParams& p, const GemmPlan& plan, float* ws, hipStream_t s);
 
-// bf16-storage mode, short-K dense GEMM with the weights resident in registers (kernels/gemm_bf16.hip, gemm_wstat_bf16_kernel): Wp = the weights in
+// bf16-storage mode, short-K dense GEMM with the weights resident in registers (kernels/rows_bf16.hip, gemm_wstat_bf16_kernel): Wp = the weights in
 // MFMA fragment order (GemmW::wf, attach_dense_frags), K = 192 (64-row A tiles) or 384 (32-row tiles), N % 192 == 0, bf16 out, bias + activation only
 bool gemm_wstat_eligible(const GemmParams& p);
 hipError_t launch_gemm_wstat(const GemmParams& p, hipStream_t s);
@@ -100,8 +100,8 @@ bool gemm_planes_eligible(const GemmParams& p);
 GemmPlan plan_gemm_planes(int M, int N, int K, int planes, bool c_planes);
 hipError_t launch_gemm_planes(const GemmParams& p, const GemmPlan& plan, float* ws, hipStream_t s);
 
-// compute mode BRN_F16: the same kernels with fp16 as the 16-bit storage / MFMA operand type (kernels/gemm_bf16.hip and kernels/deform_bf16.hip
-// compiled with -DBRN_S16_F16=1).  Same contracts as the functions of the same name above.
+// compute mode BRN_F16: the same kernels with fp16 as the 16-bit storage / MFMA operand type (kernels/gemm_bf16.hip, kernels/rows_bf16.hip and
+// kernels/deform_bf16.hip compiled with -DBRN_S16_F16=1: kernels/s16_common.h).  Same contracts as the functions of the same name above.
 namespace hf {
 GemmPlan plan_gemm_bf16(int M, int N, int K, bool f32_residual = false, bool gelu = false);
 hipError_t launch_gemm_bf16(const GemmParams& p, const GemmPlan& plan, float* ws, hipStream_t s);

@@ -21,59 +21,13 @@
 // Bound: the gather (4 x 128 bytes per pixel and K step from L1 / L2) and its VALU work, not the matrix pipe: per K step a wave
 // issues 32 MFMAs (512 matrix-pipe cycles) beside ~230 vector instructions.
 #include "../brn_kernels.h"
-#include "gemm_common.h"
+#include "s16_common.h"       // compiled twice like gemm_bf16.hip: the storage type and the namespace
 #include <cstdlib>
 #include <type_traits>
 
-// Compiled twice like gemm_bf16.hip: -DBRN_S16_F16=1 builds the fp16-storage flavour (compute mode BRN_F16) in namespace brn::hf.
-#ifndef BRN_S16_F16
-#define BRN_S16_F16 0
-#endif
-namespace brn {
-#if BRN_S16_F16
-namespace hf {
-typedef _Float16 s16_t;
-#define BRN_MFMA_16X16X32(A, B, C) __builtin_amdgcn_mfma_f32_16x16x32_f16(A, B, C, 0, 0, 0)
-#else
-typedef __bf16 s16_t;
-#define BRN_MFMA_16X16X32(A, B, C) __builtin_amdgcn_mfma_f32_16x16x32_bf16(A, B, C, 0, 0, 0)
-#endif
-typedef s16_t s16x8 __attribute__((ext_vector_type(8)));
-#if BRN_S16_F16      // (an unqualified call would also find the brn:: function of the same name through its brn::GemmParams argument)
-#define BRN_S16_SELF(FN) hf::FN
-#else
-#define BRN_S16_SELF(FN) FN
-#endif
-__device__ __forceinline__ float d16_lo_f32(unsigned r) {
-#if BRN_S16_F16
-    typedef _Float16 h2_d __attribute__((ext_vector_type(2)));
-    return (float)__builtin_bit_cast(h2_d, r)[0];
-#else
-    return __builtin_bit_cast(float, r << 16);
-#endif
-}
-__device__ __forceinline__ float d16_hi_f32(unsigned r) {
-#if BRN_S16_F16
-    typedef _Float16 h2_d __attribute__((ext_vector_type(2)));
-    return (float)__builtin_bit_cast(h2_d, r)[1];
-#else
-    return __builtin_bit_cast(float, r & 0xffff0000u);
-#endif
-}
-
-typedef float f32x4_d __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4_d __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2_d __attribute__((ext_vector_type(2)));
+BRN_S16_BEGIN
 
 constexpr int DBM = 64, DBN = 256, DBK = 64;
-
-__device__ __forceinline__ unsigned dpack2(float lo, float hi) {
-    typedef s16_t s16x2_d __attribute__((ext_vector_type(2)));
-    const s16x2_d t = {(s16_t)lo, (s16_t)hi};
-    return __builtin_bit_cast(unsigned, t);
-}
-// byte offset of 16-byte chunk c (0..7) of tile row r (128-byte rows) in the swizzled A image
-__device__ __forceinline__ int a_slot(int r, int c) { return (r >> 1) * 256 + (((((r & 1) << 3) | c) ^ ((r >> 1) & 15)) << 4); }
 
 __global__ void __launch_bounds__(256, 2) gemm_deform_bf16_kernel(const GemmParams p) {
     __shared__ __attribute__((aligned(1024))) char smem[DBM * DBN * 2];   // K loop: two 8-KB A tiles; epilogue: [64][256] bf16
@@ -111,7 +65,7 @@ __global__ void __launch_bounds__(256, 2) gemm_deform_bf16_kernel(const GemmPara
     const int nk = p.K / DBK;
     const int pix_bytes = p.lda * 2;
 
-    u32x4_d gv[2][4];
+    u32x4 gv[2][4];
     float gw[2][4];
     auto gather_issue = [&](int kt) {
         const int tap = kt / cpt, ci0 = (kt - tap * cpt) * DBK;
@@ -138,27 +92,27 @@ __global__ void __launch_bounds__(256, 2) gemm_deform_bf16_kernel(const GemmPara
             const int ylc = min(max(yl, 0), p.Hin - 1), yhc = min(max(yh, 0), p.Hin - 1);
             const int xlc = min(max(xl, 0), p.Win - 1), xhc = min(max(xh, 0), p.Win - 1);
             const char* base = a_img[i] + ci0 * 2;
-            gv[i][0] = *reinterpret_cast<const u32x4_d*>(base + (long)(ylc * p.Win + xlc) * pix_bytes);
-            gv[i][1] = *reinterpret_cast<const u32x4_d*>(base + (long)(ylc * p.Win + xhc) * pix_bytes);
-            gv[i][2] = *reinterpret_cast<const u32x4_d*>(base + (long)(yhc * p.Win + xlc) * pix_bytes);
-            gv[i][3] = *reinterpret_cast<const u32x4_d*>(base + (long)(yhc * p.Win + xhc) * pix_bytes);
+            gv[i][0] = *reinterpret_cast<const u32x4*>(base + (long)(ylc * p.Win + xlc) * pix_bytes);
+            gv[i][1] = *reinterpret_cast<const u32x4*>(base + (long)(ylc * p.Win + xhc) * pix_bytes);
+            gv[i][2] = *reinterpret_cast<const u32x4*>(base + (long)(yhc * p.Win + xlc) * pix_bytes);
+            gv[i][3] = *reinterpret_cast<const u32x4*>(base + (long)(yhc * p.Win + xhc) * pix_bytes);
         }
     };
     auto gather_finish = [&](char* abuf) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            u32x4_d o;
+            u32x4 o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 float lo = 0.f, hi = 0.f;
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
-                    lo = fmaf(gw[i][c], d16_lo_f32(gv[i][c][e]), lo);
-                    hi = fmaf(gw[i][c], d16_hi_f32(gv[i][c][e]), hi);
+                    lo = fmaf(gw[i][c], s16_lo_f32(gv[i][c][e]), lo);
+                    hi = fmaf(gw[i][c], s16_hi_f32(gv[i][c][e]), hi);
                 }
-                o[e] = dpack2(lo, hi);
+                o[e] = pack_bf16x2(lo, hi);
             }
-            *reinterpret_cast<u32x4_d*>(abuf + a_slot(gr + 32 * i, gc)) = o;
+            *reinterpret_cast<u32x4*>(abuf + swz_slot(gr + 32 * i, gc)) = o;
         }
     };
 
@@ -171,13 +125,13 @@ __global__ void __launch_bounds__(256, 2) gemm_deform_bf16_kernel(const GemmPara
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int s = 0; s < 2; ++s) a_foff[i][s] = a_slot(16 * i + (lane & 15), 4 * s + (lane >> 4));
+        for (int s = 0; s < 2; ++s) a_foff[i][s] = swz_slot(16 * i + (lane & 15), 4 * s + (lane >> 4));
 
-    f32x4_d acc[4][4];
+    f32x4 acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_d{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     gather_issue(0);
     gather_finish(smem);
@@ -211,22 +165,22 @@ __global__ void __launch_bounds__(256, 2) gemm_deform_bf16_kernel(const GemmPara
         for (int j = 0; j < 4; ++j) {
             const int nl = 64 * wave + 16 * j + 4 * q4;          // channel within the tile
             const int n = n0 + nl;
-            f32x4_d bias = {0.f, 0.f, 0.f, 0.f}, sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
+            f32x4 bias = {0.f, 0.f, 0.f, 0.f}, sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
             if (n < p.N) {                                         // N % 4 == 0 (launcher)
-                if (p.bias) bias = *reinterpret_cast<const f32x4_d*>(p.bias + n);
-                if (p.scale) { sc = *reinterpret_cast<const f32x4_d*>(p.scale + n); sh = *reinterpret_cast<const f32x4_d*>(p.shift + n); }
+                if (p.bias) bias = *reinterpret_cast<const f32x4*>(p.bias + n);
+                if (p.scale) { sc = *reinterpret_cast<const f32x4*>(p.scale + n); sh = *reinterpret_cast<const f32x4*>(p.shift + n); }
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                f32x4_d v = (acc[i][j] + bias) * sc + sh;
+                f32x4 v = (acc[i][j] + bias) * sc + sh;
                 if (p.act == ACT_RELU) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
                 }
                 const int row = 16 * i + pr;
                 const int chunk = (nl >> 3) ^ (row & 31);          // 32 chunks of 16 bytes per 512-byte row
-                const u32x2_d o = {dpack2(v[0], v[1]), dpack2(v[2], v[3])};
-                *reinterpret_cast<u32x2_d*>(smem + row * (DBN * 2) + chunk * 16 + (nl & 4) * 2) = o;
+                const u32x2 o = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
+                *reinterpret_cast<u32x2*>(smem + row * (DBN * 2) + chunk * 16 + (nl & 4) * 2) = o;
             }
         }
     }
@@ -237,8 +191,8 @@ __global__ void __launch_bounds__(256, 2) gemm_deform_bf16_kernel(const GemmPara
         for (int ps = 0; ps < DBM / 8; ++ps) {
             const int row = ps * 8 + (tid >> 5), c = tid & 31;
             const int m = m0 + row, n = n0 + c * 8;
-            const u32x4_d v = *reinterpret_cast<const u32x4_d*>(smem + row * (DBN * 2) + ((c ^ (row & 31)) << 4));
-            if (m < p.M && n < p.N) *reinterpret_cast<u32x4_d*>(Cb + (long)m * p.ldc + p.c_coff + n) = v;   // N % 8 == 0 (launcher)
+            const u32x4 v = *reinterpret_cast<const u32x4*>(smem + row * (DBN * 2) + ((c ^ (row & 31)) << 4));
+            if (m < p.M && n < p.N) *reinterpret_cast<u32x4*>(Cb + (long)m * p.ldc + p.c_coff + n) = v;   // N % 8 == 0 (launcher)
         }
     }
 }
@@ -312,7 +266,7 @@ __global__ void __launch_bounds__(256, 2) gemm_deform_bf16_v2_kernel(const GemmP
         const float ly = y - yf, lx = x - xf, hy = 1.f - ly, hx = 1.f - lx;
         const float s = inside ? mk : 0.f;
         const bool yl_ok = yl >= 0, yh_ok = yh <= p.Hin - 1, xl_ok = xl >= 0, xh_ok = xh <= p.Win - 1;
-        f32x4_d w4;
+        f32x4 w4;
         w4[0] = (yl_ok && xl_ok) ? s * (hy * hx) : 0.f;
         w4[1] = (yl_ok && xh_ok) ? s * (hy * lx) : 0.f;
         w4[2] = (yh_ok && xl_ok) ? s * (ly * hx) : 0.f;
@@ -320,19 +274,19 @@ __global__ void __launch_bounds__(256, 2) gemm_deform_bf16_v2_kernel(const GemmP
         // clamped corners: always a valid address (a corner that is not real carries a zero weight); the integer clamps also tame NaN / huge offsets
         const int ylc = min(max(yl, 0), p.Hin - 1), yhc = min(max(yh, 0), p.Hin - 1);
         const int xlc = min(max(xl, 0), p.Win - 1), xhc = min(max(xh, 0), p.Win - 1);
-        u32x4_d o4;
+        u32x4 o4;
         o4[0] = p_img + (unsigned)(ylc * p.Win + xlc) * (unsigned)pix_bytes;
         o4[1] = p_img + (unsigned)(ylc * p.Win + xhc) * (unsigned)pix_bytes;
         o4[2] = p_img + (unsigned)(yhc * p.Win + xlc) * (unsigned)pix_bytes;
         o4[3] = p_img + (unsigned)(yhc * p.Win + xhc) * (unsigned)pix_bytes;
-        *reinterpret_cast<u32x4_d*>(ptab + lane * 16) = o4;
-        *reinterpret_cast<f32x4_d*>(ptab + 1024 + (blk & 1) * 1024 + lane * 16) = w4;
+        *reinterpret_cast<u32x4*>(ptab + lane * 16) = o4;
+        *reinterpret_cast<f32x4*>(ptab + 1024 + (blk & 1) * 1024 + lane * 16) = w4;
     };
 
     // ---- gather role: thread = (row gr and gr + 32, 16-byte channel chunk gc) ----
     const int gc = tid & 7, gr = tid >> 3;
     const int e0 = (gr & 7) * 16;                                        // byte offset of this thread's first row in a table (entry pi = gr & 7; second row: pi + 8)
-    u32x4_d gv[2][2][4];
+    u32x4 gv[2][2][4];
     auto gather_issue = [&](auto set_c, int kt) {
         constexpr int S = decltype(set_c)::value;
         const int tap = kt / cpt;
@@ -340,7 +294,7 @@ __global__ void __launch_bounds__(256, 2) gemm_deform_bf16_v2_kernel(const GemmP
         const char* te = ptab + (tap & 3) * 256 + e0;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            const u32x4_d o = *reinterpret_cast<const u32x4_d*>(te + i * 128);
+            const u32x4 o = *reinterpret_cast<const u32x4*>(te + i * 128);
 #pragma unroll
             for (int c = 0; c < 4; ++c) gv[S][i][c] = __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, o[c] + ch, 0, 0);
         }
@@ -351,23 +305,23 @@ __global__ void __launch_bounds__(256, 2) gemm_deform_bf16_v2_kernel(const GemmP
         constexpr int S = decltype(set_c)::value;
         const int tap = kt / cpt;
         const char* te = ptab + 1024 + ((tap >> 2) & 1) * 1024 + (tap & 3) * 256 + e0;
-        f32x4_d gw[1][2];
-        gw[0][0] = *reinterpret_cast<const f32x4_d*>(te);
-        gw[0][1] = *reinterpret_cast<const f32x4_d*>(te + 128);
+        f32x4 gw[1][2];
+        gw[0][0] = *reinterpret_cast<const f32x4*>(te);
+        gw[0][1] = *reinterpret_cast<const f32x4*>(te + 128);
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            u32x4_d o;
+            u32x4 o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 float lo = 0.f, hi = 0.f;
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
-                    lo = fmaf(gw[0][i][c], d16_lo_f32(gv[S][i][c][e]), lo);
-                    hi = fmaf(gw[0][i][c], d16_hi_f32(gv[S][i][c][e]), hi);
+                    lo = fmaf(gw[0][i][c], s16_lo_f32(gv[S][i][c][e]), lo);
+                    hi = fmaf(gw[0][i][c], s16_hi_f32(gv[S][i][c][e]), hi);
                 }
-                o[e] = dpack2(lo, hi);
+                o[e] = pack_bf16x2(lo, hi);
             }
-            *reinterpret_cast<u32x4_d*>(abuf + a_slot(gr + 32 * i, gc)) = o;
+            *reinterpret_cast<u32x4*>(abuf + swz_slot(gr + 32 * i, gc)) = o;
         }
     };
 
@@ -376,13 +330,13 @@ __global__ void __launch_bounds__(256, 2) gemm_deform_bf16_v2_kernel(const GemmP
     const long wf_nb = (long)nk * 2 * 1024;
     // A fragment (row block i, half step s): tile row 16 i + (lane & 15), chunk 4 s + (lane >> 4).  Against (i, s) = (0, 0) the swizzled
     // offset only has bit 6 flipped by s and bit 7 by an odd i (16 rows = 8 bank rows: the XOR key's bit 3), + 2 KB per i: one register
-    const int a_f0 = a_slot(lane & 15, lane >> 4);
+    const int a_f0 = swz_slot(lane & 15, lane >> 4);
     auto a_foff = [&](int i, int s) { return i * 2048 + (a_f0 ^ (s * 64) ^ ((i & 1) * 128)); };
-    f32x4_d acc[4][4];
+    f32x4 acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_d{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     s16x8 wfr[2][4];                                                    // [half step s][n16 block j]
     auto load_w = [&](auto s_c, int kt) {
         constexpr int S = decltype(s_c)::value;
@@ -453,22 +407,22 @@ __global__ void __launch_bounds__(256, 2) gemm_deform_bf16_v2_kernel(const GemmP
         for (int j = 0; j < 4; ++j) {
             const int nl = 64 * wave + 16 * j + 4 * q4;
             const int n = n0 + nl;
-            f32x4_d bias = {0.f, 0.f, 0.f, 0.f}, sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
+            f32x4 bias = {0.f, 0.f, 0.f, 0.f}, sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
             if (n < p.N) {
-                if (p.bias) bias = *reinterpret_cast<const f32x4_d*>(p.bias + n);
-                if (p.scale) { sc = *reinterpret_cast<const f32x4_d*>(p.scale + n); sh = *reinterpret_cast<const f32x4_d*>(p.shift + n); }
+                if (p.bias) bias = *reinterpret_cast<const f32x4*>(p.bias + n);
+                if (p.scale) { sc = *reinterpret_cast<const f32x4*>(p.scale + n); sh = *reinterpret_cast<const f32x4*>(p.shift + n); }
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                f32x4_d v = (acc[i][j] + bias) * sc + sh;
+                f32x4 v = (acc[i][j] + bias) * sc + sh;
                 if (p.act == ACT_RELU) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
                 }
                 const int row = 16 * i + pr;
                 const int chunk = (nl >> 3) ^ (row & 31);
-                const u32x2_d o = {dpack2(v[0], v[1]), dpack2(v[2], v[3])};
-                *reinterpret_cast<u32x2_d*>(smem + row * (DBN * 2) + chunk * 16 + (nl & 4) * 2) = o;
+                const u32x2 o = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
+                *reinterpret_cast<u32x2*>(smem + row * (DBN * 2) + chunk * 16 + (nl & 4) * 2) = o;
             }
         }
     }
@@ -479,8 +433,8 @@ __global__ void __launch_bounds__(256, 2) gemm_deform_bf16_v2_kernel(const GemmP
         for (int ps = 0; ps < DBM / 8; ++ps) {
             const int row = ps * 8 + (tid >> 5), c = tid & 31;
             const int m = m0 + row, n = n0 + c * 8;
-            const u32x4_d v = *reinterpret_cast<const u32x4_d*>(smem + row * (DBN * 2) + ((c ^ (row & 31)) << 4));
-            if (m < p.M && n < p.N) *reinterpret_cast<u32x4_d*>(Cb + (long)m * p.ldc + p.c_coff + n) = v;
+            const u32x4 v = *reinterpret_cast<const u32x4*>(smem + row * (DBN * 2) + ((c ^ (row & 31)) << 4));
+            if (m < p.M && n < p.N) *reinterpret_cast<u32x4*>(Cb + (long)m * p.ldc + p.c_coff + n) = v;
         }
     }
 }
@@ -503,7 +457,4 @@ hipError_t launch_deform_bf16(const GemmParams& p, hipStream_t s) {
     return hipGetLastError();
 }
 
-#if BRN_S16_F16
-}  // namespace hf
-#endif
-}  // namespace brn
+BRN_S16_END

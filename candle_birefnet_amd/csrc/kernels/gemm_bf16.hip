@@ -18,57 +18,14 @@
 //     permutation is applied to the per-lane SOURCE offset (which row / chunk a lane fetches), never to the destination;
 //   * a wave's instructions are i = w + NW j, so a lane's (row parity, chunk) is the same for all of them: the implicit-GEMM
 //     mode tracks ONE (tap, channel) per lane per K step, by increments (no division in the loop).
+// The file holds that tiled kernel (gemm_bf16_kernel), its split-K second pass, the tile planner and launch_gemm_bf16, and the CU count
+// the persistent grids are sized for.  The whole-row kernels of the same modes (weight-stationary short-K GEMM, projection + LayerNorm) are
+// in rows_bf16.hip; the storage-type prelude of both — and the second, fp16, compilation — is described in s16_common.h.
 #include "../brn_kernels.h"
-#include "gemm_common.h"
+#include "s16_common.h"
 #include <type_traits>
 
-// The file is compiled twice (Makefile): as is for compute mode BRN_BF16, and with -DBRN_S16_F16=1 for BRN_F16 — the same kernels with fp16
-// as the 16-bit storage / MFMA operand type (3 more mantissa bits at the same bytes and the same matrix rate), in namespace brn::hf.
-#ifndef BRN_S16_F16
-#define BRN_S16_F16 0
-#endif
-namespace brn {
-#if BRN_S16_F16
-namespace hf {
-typedef _Float16 s16_t;
-#define BRN_MFMA_32X32X16(A, B, C) __builtin_amdgcn_mfma_f32_32x32x16_f16(A, B, C, 0, 0, 0)
-#define BRN_MFMA_16X16X32(A, B, C) __builtin_amdgcn_mfma_f32_16x16x32_f16(A, B, C, 0, 0, 0)
-#else
-typedef __bf16 s16_t;
-#define BRN_MFMA_32X32X16(A, B, C) __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, B, C, 0, 0, 0)
-#define BRN_MFMA_16X16X32(A, B, C) __builtin_amdgcn_mfma_f32_16x16x32_bf16(A, B, C, 0, 0, 0)
-#endif
-typedef s16_t s16x8 __attribute__((ext_vector_type(8)));
-#if BRN_S16_F16      // (an unqualified call would also find the brn:: function of the same name through its brn::GemmParams argument)
-#define BRN_S16_SELF(FN) hf::FN
-#else
-#define BRN_S16_SELF(FN) FN
-#endif
-
-typedef unsigned u32x2_b __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {      // v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32 (round to nearest even): lo in bits 0-15
-    typedef s16_t s16x2_b __attribute__((ext_vector_type(2)));
-    const s16x2_b t = {(s16_t)lo, (s16_t)hi};
-    return __builtin_bit_cast(unsigned, t);
-}
-// the two 16-bit storage values packed in a dword, as fp32
-__device__ __forceinline__ float s16_lo_f32(unsigned r) {
-#if BRN_S16_F16
-    typedef _Float16 h2_b __attribute__((ext_vector_type(2)));
-    return (float)__builtin_bit_cast(h2_b, r)[0];
-#else
-    return __builtin_bit_cast(float, r << 16);
-#endif
-}
-__device__ __forceinline__ float s16_hi_f32(unsigned r) {
-#if BRN_S16_F16
-    typedef _Float16 h2_b __attribute__((ext_vector_type(2)));
-    return (float)__builtin_bit_cast(h2_b, r)[1];
-#else
-    return __builtin_bit_cast(float, r & 0xffff0000u);
-#endif
-}
+BRN_S16_BEGIN
 
 __device__ __attribute__((aligned(16))) unsigned g_zero_page[64];   // 256 zero bytes (code-object global: zero-initialised)
 
@@ -91,17 +48,6 @@ constexpr bool SCHED = BRN_BF16_SCHED != 0;
 #ifndef BRN_BF16_CFG2_M16          // the 256 x 256 tile keeps 32x32x16 with both fragment sets double-buffered: with 16x16x32 it has no
 #define BRN_BF16_CFG2_M16 0        // registers left (spills, rematerialised addresses) and measured 7 % slower; the smaller tiles gain 5-13 %
 #endif
-
-__device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
-}
-__device__ __forceinline__ void blds16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, int soff, void* lds_dst) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_dst, 16, voff, soff, 0, 0);
-}
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-__device__ __forceinline__ float bf16_bits_to_f32(unsigned short h) { return s16_lo_f32((unsigned)h); }
 
 // 8 consecutive outputs of one row: everything of the epilogue after the accumulator
 template <bool VEC>
@@ -676,488 +622,13 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_bf16_kernel(const GemmParams
     }
 }
 
-
-// =====================================================================================================================
-// gemm_wstat_bf16_kernel — dense C = act(A W^T + b) for SHORT K (K = 64 KS: 192, or 384 with 32-row tiles) and wide A (M >> N): the stage-0 /
-// stage-1 qkv and fc1 GEMMs of the Swin backbone at batch >= 4 (swin.rs:98,130; M = 655 360, K = 192, N = 576 / 768 at batch 8).  With three K steps per tile the
-// persistent 256 x 256 kernel above is prologue / epilogue all the way (2.0 - 2.6 TB/s of algorithmic traffic); here the weights never
-// move: a wave keeps its 48 columns of W (K x 48 bf16 = 72 VGPRs, loaded once, stored in MFMA fragment order by attach_dense_frags) for
-// the whole launch and the workgroup streams 64-row tiles of A through a two-buffer LDS ring (LDS-DMA, XOR-swizzled 128-byte rows as
-// above); what is left per tile is 24 KB in, 96 MFMAs per wave, 24 KB out.  A workgroup = 4 waves = 192 columns; the N / 192 column
-// groups of a row tile are neighbouring workgroups of one XCD walking the same tiles (the A tile is read from HBM once, then from L2).
-// The C tile goes back through the A buffer it came from (two 32-row halves, 512-byte rows, XOR-ed chunks) and leaves as 384-byte
-// row segments.
-// =====================================================================================================================
-constexpr int WSTAT_WG_PER_CU = 2;      // 2: <= 256 VGPRs, no spill (forced to 168 for three per CU the kernel spills 30-40 registers)
-// CUs the persistent grids of this file are sized for: 256, or the size of the CU mask of the stream being launched on (a sub-batch
+// CUs the persistent grids of this file and of rows_bf16.hip are sized for: 256, or the size of the CU mask of the stream being launched on (a sub-batch
 // stream confined to a part of the chip, brn_api.cpp run_model); thread-local: set by the host thread that enqueues the forward
 #if !BRN_S16_F16     // (one state for both builds: brn::launch_cus)
 static thread_local int g_launch_cus = 256;
 int launch_cus() { return g_launch_cus; }
 void set_launch_cus(int n) { g_launch_cus = n < 8 ? 8 : (n > 256 ? 256 : n) / 8 * 8; }
 #endif
-
-__device__ __forceinline__ int ws_slot(int r, int c) { return (r >> 1) * 256 + (((((r & 1) << 3) | c) ^ ((r >> 1) & 15)) << 4); }
-
-// WBM = rows per A tile: 64 at K = 192 (two 24-KB buffers), 32 at K = 384 (the W slice is 144 VGPRs there; two 24-KB buffers again,
-// so two workgroups still share a CU and one's epilogue overlaps the other's MFMAs)
-template <int KS, int ACT, int WBM = 64>
-__global__ void __launch_bounds__(256, 2) gemm_wstat_bf16_kernel(const GemmParams p) {
-    constexpr int WBN = 192, SUB = WBM * 128;                            // columns per workgroup, bytes of one K step's sub-tile
-    constexpr int K32 = KS * 2, ABUF = KS * SUB;
-    constexpr int NJ = WBM / 32, RF = WBM / 16;                          // LDS-DMA instructions per wave and K step, 16-row fragments per tile
-    static_assert(WBM == 64 || WBM == 32, "tile rows");
-    static_assert(ABUF >= 32 * 512, "a 32-row half of the C tile (512-byte rows) must fit the A buffer it replaces");
-    __shared__ __attribute__((aligned(1024))) char smem[2 * ABUF];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int G = p.N / WBN, T = (p.M + WBM - 1) / WBM;
-    // workgroups of one XCD (same blockIdx % 8): local index li -> column group li % G, walker li / G of nw; XCD x owns a contiguous run of row tiles
-    const int xcd = blockIdx.x & 7, li = blockIdx.x >> 3, nw = ((int)gridDim.x >> 3) / G;
-    const int grp = li % G, wk = li / G;
-    const int t_lo = (int)((long)T * xcd / 8), t_hi = (int)((long)T * (xcd + 1) / 8);
-    if (wk >= nw) return;
-    const int n0 = grp * WBN + wave * 48;                               // this wave's first column
-    // ---- W fragments, resident for the whole launch ----
-    s16x8 wfr[3][K32];
-    {
-        const char* wf = reinterpret_cast<const char*>(p.Wp) + ((long)(n0 >> 4) * K32 * 64 + lane) * 16;
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-#pragma unroll
-            for (int ks = 0; ks < K32; ++ks) wfr[j][ks] = *reinterpret_cast<const s16x8*>(wf + (long)(j * K32 + ks) * 1024);
-    }
-    f32x4 bias[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) bias[j] = p.bias ? *reinterpret_cast<const f32x4*>(p.bias + n0 + 16 * j + 4 * (lane >> 4)) : zero4();
-    // ---- this lane's share of an A tile: LDS-DMA instruction ii = wave + 4 j (j < NJ) of every sub-tile fills bank rows 4 ii .. 4 ii + 3 ----
-    unsigned a_voff[NJ];
-    int a_row[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int pr = 4 * (wave + 4 * j) + (lane >> 4), qs = (lane & 15) ^ (pr & 15);
-        a_row[j] = 2 * pr + (qs >> 3);
-        a_voff[j] = (unsigned)((qs & 7) * 16);                          // byte offset inside the 128-byte K-step piece of the row
-    }
-    const s16_t* Ab = reinterpret_cast<const s16_t*>(p.A);
-    auto issue = [&](int t, char* buf) {
-        const int m0 = t * WBM;
-        __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<s16_t*>(Ab + (long)m0 * p.lda + p.a_coff), 0, 0x7fffffff, 0x00020000);
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const unsigned ro = (unsigned)((min(m0 + a_row[j], p.M - 1) - m0) * p.lda * 2) + a_voff[j];   // rows >= M re-read row M - 1 (never stored)
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) blds16(rs, ro, ks * 128, buf + ks * SUB + (wave + 4 * j) * 1024);
-        }
-    };
-    int a_foff[RF][2];
-#pragma unroll
-    for (int i = 0; i < RF; ++i)
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) a_foff[i][s2] = ws_slot(16 * i + (lane & 15), 4 * s2 + (lane >> 4));
-
-    int t = t_lo + wk;
-    if (t < t_hi) issue(t, smem);
-    for (int it = 0; t < t_hi; ++it, t += nw) {
-        char* buf = smem + (it & 1) * ABUF;
-        const bool more = t + nw < t_hi;
-        if (more) { issue(t + nw, smem + ((it + 1) & 1) * ABUF); wait_vmcnt<NJ * KS>(); }   // this tile (and the previous tile's stores) landed; the next one may be in flight
-        else wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        f32x4 acc[RF][3];
-#pragma unroll
-        for (int i = 0; i < RF; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) acc[i][j] = zero4();
-#pragma unroll
-        for (int ks = 0; ks < K32; ++ks) {
-            s16x8 af[RF];
-#pragma unroll
-            for (int i = 0; i < RF; ++i) af[i] = *reinterpret_cast<const s16x8*>(buf + (ks >> 1) * SUB + a_foff[i][ks & 1]);
-#pragma unroll
-            for (int j = 0; j < 3; ++j)
-#pragma unroll
-                for (int i = 0; i < RF; ++i) acc[i][j] = BRN_MFMA_16X16X32(wfr[j][ks], af[i], acc[i][j]);
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();                                   // every wave has read its fragments: the buffer now takes the C tile
-        const int m0 = t * WBM;
-        s16_t* Cb = reinterpret_cast<s16_t*>(p.C);
-#pragma unroll
-        for (int half = 0; half < WBM / 32; ++half) {
-#pragma unroll
-            for (int ii = 0; ii < 2; ++ii) {
-                const int i = 2 * half + ii, row = 16 * ii + (lane & 15);          // row within the 32-row half
-#pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    f32x4 v = acc[i][j] + bias[j];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        if (ACT == ACT_GELU_ERF) v[e] = gelu_erf_bf16out(v[e]);
-                        else if (ACT == ACT_RELU) v[e] = fmaxf(v[e], 0.f);
-                    }
-                    const int col = wave * 48 + 16 * j + 4 * (lane >> 4);           // column within the workgroup's 192
-                    const u32x2_b o = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
-                    *reinterpret_cast<u32x2_b*>(buf + row * 512 + (((col >> 3) ^ (row & 31)) << 4) + (col & 4) * 2) = o;
-                }
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {                                // 32 rows x 24 chunks of 16 bytes over 256 threads
-                const int idx = tid + 256 * q, row = idx / 24, ch = idx - row * 24;
-                const u32x4 v = *reinterpret_cast<const u32x4*>(buf + row * 512 + ((ch ^ (row & 31)) << 4));
-                const int m = m0 + half * 32 + row;
-                if (m < p.M) *reinterpret_cast<u32x4*>(Cb + (long)m * p.ldc + p.c_coff + grp * WBN + ch * 8) = v;
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();                               // the half (and, after the second one, the buffer) is free again
-        }
-    }
-}
-
-// =====================================================================================================================
-// gemm_wstat_ln_bf16_kernel — the attention output projection of a C = 192 stage with the block's second LayerNorm in its epilogue
-// (swin.rs:310,406,407): x = A Wᵀ + bias + x (fp32 residual stream, in place) and y = LayerNorm(x) γ + β (bf16, the fc1 operand).
-// N = K = 192: a workgroup of the weight-stationary kernel above owns WHOLE rows (4 waves x 48 columns), so the row statistics are
-// local.  The C tile goes through the A buffer as fp32 (32 rows x 768 B = the 24-KB buffer, 16-byte chunks XOR-ed with the row); on the
-// way back 8 lanes share a row (6 chunks each): residual add, store of x, two-pass mean / biased variance (the arithmetic of
-// layernorm_kernel) over the 8 lanes by DPP shuffles, store of y.  What it saves is the stand-alone LayerNorm's read of x.
-// =====================================================================================================================
-__global__ void __launch_bounds__(256, 2) gemm_wstat_ln_bf16_kernel(const GemmParams p, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                                     const float eps, s16_t* __restrict__ Y, const int ldy) {
-    constexpr int KS = 3, WBM = 64, WBN = 192, SUB = WBM * 128;
-    constexpr int K32 = KS * 2, ABUF = KS * SUB;
-    static_assert(ABUF == 32 * WBN * 4, "a 32-row half of the fp32 C tile is exactly one A buffer");
-    __shared__ __attribute__((aligned(1024))) char smem[2 * ABUF];
-    __shared__ __attribute__((aligned(16))) float gb_s[2 * WBN];         // gamma | beta
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int T = (p.M + WBM - 1) / WBM;
-    const int xcd = blockIdx.x & 7, wk = blockIdx.x >> 3, nw = (int)gridDim.x >> 3;
-    const int t_lo = (int)((long)T * xcd / 8), t_hi = (int)((long)T * (xcd + 1) / 8);
-    if (tid < WBN) { gb_s[tid] = gamma[tid]; gb_s[WBN + tid] = beta[tid]; }
-    const int n0 = wave * 48;
-    s16x8 wfr[3][K32];
-    {
-        const char* wf = reinterpret_cast<const char*>(p.Wp) + ((long)(n0 >> 4) * K32 * 64 + lane) * 16;
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-#pragma unroll
-            for (int ks = 0; ks < K32; ++ks) wfr[j][ks] = *reinterpret_cast<const s16x8*>(wf + (long)(j * K32 + ks) * 1024);
-    }
-    f32x4 bias[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) bias[j] = p.bias ? *reinterpret_cast<const f32x4*>(p.bias + n0 + 16 * j + 4 * (lane >> 4)) : zero4();
-    unsigned a_voff[2];
-    int a_row[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int pr = 4 * (wave + 4 * j) + (lane >> 4), qs = (lane & 15) ^ (pr & 15);
-        a_row[j] = 2 * pr + (qs >> 3);
-        a_voff[j] = (unsigned)((qs & 7) * 16);
-    }
-    const s16_t* Ab = reinterpret_cast<const s16_t*>(p.A);
-    auto issue = [&](int t, char* buf) {
-        const int m0 = t * WBM;
-        __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<s16_t*>(Ab + (long)m0 * p.lda + p.a_coff), 0, 0x7fffffff, 0x00020000);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const unsigned ro = (unsigned)((min(m0 + a_row[j], p.M - 1) - m0) * p.lda * 2) + a_voff[j];
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) blds16(rs, ro, ks * 128, buf + ks * SUB + (wave + 4 * j) * 1024);
-        }
-    };
-    int a_foff[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) a_foff[i][s2] = ws_slot(16 * i + (lane & 15), 4 * s2 + (lane >> 4));
-    const int er = tid >> 3, ec = tid & 7;                               // read-back: row of the 32-row half, first chunk (then + 8 k)
-    float* Cf = reinterpret_cast<float*>(p.C);
-    const float* Rf = reinterpret_cast<const float*>(p.R);
-
-    int t = t_lo + wk;
-    if (t < t_hi) issue(t, smem);
-    for (int it = 0; t < t_hi; ++it, t += nw) {
-        char* buf = smem + (it & 1) * ABUF;
-        const bool more = t + nw < t_hi;
-        if (more) { issue(t + nw, smem + ((it + 1) & 1) * ABUF); wait_vmcnt<2 * KS>(); }
-        else wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        f32x4 acc[4][3];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) acc[i][j] = zero4();
-#pragma unroll
-        for (int ks = 0; ks < K32; ++ks) {
-            s16x8 af[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) af[i] = *reinterpret_cast<const s16x8*>(buf + (ks >> 1) * SUB + a_foff[i][ks & 1]);
-#pragma unroll
-            for (int j = 0; j < 3; ++j)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc[i][j] = BRN_MFMA_16X16X32(wfr[j][ks], af[i], acc[i][j]);
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();                                   // every wave has read its fragments: the buffer now takes the C tile
-        const int m0 = t * WBM;
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-            const int m = m0 + half * 32 + er, mc = min(m, p.M - 1);
-            f32x4 rr[6];
-#pragma unroll
-            for (int k = 0; k < 6; ++k) rr[k] = *reinterpret_cast<const f32x4*>(Rf + (long)mc * p.ldr + p.r_coff + (ec + 8 * k) * 4);
-#pragma unroll
-            for (int ii = 0; ii < 2; ++ii) {
-                const int i = 2 * half + ii, row = 16 * ii + (lane & 15);
-#pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    const int ch = (wave * 48 + 16 * j + 4 * (lane >> 4)) >> 2;      // 16-byte chunk of the 768-byte row
-                    *reinterpret_cast<f32x4*>(buf + row * 768 + ((ch ^ (row & 7)) << 4)) = acc[i][j] + bias[j];
-                }
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            f32x4 xv[6];
-            float sum = 0.f;
-#pragma unroll
-            for (int k = 0; k < 6; ++k) {
-                const int ch = ec + 8 * k;
-                xv[k] = *reinterpret_cast<const f32x4*>(buf + er * 768 + ((ch ^ (er & 7)) << 4)) + rr[k];
-                sum += (xv[k][0] + xv[k][1]) + (xv[k][2] + xv[k][3]);
-            }
-            if (m < p.M) {
-#pragma unroll
-                for (int k = 0; k < 6; ++k) *reinterpret_cast<f32x4*>(Cf + (long)m * p.ldc + p.c_coff + (ec + 8 * k) * 4) = xv[k];
-            }
-            sum += __shfl_xor(sum, 1); sum += __shfl_xor(sum, 2); sum += __shfl_xor(sum, 4);
-            const float mean = sum / (float)WBN;
-            float sq = 0.f;
-#pragma unroll
-            for (int k = 0; k < 6; ++k) {
-                xv[k] = xv[k] - mean;
-                sq += (xv[k][0] * xv[k][0] + xv[k][1] * xv[k][1]) + (xv[k][2] * xv[k][2] + xv[k][3] * xv[k][3]);
-            }
-            sq += __shfl_xor(sq, 1); sq += __shfl_xor(sq, 2); sq += __shfl_xor(sq, 4);
-            const float rstd = 1.0f / sqrtf(sq / (float)WBN + eps);
-            if (m < p.M) {
-#pragma unroll
-                for (int k = 0; k < 6; ++k) {
-                    const int c0 = (ec + 8 * k) * 4;
-                    const f32x4 gm = *reinterpret_cast<const f32x4*>(gb_s + c0), bt = *reinterpret_cast<const f32x4*>(gb_s + WBN + c0);
-                    const f32x4 o = xv[k] * rstd * gm + bt;
-                    const u32x2_b ob = {pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3])};
-                    *reinterpret_cast<u32x2_b*>(Y + (long)m * ldy + c0) = ob;
-                }
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();                               // the half (and, after the second one, the buffer) is free again
-        }
-    }
-}
-// =====================================================================================================================
-// gemm_rowln_bf16_kernel<NC> (round 4) — the row-owning projection for the WIDE stages (NC = 768: stage 2, 18 of the 24 blocks; NC = 384:
-// stage 1): x = A W^T + bias + x on the fp32 residual stream (in place) AND y = LayerNorm(x) gamma + beta as the bf16 operand of the next
-// GEMM, in one launch (swin.rs:310,406,407) — the stand-alone LayerNorm launch and its fp32 re-read of x are gone.
-// A workgroup of 8 waves owns 64 WHOLE rows (64 x NC fp32 accumulators = 96 / 48 VGPRs per lane; wave w = columns [w NC/8, (w+1) NC/8)),
-// so the row statistics are local.  W does not fit anything but L2, so it streams through LDS: K step 32 (64-byte tile rows, four per
-// 256-byte bank row, 16-byte chunks XOR-ed with the bank row as in gemm_bf16_kernel<BBK = 32>), three ring slots of (64 + NC) x 64 B, the
-// pieces of K step t + 2 issued right after the barrier of step t (counted vmcnt; waves 0-3 carry the A pieces).  Per 64 rows the
-// workgroup takes in the whole W (1.18 MB at NC = 768): the K loop is bound by the CU's L2 -> LDS intake, not by the matrix pipe, and the
-// launch as a whole by HBM (A once, x read + written once, y once) — which is the point: 378 MB per stage-2 launch instead of the 504 MB of
-// projection + LayerNorm.  Epilogue: the C tile leaves through the ring as fp32 in two 32-row halves (16-byte chunks XOR-ed with the row),
-// comes back with 16 lanes per row (whole 256-byte segments), + residual, store x, two-pass mean / biased variance (the arithmetic of
-// layernorm_kernel), store y.  The next tile's first K step is already in flight (slot 2) during the epilogue.
-// =====================================================================================================================
-template <int NC>
-__global__ void __launch_bounds__(512) gemm_rowln_bf16_kernel(const GemmParams p, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                              const float eps, s16_t* __restrict__ Y, const int ldy) {
-    constexpr int RBM = 64, RBK = 32, ROWB = RBK * 2;                    // 64-byte tile rows
-    constexpr int WCOL = NC / 8;                                         // columns per wave: 96 / 48
-    constexpr int FN = WCOL / 16, FM = RBM / 16;                         // 16 x 16 blocks of a wave tile
-    constexpr int A_BYTES = RBM * ROWB, SLOT = (RBM + NC) * ROWB;        // 4 KB + 48 / 24 KB
-    constexpr int LW = NC / 16 / 8;                                      // W pieces (1 KiB = 16 tile rows) per wave and K step: 6 / 3
-    constexpr int HALF_BYTES = 32 * NC * 4;                              // a 32-row half of the fp32 C tile
-    constexpr int CH_ROW = NC / 4, CPL = CH_ROW / 16;                    // 16-byte chunks per C row, chunks per lane in the read-back (16 lanes per row)
-    static_assert(3 * SLOT <= 160 * 1024 && HALF_BYTES <= 2 * SLOT - 0 && NC % 128 == 0, "ring / epilogue geometry");
-    __shared__ __attribute__((aligned(1024))) char smem[3 * SLOT];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int T = (p.M + RBM - 1) / RBM;
-    const int xcd = blockIdx.x & 7, wk = blockIdx.x >> 3, nw = (int)gridDim.x >> 3;
-    const int t_lo = (int)((long)T * xcd / 8), t_hi = (int)((long)T * (xcd + 1) / 8);
-    const int nk = p.K / RBK;
-    const s16_t* Ab = reinterpret_cast<const s16_t*>(p.A);
-    const s16_t* Wb = reinterpret_cast<const s16_t*>(p.Wp);
-
-    // ---- LDS-DMA: instruction ii fills bank rows 4 ii .. 4 ii + 3 (16 tile rows); lane -> (tile row, k chunk) through the swizzle ----
-    const int pr_l = lane >> 4;
-    // (bank row pr = 4 ii + pr_l, key pr & 3 = pr_l: the lane's logical slot and hence its (row in the 16-row piece, chunk) are the same for every piece)
-    const int qs = (lane & 15) ^ pr_l;
-    const int row16 = 4 * pr_l + (qs >> 2);                              // row within a 16-row piece
-    const unsigned kch_b = (unsigned)((qs & 3) * 16);                    // byte offset of the lane's k chunk within the 64-byte K step
-    const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<s16_t*>(Wb), 0, 0x7fffffff, 0x00020000);
-    unsigned w_voff[LW];
-#pragma unroll
-    for (int j = 0; j < LW; ++j) w_voff[j] = (unsigned)((16 * (wave * LW + j) + row16) * p.wp_ld * 2) + kch_b;
-    auto issue = [&](int m0, int kt, int slot) {                         // K step kt of the row tile at m0 into ring slot `slot`
-        char* sb = smem + slot * SLOT;
-        if (wave < 4) {
-            const int r = 16 * wave + row16;
-            const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<s16_t*>(Ab + (long)m0 * p.lda + p.a_coff), 0, 0x7fffffff, 0x00020000);
-            const unsigned vo = (unsigned)((min(m0 + r, p.M - 1) - m0) * p.lda * 2) + kch_b;     // rows >= M re-read row M - 1 (never stored)
-            blds16(a_rsrc, vo, kt * ROWB, sb + wave * 1024);
-        }
-#pragma unroll
-        for (int j = 0; j < LW; ++j) blds16(w_rsrc, w_voff[j], kt * ROWB, sb + A_BYTES + (wave * LW + j) * 1024);
-    };
-    // fragment offsets within a slot: 16x16x32: lane reads row (lane & 15) of a 16-row block (4 bank rows), chunk lane >> 4 (all of a K step)
-    const int f_off = ((lane & 15) >> 2) * 256 + (((((lane & 15) & 3) << 2) | (lane >> 4)) ^ (((lane & 15) >> 2) & 3)) * 16;
-
-    int t = t_lo + wk;
-    if (t < t_hi) issue(t * RBM, 0, 2);                                  // K step kt lives in slot (kt + 2) % 3
-    for (; t < t_hi; t += nw) {
-        const int m0 = t * RBM;
-        f32x4 acc[FM][FN];
-#pragma unroll
-        for (int i = 0; i < FM; ++i)
-#pragma unroll
-            for (int j = 0; j < FN; ++j) acc[i][j] = zero4();
-        if (nk > 1) issue(m0, 1, 0);
-        for (int kt = 0; kt < nk; ++kt) {
-            // this wave's pieces of step kt have landed when at most those of step kt + 1 are outstanding
-            if (kt + 1 < nk) { if (wave < 4) wait_vmcnt<LW + 1>(); else wait_vmcnt<LW>(); }
-            else wait_vmcnt<0>();
-            __builtin_amdgcn_s_barrier();                                // everybody's pieces landed; everybody is done reading step kt - 1
-            if (kt + 2 < nk) issue(m0, kt + 2, (kt + 4) % 3);            // into the slot step kt - 1 just left
-            const char* sb = smem + ((kt + 2) % 3) * SLOT;
-            s16x8 af[FM], bfr[FN];
-#pragma unroll
-            for (int i = 0; i < FM; ++i) af[i] = *reinterpret_cast<const s16x8*>(sb + i * 1024 + f_off);
-#pragma unroll
-            for (int j = 0; j < FN; ++j) bfr[j] = *reinterpret_cast<const s16x8*>(sb + A_BYTES + (wave * FN + j) * 1024 + f_off);
-#pragma unroll
-            for (int j = 0; j < FN; ++j)
-#pragma unroll
-                for (int i = 0; i < FM; ++i) acc[i][j] = BRN_MFMA_16X16X32(bfr[j], af[i], acc[i][j]);
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();                                    // every fragment read of the tile is done: the ring is free
-        const bool more = t + nw < t_hi;
-        if (more) issue((t + nw) * RBM, 0, 2);                           // the next tile's first K step flies during the epilogue (slot 2 is not touched by it)
-        // ---- epilogue: two 32-row halves through smem[0, HALF_BYTES) ----
-        const int er = tid >> 4, ec = tid & 15;                          // read-back: row of the half, first chunk (then + 16 k)
-        float* Cf = reinterpret_cast<float*>(p.C);
-        const float* Rf = reinterpret_cast<const float*>(p.R);
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-            const int m = m0 + half * 32 + er, mc = min(m, p.M - 1);
-            f32x4 rr[CPL];
-#pragma unroll
-            for (int k = 0; k < CPL; ++k) rr[k] = *reinterpret_cast<const f32x4*>(Rf + (long)mc * p.ldr + p.r_coff + (ec + 16 * k) * 4);
-#pragma unroll
-            for (int ii = 0; ii < 2; ++ii) {
-                const int i = 2 * half + ii, row = 16 * ii + (lane & 15);
-#pragma unroll
-                for (int j = 0; j < FN; ++j) {
-                    const int col = wave * WCOL + 16 * j + 4 * (lane >> 4);
-                    f32x4 bias4 = p.bias ? *reinterpret_cast<const f32x4*>(p.bias + col) : zero4();
-                    const int ch = col >> 2;
-                    *reinterpret_cast<f32x4*>(smem + row * (NC * 4) + (((ch & ~15) | ((ch ^ row) & 15)) << 4)) = acc[i][j] + bias4;
-                }
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            f32x4 xv[CPL];
-            float sum = 0.f;
-#pragma unroll
-            for (int k = 0; k < CPL; ++k) {
-                const int ch = ec + 16 * k;
-                xv[k] = *reinterpret_cast<const f32x4*>(smem + er * (NC * 4) + (((ch & ~15) | ((ch ^ er) & 15)) << 4)) + rr[k];
-                sum += (xv[k][0] + xv[k][1]) + (xv[k][2] + xv[k][3]);
-            }
-            if (m < p.M) {
-#pragma unroll
-                for (int k = 0; k < CPL; ++k) *reinterpret_cast<f32x4*>(Cf + (long)m * p.ldc + p.c_coff + (ec + 16 * k) * 4) = xv[k];
-            }
-            sum += __shfl_xor(sum, 1); sum += __shfl_xor(sum, 2); sum += __shfl_xor(sum, 4); sum += __shfl_xor(sum, 8);
-            const float mean = sum / (float)NC;
-            float sq = 0.f;
-#pragma unroll
-            for (int k = 0; k < CPL; ++k) {
-                xv[k] = xv[k] - mean;
-                sq += (xv[k][0] * xv[k][0] + xv[k][1] * xv[k][1]) + (xv[k][2] * xv[k][2] + xv[k][3] * xv[k][3]);
-            }
-            sq += __shfl_xor(sq, 1); sq += __shfl_xor(sq, 2); sq += __shfl_xor(sq, 4); sq += __shfl_xor(sq, 8);
-            const float rstd = 1.0f / sqrtf(sq / (float)NC + eps);
-            if (m < p.M) {
-#pragma unroll
-                for (int k = 0; k < CPL; ++k) {
-                    const int c0 = (ec + 16 * k) * 4;
-                    const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + c0), bt = *reinterpret_cast<const f32x4*>(beta + c0);
-                    const f32x4 o = xv[k] * rstd * gm + bt;
-                    const u32x2_b ob = {pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3])};
-                    *reinterpret_cast<u32x2_b*>(Y + (long)m * ldy + c0) = ob;
-                }
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();                               // the half is free again (second half; after it: the K loop's slots 0 / 1)
-        }
-    }
-}
-bool gemm_rowln_eligible(const GemmParams& p) {
-    return p.mode == GEMM_DENSE && p.Wp && (p.N == 768 || p.N == 384) && p.K >= 64 && (p.K % 32) == 0 && p.c_f32 && p.R && p.r_f32 && !p.scale && !p.bbias &&
-           p.act == ACT_NONE && ((p.lda | p.a_coff) & 7) == 0 && ((p.ldc | p.c_coff | p.ldr | p.r_coff) & 3) == 0 && p.M >= 8192 && p.wp_rows >= p.N &&
-           p.wp_ld >= p.K && (p.wp_ld & 7) == 0 && (double)p.wp_ld * 2.0 * p.N < 2147483648.0 && (double)p.lda * 2.0 * 64 < 2147483648.0;
-}
-hipError_t launch_gemm_rowln(const GemmParams& p, const float* gamma, const float* beta, float eps, void* y_bf16, int ldy, hipStream_t s) {
-    if (!BRN_S16_SELF(gemm_rowln_eligible)(p) || !gamma || !beta || !y_bf16 || (ldy & 3)) return hipErrorInvalidValue;
-    const int tiles = (p.M + 63) / 64;
-    int g = launch_cus();
-    if (g > tiles) g = (tiles + 7) / 8 * 8;
-    dim3 grid(g), block(512);
-    if (p.N == 768) hipLaunchKernelGGL(gemm_rowln_bf16_kernel<768>, grid, block, 0, s, p, gamma, beta, eps, reinterpret_cast<s16_t*>(y_bf16), ldy);
-    else hipLaunchKernelGGL(gemm_rowln_bf16_kernel<384>, grid, block, 0, s, p, gamma, beta, eps, reinterpret_cast<s16_t*>(y_bf16), ldy);
-    return hipGetLastError();
-}
-
-bool gemm_wstat_ln_eligible(const GemmParams& p) {
-    return p.mode == GEMM_DENSE && p.Wp && p.K == 192 && p.N == 192 && p.c_f32 && p.R && p.r_f32 && !p.scale && !p.bbias && p.act == ACT_NONE &&
-           ((p.lda | p.a_coff) & 7) == 0 && ((p.ldc | p.c_coff | p.ldr | p.r_coff) & 3) == 0 && p.M >= 32768 && (long)p.lda * 2 * 64 < 0x7fffffffL;
-}
-hipError_t launch_gemm_wstat_ln(const GemmParams& p, const float* gamma, const float* beta, float eps, void* y_bf16, int ldy, hipStream_t s) {
-    if (!BRN_S16_SELF(gemm_wstat_ln_eligible)(p) || !gamma || !beta || !y_bf16 || (ldy & 3)) return hipErrorInvalidValue;
-    dim3 grid(8 * (launch_cus() * 2 / 8)), block(256);
-    hipLaunchKernelGGL(gemm_wstat_ln_bf16_kernel, grid, block, 0, s, p, gamma, beta, eps, reinterpret_cast<s16_t*>(y_bf16), ldy);
-    return hipGetLastError();
-}
-
-bool gemm_wstat_eligible(const GemmParams& p) {
-    // (N / 192 column groups share the chip's workgroup slots: beyond that many groups there is no walker left per group, and the
-    // tiled kernel serves the shape)
-    return p.mode == GEMM_DENSE && p.Wp && (p.K == 192 || p.K == 384) && p.N >= 192 && (p.N % 192) == 0 && p.N / 192 <= launch_cus() * WSTAT_WG_PER_CU / 8 &&
-           !p.c_f32 && !p.R && !p.scale && !p.bbias &&
-           ((p.lda | p.a_coff | p.ldc | p.c_coff) & 7) == 0 && p.M >= 32768 && (long)p.lda * 2 * 64 < 0x7fffffffL;
-}
-hipError_t launch_gemm_wstat(const GemmParams& p, hipStream_t s) {
-    if (!BRN_S16_SELF(gemm_wstat_eligible)(p)) return hipErrorInvalidValue;
-    const int G = p.N / 192;
-    const int nw = (launch_cus() * WSTAT_WG_PER_CU / 8) / G;
-    if (nw < 1) return hipErrorInvalidValue;
-    dim3 grid(8 * G * nw), block(256);
-    if (p.K == 384) {
-        if (p.act == ACT_GELU_ERF) hipLaunchKernelGGL((gemm_wstat_bf16_kernel<6, ACT_GELU_ERF, 32>), grid, block, 0, s, p);
-        else if (p.act == ACT_RELU) hipLaunchKernelGGL((gemm_wstat_bf16_kernel<6, ACT_RELU, 32>), grid, block, 0, s, p);
-        else hipLaunchKernelGGL((gemm_wstat_bf16_kernel<6, ACT_NONE, 32>), grid, block, 0, s, p);
-        return hipGetLastError();
-    }
-    if (p.act == ACT_GELU_ERF) hipLaunchKernelGGL((gemm_wstat_bf16_kernel<3, ACT_GELU_ERF>), grid, block, 0, s, p);
-    else if (p.act == ACT_RELU) hipLaunchKernelGGL((gemm_wstat_bf16_kernel<3, ACT_RELU>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((gemm_wstat_bf16_kernel<3, ACT_NONE>), grid, block, 0, s, p);
-    return hipGetLastError();
-}
 
 // split-K second pass for the bf16 mode: fixed-order sum of the fp32 slices + the epilogue, bf16 (or fp32) out
 __global__ void splitk_reduce_bf16_kernel(const GemmParams p) {
@@ -1274,7 +745,4 @@ hipError_t launch_gemm_bf16(const GemmParams& p_in, const GemmPlan& pl, float* w
     return hipGetLastError();
 }
 
-#if BRN_S16_F16
-}  // namespace hf
-#endif
-}  // namespace brn
+BRN_S16_END

@@ -1,6 +1,6 @@
 // gemm_common.h — device helpers shared by the GEMM-shaped kernel files (gemm_f32 / gemm_split / gemm_probes / gemm_bf16 / gemm_planes /
-// deform_bf16): vector types, masked loads, the tile order, the three erf-GELU forms and the fp32 epilogue.  Everything lives in namespace
-// brn; the files compiled a second time inside brn::hf (gemm_bf16.hip, deform_bf16.hip) see these names from there.
+// rows_bf16 / deform_bf16): vector types, masked loads, the tile order, the three erf-GELU forms and the fp32 epilogue.  Everything lives in
+// namespace brn; the files compiled a second time inside brn::hf (gemm_bf16.hip, rows_bf16.hip, deform_bf16.hip) see these names from there.
 #pragma once
 #include "../brn_kernels.h"
 #include "split_planes.h"   // f32x4, the bf16 vector types and the P-layout stores
@@ -9,6 +9,7 @@ namespace brn {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ f32x4 zero4() { f32x4 z = {0.f, 0.f, 0.f, 0.f}; return z; }
 // a load the optimiser may not sink under the predicate that later selects its value: hipcc turns `ok ? *p : 0` (and
@@ -66,7 +67,7 @@ __device__ __forceinline__ float gelu_erf_as(float x) {
     const float one_plus_erf = x < 0.f ? q : 2.0f - q;
     return 0.5f * x * one_plus_erf;
 }
-// gelu_erf_bf16out: for a result that is rounded to bf16 right away (gemm_bf16.hip: epilogue flavour 0 and the weight-stationary kernels).
+// gelu_erf_bf16out: for a result that is rounded to bf16 right away (gemm_bf16.hip: epilogue flavour 0; rows_bf16.hip: the weight-stationary kernel).
 // fc1's epilogue is VALU time the persistent workgroup cannot hide behind MFMAs (20 % of an fc1 launch with the round-2 form: erfc by
 // Abramowitz-Stegun 7.1.25, 3 terms = 9 VALU + v_rcp + v_exp, |error| < 2.6e-5), so the form is chosen by issue slots.  Round 4: gelu_erf's
 // form with P a degree-5 polynomial (P(u) ~ -1 - 1.15 u - 0.46 u^2 ...) — 1 clamp + 5 fma + v_exp + max + fma = 12 issue slots instead of

@@ -524,19 +524,32 @@ def test_short_k_weight_stationary_gemm_bf16_mode(gpu, C, H, W, O, act):
     qkv and fc1 GEMMs at batch >= 4) through a 1x1 conv on a bf16 map: full and ragged row tiles (M % 64, M % 32 != 0), 1 ... 8 column
     groups, bias, GELU / ReLU.  Exact-operand reference; the output map is bf16: one bf16 ulp + 1e-5 (fp32 accumulation; the bf16-output
     GELU, 2^P(|x|) with P of degree 5, is within 3e-6 of erf-GELU: the erfc series it replaced needed 4e-5 here)."""
+    _check_short_k_weight_stationary_gemm("bf16", C, H, W, O, act)
+
+
+def _check_short_k_weight_stationary_gemm(s16, C, H, W, O, act):
     from candle_birefnet_amd import ops
     x, w, b = rnd(1, C, H, W, seed=1), rnd(O, C, 1, 1, seed=2, std=C ** -0.5), rnd(O, seed=3, std=0.1)
-    ops.set_compute("bf16")
+    ops.set_compute(s16)
     try:
         y = ops.conv2d(x, w, b, act=act)
         y2 = ops.conv2d(x, w, b, act=act)
     finally:
         ops.set_compute("f32")
     np.testing.assert_array_equal(y, y2)
-    ref = F.conv2d(torch.from_numpy(_bf16_round(x)), torch.from_numpy(_bf16_round(w)), torch.from_numpy(b).double())
+    ref = F.conv2d(torch.from_numpy(_bf16_round(x, s16)), torch.from_numpy(_bf16_round(w, s16)), torch.from_numpy(b).double())
     ref = (F.gelu(ref) if act == "gelu_erf" else F.relu(ref) if act == "relu" else ref).numpy()
     err = np.abs(np.asarray(y, np.float64) - ref)
-    assert (err <= 2.0 ** -8 * np.abs(ref) + 1e-5).all(), f"max abs err {err.max():.3e}"
+    print(f"weight-stationary GEMM {s16} C{C} {H}x{W} O{O} {act}: max abs err {err.max():.3e}, max err / (ulp |ref| + 1e-5) {(err / (S16_ULP[s16] * np.abs(ref) + 1e-5)).max():.3f}")
+    assert (err <= S16_ULP[s16] * np.abs(ref) + 1e-5).all(), f"max abs err {err.max():.3e}"
+
+
+@pytest.mark.parametrize("C,H,W,O,act", [(192, 181, 183, 192, "relu"), (384, 181, 183, 384, "gelu_erf")])
+def test_short_k_weight_stationary_gemm_f16_mode(gpu, C, H, W, O, act):
+    """the fp16-storage build of gemm_wstat_bf16_kernel (rows_bf16.hip compiled with fp16 as the 16-bit type), at the smallest shapes that
+    reach both tile heights and their ragged last tile (M = 33123: M % 64, M % 32 != 0).  The bound of the bf16 test with the stored
+    value's ulp swapped (2^-11 |ref| for 2^-8 |ref|): the accumulation is the same fp32, only the output rounding differs."""
+    _check_short_k_weight_stationary_gemm("f16", C, H, W, O, act)
 
 
 def test_conv2d_nan_stays_local(gpu):
@@ -676,26 +689,39 @@ def test_linear_residual_layer_norm_bf16_mode(gpu, M, K, N):
     and above one round of workgroups), gemm_wstat_ln_bf16_kernel for N = 192, GEMM + LayerNorm launches otherwise (M below the fused
     kernel's threshold, N = 1536).  Exact-operand reference: A and W rounded to bf16, everything else fp64; x is an fp32 matrix
     (accumulation noise), y a bf16-rounded one (one ulp + the LayerNorm arithmetic in fp32)."""
+    _check_linear_residual_layer_norm("bf16", M, K, N)
+
+
+def _check_linear_residual_layer_norm(s16, M, K, N):
     from candle_birefnet_amd import ops
     a, w, b = rnd(M, K, seed=1), rnd(N, K, seed=2, std=K ** -0.5), rnd(N, seed=3, std=0.1)
     r = rnd(M, N, seed=4, std=2.0)
     g, bt = (1.0 + rnd(N, seed=5, std=0.05)).astype(np.float32), rnd(N, seed=6, std=0.02)
-    ops.set_compute("bf16")
+    ops.set_compute(s16)
     try:
         xo, yo = ops.linear_residual_layer_norm(a, w, b, r, g, bt)
         xo2, yo2 = ops.linear_residual_layer_norm(a, w, b, r, g, bt)
     finally:
         ops.set_compute("f32")
     np.testing.assert_array_equal(xo, xo2); np.testing.assert_array_equal(yo, yo2)
-    xr = _bf16_round(a) @ _bf16_round(w).T + b.astype(np.float64) + r.astype(np.float64)
+    xr = _bf16_round(a, s16) @ _bf16_round(w, s16).T + b.astype(np.float64) + r.astype(np.float64)
     mu = xr.mean(-1, keepdims=True)
     var = ((xr - mu) ** 2).mean(-1, keepdims=True)
     yr = (xr - mu) / np.sqrt(var + 1e-5) * g.astype(np.float64) + bt.astype(np.float64)
     ex = np.abs(np.asarray(xo, np.float64) - xr).max()
     ey = np.abs(np.asarray(yo, np.float64) - yr)
-    print(f"linear+residual+LN bf16 M{M} K{K} N{N}: x max abs err {ex:.2e} (|x| max {np.abs(xr).max():.1f}), y max abs err {ey.max():.2e}")
+    print(f"linear+residual+LN {s16} M{M} K{K} N{N}: x max abs err {ex:.2e} (|x| max {np.abs(xr).max():.1f}), y max abs err {ey.max():.2e}, "
+          f"max y err / (ulp |y| + 1e-4) {(ey / (S16_ULP[s16] * np.abs(yr) + 1e-4)).max():.3f}")
     assert ex <= 2e-5 * max(1.0, np.abs(xr).max())
-    assert (ey <= 2.0 ** -8 * np.abs(yr) + 1e-4).all()
+    assert (ey <= S16_ULP[s16] * np.abs(yr) + 1e-4).all()
+
+
+@pytest.mark.parametrize("M,K,N", [(33000, 192, 192), (8192 + 37, 768, 768), (8200, 1536, 384)])
+def test_linear_residual_layer_norm_f16_mode(gpu, M, K, N):
+    """the fp16-storage builds of gemm_wstat_ln_bf16_kernel (N = 192) and gemm_rowln_bf16_kernel<768> / <384>, each with a ragged last
+    tile.  The bounds of the bf16 test with the stored value's ulp swapped (2^-11 |y| for 2^-8 |y|); the absolute term and the bound on
+    the fp32 x are the same: the accumulation is the same fp32, only the rounding of y differs."""
+    _check_linear_residual_layer_norm("f16", M, K, N)
 
 
 def test_linear_residual_layer_norm_fp32_modes(gpu):
