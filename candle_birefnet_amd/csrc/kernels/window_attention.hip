@@ -18,6 +18,7 @@
 #include "attention_mfma.h"
 #include "window_geometry.h"
 #include "window_attention_select.h"
+#include "window_attention_index.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -54,12 +55,15 @@ template <int WSZ = WS>
 __device__ __forceinline__ bool att_has_mask(const WindowAttnParams& p, int wr, int wc) {
     return p.shift > 0 && ((wr == p.Hp / WSZ - 1) | (wc == p.Wp / WSZ - 1));
 }
-// relative position index (swin.rs:182-184) of (query (qi, qj), key) = (qi-ki+W-1)*(2W-1) + (qj-kj+W-1) = att_qbase(qi, qj) - (key + (W-1)*(key/W));
-// att_qrev: the same base into a table stored reversed (rev[j] = table[(2W-1)^2 - 1 - j]), where the index GROWS with the key
-template <int WSZ = WS>
-__device__ __forceinline__ int att_qbase(int qi, int qj) { return (qi + WSZ - 1) * (2 * WSZ - 1) + qj + WSZ - 1; }
-template <int WSZ = WS>
-__device__ __forceinline__ int att_qrev(int qi, int qj) { return (2 * WSZ - 1) * (2 * WSZ - 1) - 1 - att_qbase<WSZ>(qi, qj); }
+// relative position index (swin.rs:182-184) of a (query, key) pair: att_qbase, att_qrev, att_koff, att_key0 (kernels/window_attention_index.h)
+// v_max3_f32 spelled out: in the bf16 kernel fmaxf came with a canonicalising v_max x, x in front of every maximum (the scores are MFMA /
+// fma results: never signalling; in the split kernel hipcc forms the same 18 v_max3_f32 per tile from fmaxf as well).  A maximum is exact,
+// so for finite scores the grouping does not change the result; a NaN score still reaches the output through exp and the row sum
+__device__ __forceinline__ float max3f(float a, float b, float c) {
+    float r;
+    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
 
 // ---- split and bf16 kernels: 16-bit operands (E = __bf16 or _Float16), LDS images Kp[key][32 d] and Vt[d][VT_LD keys] of
 // kernels/attention_mfma.h (the split kernel's row = plane * NTOK + key: NTOK % 16 == 0, so the plane does not change the swizzle) ----
@@ -237,8 +241,7 @@ __global__ void __launch_bounds__(NWV * 64) window_attention_f32_kernel(const Wi
             const int qrev = att_qrev<WS>(qt_ / WS, qt_ % WS);
 #pragma unroll
             for (int kt = 0; kt < NT16; ++kt) {
-                const int key0 = kt * 16 + g * 4;
-                const float* tb = tab_s + qrev + key0 + (WS - 1) * (key0 / WS);
+                const float* tb = tab_s + qrev + att_koff<WS>(att_key0(kt, g));
 #pragma unroll
                 for (int r = 0; r < 4; ++r) st[kt][r] = fmaf(st[kt][r], ATT_LOG2E, tb[r]);
             }
@@ -340,7 +343,11 @@ __global__ void __launch_bounds__(ATT_THREADS) __attribute__((amdgpu_waves_per_e
     __shared__ __attribute__((aligned(16))) __bf16 Kp[NP * NTOK * HD];
     __shared__ __attribute__((aligned(16))) __bf16 Vt[NP * HD * VT_LD];
     constexpr int TABN = (2 * WS - 1) * (2 * WS - 1);
-    __shared__ float tab_s[TABN];
+    // the head's bias column REVERSED, in plain units: rev_s[j] = table[528 - j].  The 4 keys 16 kt + 4 g + {0..3} of a lane lie in one
+    // window row, so their words are rev_s[qrev + koff + 0..3]: one address per key tile (kernels/window_attention_index.h; the largest
+    // index a real query can form is 528)
+    static_assert(WS % 4 == 0 && NTOK % 16 == 0, "the four keys of a lane's tile chunk lie in one window row");
+    __shared__ float rev_s[TABN];
     __shared__ unsigned char rid_s[NTOK];
     __shared__ __attribute__((aligned(16))) float qb_s[HD];    // the head's q bias: what a pad query is (kept out of the loop's registers)
 
@@ -455,19 +462,25 @@ __global__ void __launch_bounds__(ATT_THREADS) __attribute__((amdgpu_waves_per_e
     }
 #pragma unroll
     for (int j = 0; j < 3; ++j)
-        if (tid + j * ATT_THREADS < TABN) tab_s[tid + j * ATT_THREADS] = tbw[j];
+        if (tid + j * ATT_THREADS < TABN) rev_s[TABN - 1 - (tid + j * ATT_THREADS)] = tbw[j];
     if (tid < 64 && li == 0) {
         *reinterpret_cast<f32x4*>(qb_s + g * 8) = qbias0;
         *reinterpret_cast<f32x4*>(qb_s + g * 8 + 4) = qbias1;
     }
     __syncthreads();
 
+    // per key tile: the byte offset of att_koff(16 kt + 4 g), once per workgroup; added to an LDS address the compiler cannot take apart
+    // (window_attention_bf16_kernel: with `rev_s + qrev + koff` it re-associates the array's base out of the sum, four VALU per key tile)
+    typedef __attribute__((address_space(3))) const float lds_cfloat;
+    unsigned koffb[9];
+#pragma unroll
+    for (int kt = 0; kt < 9; ++kt) koffb[kt] = (unsigned)att_koff(att_key0(kt, g)) * 4u;
     for (int qt = wave; qt < ntile; qt += 3) {
         const int slot = qt * 16 + li;
-        const int qtok = qtok_n;
+        const int qtok = qtok_n;                                     // a real token of the window, also for a slot past nq (load_q clamps)
         const int qsrc = qsrc_n;
         const int qrid = rid_s[qtok];
-        const int qbase = att_qbase(qtok / WS, qtok % WS);
+        const int qrev = att_qrev(qtok / WS, qtok % WS);
         // Q fragment (B operand of S^T = K Q^T): d = 8g .. 8g+7 of this lane's query, scaled (swin.rs:278), split
         bf16x8 qf[NP];
         {
@@ -488,18 +501,26 @@ __global__ void __launch_bounds__(ATT_THREADS) __attribute__((amdgpu_waves_per_e
             st[kt] = att_plane_mfma<NP, H>(kf, qf, f32x4{0.f, 0.f, 0.f, 0.f});
             if (kt % 3 == 2) __builtin_amdgcn_sched_barrier(0);
         }
-        float mx = ATT_NEG;
+        // + relative position bias (swin.rs:284-285), + SW-MSA mask (swin.rs:288-297, value -100 swin.rs:651): per score the same
+        // operations on the same operands as with one table index per score
+        unsigned tbq = (unsigned)(unsigned long)(lds_cfloat*)(rev_s + qrev);
+        asm volatile("" : "+v"(tbq));
 #pragma unroll
         for (int kt = 0; kt < 9; ++kt) {
+            lds_cfloat* tb = (lds_cfloat*)(unsigned long)(tbq + koffb[kt]);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int key = kt * 16 + g * 4 + r;
-                float sv = H ? fmaf(st[kt][r], 1.0f / (ATT_H_QKV * ATT_H_QKV), tab_s[qbase - key - 11 * (key / WS)]) : st[kt][r] + tab_s[qbase - key - 11 * (key / WS)];
-                if (has_mask) sv += ((int)rid_s[key] != qrid) ? -100.0f : 0.0f;
-                st[kt][r] = sv;
-                mx = fmaxf(mx, sv);
+            for (int r = 0; r < 4; ++r) st[kt][r] = H ? fmaf(st[kt][r], 1.0f / (ATT_H_QKV * ATT_H_QKV), tb[r]) : st[kt][r] + tb[r];
+        }
+        if (has_mask) {                                              // (hipcc reads the four ids of a chunk as one word and compares its bytes)
+#pragma unroll
+            for (int kt = 0; kt < 9; ++kt) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) st[kt][r] += ((int)rid_s[att_key0(kt, g) + r] != qrid) ? -100.0f : 0.0f;
             }
         }
+        float mx = ATT_NEG;
+#pragma unroll
+        for (int kt = 0; kt < 9; ++kt) mx = max3f(max3f(mx, st[kt][0], st[kt][1]), st[kt][2], st[kt][3]);
         mx = att_group_max(mx);
         float sum = 0.f;
 #pragma unroll
@@ -543,12 +564,6 @@ __global__ void __launch_bounds__(ATT_THREADS) __attribute__((amdgpu_waves_per_e
 // (16-byte loads of 8 bf16, no split) and that q's scale is applied to the fp32 scores instead of to q (q is already
 // rounded to bf16: scaling the accumulator avoids a second rounding; identical in real arithmetic, swin.rs:278).
 // =====================================================================================================================
-// v_max3_f32 without the canonicalising v_max x, x that fmaxf puts in front of it (the scores are MFMA / fma results: never signalling)
-__device__ __forceinline__ float max3f(float a, float b, float c) {
-    float r;
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
 template <typename E>
 __device__ __forceinline__ vec8<E> bias8_s16(const float* bp) {
     vec8<E> r;
@@ -674,7 +689,7 @@ __global__ void __launch_bounds__(ATT_BF16_HPW * ATT_THREADS) __attribute__((amd
     typedef __attribute__((address_space(3))) const float lds_cfloat;
     unsigned koffb[9];
 #pragma unroll
-    for (int kt = 0; kt < 9; ++kt) { const int key0 = kt * 16 + g * 4; koffb[kt] = (unsigned)(key0 + 11 * (key0 / WS)) * 4u; }
+    for (int kt = 0; kt < 9; ++kt) koffb[kt] = (unsigned)att_koff(att_key0(kt, g)) * 4u;
 #pragma unroll
     for (int u = 0; u < 3; ++u) {
         const int qt = wv + 3 * u;
