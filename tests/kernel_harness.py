@@ -1,4 +1,4 @@
-"""Loader of the kernel harness: tests/kernel_harness/harness.cpp + kernels/elementwise.hip + kernels/layernorm.hip, compiled from where
+"""Loader of the test harnesses (class Harness; the GEMM one is set up in gemm_harness.py) and the kernel harness itself: tests/kernel_harness/harness.cpp + kernels/elementwise.hip + kernels/layernorm.hip, compiled from where
 they live with the Makefile's own CXXFLAGS into tests/kernel_harness/kernel_harness_<hash>.so, and called through ctypes with raw device
 pointers (torch tensors by data_ptr()).  The hash covers the three sources, every header they include and the flags, so a stale object
 is never loaded.  With hipcc the object is built on first use; without it an up-to-date object is loaded if there is one; otherwise the
@@ -71,25 +71,52 @@ def _with_headers(paths):
     return sorted(seen)
 
 
+class Harness:
+    """One shared object tests/<name>/<name>_<hash>.so: `sources` (the first is the harness file under tests/<name>/, the others are kernel
+    files taken from where they live) compiled together with the Makefile's own flags"""
+
+    def __init__(self, name, sources):
+        self.name, self.sources, self.hdir = name, list(sources), os.path.dirname(sources[0])
+
+    def object_path(self):
+        h = hashlib.sha256(" ".join(build_flags()[:-1]).encode())      # (not the -I path: it differs between checkouts)
+        for f in _with_headers(self.sources):
+            h.update(os.path.relpath(f, ROOT).encode() + b"\0" + open(f, "rb").read() + b"\0")
+        return os.path.join(self.hdir, f"{self.name}_{h.hexdigest()[:16]}.so")
+
+    def build(self):
+        """compile the object if it is not there yet; returns its path (needs hipcc)"""
+        out = self.object_path()
+        if not os.path.exists(out):
+            tmp = os.path.join(self.hdir, f"tmp{os.getpid()}_{self.name}.so")       # (git-ignored like the object itself)
+            subprocess.run([hipcc(), *build_flags(), "-x", "hip", "-shared", *self.sources, "-o", tmp, "-Wl,-rpath,/opt/rocm/lib"],
+                           check=True, capture_output=True, timeout=900)
+            os.replace(tmp, out)
+            for old in glob.glob(os.path.join(self.hdir, f"{self.name}_*.so")):
+                if old != out:
+                    os.remove(old)
+        return out
+
+    def load(self):
+        """(the ctypes library, "built" or "loaded"); skips the calling test when the object can be neither built nor found"""
+        out = self.object_path()
+        route = "loaded" if os.path.exists(out) else "built"
+        if not os.path.exists(out):
+            if hipcc() is None:
+                pytest.skip(f"{self.name.replace('_', ' ')}: no hipcc and no up-to-date {os.path.basename(out)}")
+            self.build()
+        return ctypes.CDLL(out), route
+
+
+KERNEL_HARNESS = Harness("kernel_harness", SOURCES)
+
+
 def object_path():
-    h = hashlib.sha256(" ".join(build_flags()[:-1]).encode())      # (not the -I path: it differs between checkouts)
-    for f in _with_headers(SOURCES):
-        h.update(os.path.relpath(f, ROOT).encode() + b"\0" + open(f, "rb").read() + b"\0")
-    return os.path.join(HDIR, f"kernel_harness_{h.hexdigest()[:16]}.so")
+    return KERNEL_HARNESS.object_path()
 
 
 def build():
-    """compile the object if it is not there yet; returns its path (needs hipcc)"""
-    out = object_path()
-    if not os.path.exists(out):
-        tmp = os.path.join(HDIR, f"tmp{os.getpid()}_kernel_harness.so")       # (git-ignored like the object itself)
-        subprocess.run([hipcc(), *build_flags(), "-x", "hip", "-shared", *SOURCES, "-o", tmp, "-Wl,-rpath,/opt/rocm/lib"],
-                       check=True, capture_output=True, timeout=900)
-        os.replace(tmp, out)
-        for old in glob.glob(os.path.join(HDIR, "kernel_harness_*.so")):
-            if old != out:
-                os.remove(old)
-    return out
+    return KERNEL_HARNESS.build()
 
 
 ROUTE = None     # "built" or "loaded", once lib() has run
@@ -99,13 +126,7 @@ ROUTE = None     # "built" or "loaded", once lib() has run
 def lib():
     """the loaded harness; skips the calling test when it can be neither built nor found"""
     global ROUTE
-    out = object_path()
-    ROUTE = "loaded" if os.path.exists(out) else "built"
-    if not os.path.exists(out):
-        if hipcc() is None:
-            pytest.skip(f"kernel harness: no hipcc and no up-to-date {os.path.basename(out)}")
-        build()
-    so = ctypes.CDLL(out)
+    so, ROUTE = KERNEL_HARNESS.load()
     for name, sig in SIGNATURES.items():
         fn = getattr(so, "kh_" + name)
         fn.argtypes = [_CTYPES[c] for c in sig]
@@ -123,16 +144,20 @@ def launcher_names():
     return sorted(set(names))
 
 
+def synchronize(name):
+    try:
+        torch.cuda.synchronize()
+    except RuntimeError as e:          # a device fault: nothing more may run on this GPU from this process
+        pytest.exit(f"{name}: {e}", returncode=3)
+
+
 def call(name, *args):
     """run one launcher on the null stream and synchronise; args are the wrapper's without the stream; returns the hipError_t"""
     conv = [a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args]
     conv.insert(SIGNATURES[name].index("s"), None)
     assert len(conv) == len(SIGNATURES[name]), f"{name}: {len(conv)} arguments for {SIGNATURES[name]}"
     rc = getattr(lib(), "kh_" + name)(*conv)
-    try:
-        torch.cuda.synchronize()
-    except RuntimeError as e:          # a device fault: nothing more may run on this GPU from this process
-        pytest.exit(f"{name}: {e}", returncode=3)
+    synchronize(name)
     return rc
 
 

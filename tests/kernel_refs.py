@@ -1,5 +1,5 @@
 """High-precision references for the kernel-harness tests (fp64 torch / numpy) and the emulation of the operand-plane formats of
-kernels/split_planes.h.  Checked on the CPU by test_kernel_refs_cpu.py."""
+kernels/split_planes.h.  Checked on the CPU by test_kernel_refs_cpu.py and test_gemm_refs_cpu.py."""
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -119,3 +119,104 @@ def bf16_bits_to_f64(b):
 
 def f16_bits_to_f64(b):
     return np.asarray(b, np.uint16).view(np.float16).astype(np.float64)
+
+
+# ---- the GEMMs of kernels/gemm_f32.hip and kernels/gemm_split.hip ----
+# The plane products a kernel keeps, as (A plane, W plane): three bf16 planes drop ml, lm, ll; two drop mm; the fp16 pair drops ll.
+KEPT = {
+    "bf16x3": ((0, 0), (0, 1), (1, 0), (0, 2), (2, 0), (1, 1)),
+    "bf16x2": ((0, 0), (0, 1), (1, 0)),
+    "h2": ((0, 0), (0, 1), (1, 0)),
+}
+ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
+
+
+def gemm_planes_ref(a_planes, w_planes, kept, out_scale=1.0):
+    """a_planes [NP, M, K], w_planes [NP, N, K] (plane VALUES) -> fp64 [M, N]: out_scale * the sum over `kept` of A_pa W_pb^T.  Every product
+    of two 16-bit values is exact in fp64; out_scale is the power of two 1 / (a_scale w_scale) of the fp16 pair."""
+    a, w = np.asarray(a_planes, np.float64), np.asarray(w_planes, np.float64)
+    acc = np.zeros((a.shape[1], w.shape[1]), np.float64)
+    for pa, pb in kept:
+        acc += a[pa] @ w[pb].T
+    return acc * float(out_scale)
+
+
+def gemm_epilogue_ref(acc, bias=None, bbias=None, bbias_rows=0, scale=None, shift=None, act=ACT_NONE, R=None):
+    """GemmParams' epilogue in fp64, in its documented order: bias[n], bbias[m / bbias_rows][n], scale and shift, activation, residual"""
+    v = np.asarray(acc, np.float64).copy()
+    if bias is not None:
+        v += np.asarray(bias, np.float64)[None, :]
+    if bbias is not None:
+        v += np.asarray(bbias, np.float64)[np.arange(v.shape[0]) // bbias_rows]
+    if scale is not None:
+        v = v * np.asarray(scale, np.float64)[None, :] + np.asarray(shift, np.float64)[None, :]
+    if act == ACT_RELU:
+        v = np.maximum(v, 0.0)
+    elif act == ACT_GELU:
+        v = F.gelu(torch.from_numpy(v)).numpy()                       # erf form, fp64
+    if R is not None:
+        v += np.asarray(R, np.float64)
+    return v
+
+
+def im2col_nhwc(x, kh, kw, stride, pad, dil=1):
+    """GEMM_CONV_NHWC's rows: x [B, H, W, C] -> ([B Hout Wout, kh kw C], Hout, Wout), K order (ky, kx, ci), zero outside the map"""
+    x = np.asarray(x)
+    B, H, W, C = x.shape
+    Ho, Wo = (H + 2 * pad - dil * (kh - 1) - 1) // stride + 1, (W + 2 * pad - dil * (kw - 1) - 1) // stride + 1
+    xp = np.zeros((B, H + 2 * pad, W + 2 * pad, C), x.dtype)
+    xp[:, pad:pad + H, pad:pad + W] = x
+    taps = [xp[:, ky * dil:ky * dil + (Ho - 1) * stride + 1:stride, kx * dil:kx * dil + (Wo - 1) * stride + 1:stride]
+            for ky in range(kh) for kx in range(kw)]
+    return np.stack(taps, axis=3).reshape(B * Ho * Wo, kh * kw * C), Ho, Wo
+
+
+def im2col_nchw(x, kh, kw, stride, pad, kpad):
+    """GEMM_GATHER_NCHW's rows: x [B, C, H, W] -> ([B Hout Wout, kpad], Hout, Wout), K order (ci, ky, kx), zero outside the map and in [C kh kw, kpad)"""
+    x = np.asarray(x)
+    cols, Ho, Wo = im2col_nhwc(x.transpose(0, 2, 3, 1), kh, kw, stride, pad)
+    B, C = x.shape[:2]
+    cols = cols.reshape(-1, kh * kw, C).transpose(0, 2, 1).reshape(B * Ho * Wo, C * kh * kw)
+    out = np.zeros((cols.shape[0], kpad), x.dtype)
+    out[:, :C * kh * kw] = cols
+    return out, Ho, Wo
+
+
+# Plane-exact data: sign * (1 + j 2^-9 + l 2^-18), j in {0, 1}, l in {0, j} ("bf16x3": the planes are 1, j 2^-9, l 2^-18 — an l without its j
+# would sit in the MIDDLE plane), sign * (1 + j 2^-9) ("bf16x2", "f32") or sign * (1 + j 2^-12) ("h2": fp16 planes 1, j 2^-12 of the unscaled
+# value).  Every kept plane product, and every product of two "f32" values, is then a multiple of UNIT[kind] (times the power-of-two operand
+# scales), so any partial sum of them in any order is exact in fp32 as long as its magnitude stays below 2^24 UNIT: plane_exact_bound.
+UNIT = {"f32": 2.0 ** -18, "bf16x3": 2.0 ** -18, "bf16x2": 2.0 ** -9, "h2": 2.0 ** -12}
+
+
+def plane_exact_values(shape, kind, seed):
+    g = np.random.default_rng(seed)
+    sign = g.integers(0, 2, shape) * 2.0 - 1.0
+    j = g.integers(0, 2, shape).astype(np.float64)
+    l = g.integers(0, 2, shape) * j
+    if kind == "h2":
+        v = 1.0 + j * 2.0 ** -12
+    elif kind == "bf16x3":
+        v = 1.0 + j * 2.0 ** -9 + l * 2.0 ** -18
+    else:
+        v = 1.0 + j * 2.0 ** -9
+    return (sign * v).astype(np.float32)
+
+
+def keep_per_row(rows, cols, nkeep, seed):
+    """a 0 / 1 mask [rows, cols] with exactly min(nkeep, cols) ones per row, at random columns"""
+    g = np.random.default_rng(seed)
+    order = np.argsort(g.random((rows, cols)), axis=1)
+    return (order < min(nkeep, cols)).astype(np.float32)
+
+
+def assert_plane_exact(a_rows, w, kind, addends=0.0, scale_max=1.0, scale_min=1.0, post=0.0):
+    """The exactness condition of a plane-exact case, asserted on the CPU: a_rows [M, K] (the rows the kernel contracts: after im2col), w [N, K].
+    max_mn sum_k |a||w| bounds every partial sum of kept products whatever the tile, ring depth or split-K.  The epilogue's operands are
+    multiples of 1/4: bias and bbias (`addends` = the largest |bias| + |bbias|) keep the unit, a power-of-two scale multiplies value and unit
+    (scale_min <= 1 <= scale_max), shift and residual (`post` = the largest |shift| + |R|) are added after it.  Returns the margin (< 1)."""
+    sums = np.abs(np.asarray(a_rows, np.float64)) @ np.abs(np.asarray(w, np.float64)).T
+    top = (sums.max() + addends) * scale_max + post
+    limit = 2.0 ** 24 * UNIT[kind] * scale_min
+    assert top < limit, f"not plane-exact: partial sums reach {top} >= 2^24 x {UNIT[kind] * scale_min}"
+    return top / limit
