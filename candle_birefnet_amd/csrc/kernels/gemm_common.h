@@ -132,6 +132,18 @@ __device__ __forceinline__ TileSlice tile_slice(const GemmParams& p, int kstep) 
     return t;
 }
 
+// Implicit GEMM over channels-last maps: k = (tap, channel), tap = ky * kw + kx.  Cin is a multiple of the K tile, so a K tile lies inside
+// one tap: `tap` and its first channel `ci0`; the tap's place in the window is (ky, kx) x the dilation.
+struct ConvTap { int tap, ci0, ky, kx; };
+__device__ __forceinline__ ConvTap conv_tap_at(const GemmParams& p, int tap, int ci0) {
+    const int ky = tap / p.kw;
+    return ConvTap{tap, ci0, ky, tap - ky * p.kw};
+}
+__device__ __forceinline__ ConvTap conv_tap(const GemmParams& p, int k0) {
+    const int tap = k0 / p.Cin;
+    return conv_tap_at(p, tap, k0 - tap * p.Cin);
+}
+
 // Per-row state of a register-staged A loader, fixed over the K loop.  Dense: base = the row's offset.  Channels-last implicit GEMM
 // (row m = output pixel (b, oy, ox)): base = the offset of image b's window, (iy, ix) = the input pixel under tap (0, 0).
 template <int MODE>
@@ -147,6 +159,30 @@ __device__ __forceinline__ void gather_row_init(const GemmParams& p, int m, bool
         iy = oy * p.stride - p.pad;
         ix = ox * p.stride - p.pad;
         base = (long)b * p.Hin * p.Win * p.lda + p.a_coff;
+    }
+}
+// The register-staged A loader of dense and channels-last implicit-GEMM rows (MODE: GEMM_DENSE or GEMM_CONV_NHWC): floats k0 + 4 kq .. + 3 of
+// a thread's PA rows.  An unconditional load from a clamped address + the keep mask (load4_masked: no exec branch around the load, so the
+// compiler keeps counted vmcnt waits); rows >= M and taps in the padding are masked.
+// (The parameters come by address: behind a reference the compiler speculates the loads of p.Hin / p.Win and drops the short circuit of the
+// bounds test — other code than the three loaders this replaced, profiles/isa_parity_gemm_split.md.)
+template <int MODE, int PA>
+__device__ __forceinline__ void gather_rows_load(const GemmParams* pp, int k0, int kq, const bool (&ok)[PA], const long (&base)[PA], const int (&iy)[PA],
+                                                 const int (&ix)[PA], f32x4 (&qa)[PA], unsigned (&qm)[PA]) {
+    const GemmParams& p = *pp;
+    if (MODE == GEMM_DENSE) {
+#pragma unroll
+        for (int i = 0; i < PA; ++i) qa[i] = load4_masked(p.A + (ok[i] ? base[i] : 0) + k0 + kq * 4, ok[i], qm[i]);
+    } else {
+        const ConvTap t = conv_tap(p, k0);
+        const int dy = t.ky * p.dil, dx = t.kx * p.dil;
+#pragma unroll
+        for (int i = 0; i < PA; ++i) {
+            const int y = iy[i] + dy, x = ix[i] + dx;
+            const bool in = ok[i] && (unsigned)y < (unsigned)p.Hin && (unsigned)x < (unsigned)p.Win;
+            const long off = in ? base[i] + ((long)y * p.Win + x) * p.lda + t.ci0 : (long)p.a_coff;
+            qa[i] = load4_masked(p.A + off + kq * 4, in, qm[i]);
+        }
     }
 }
 

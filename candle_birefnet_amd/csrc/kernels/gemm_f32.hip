@@ -71,23 +71,8 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_f32_kernel(const GemmParams 
         const int k0 = kt * BK;
 #pragma unroll
         for (int i = 0; i < PB; ++i) rb[i] = *reinterpret_cast<const f32x4*>(wrow + (long)i * RPP * p.K + k0);
-        if (MODE == GEMM_DENSE) {
-#pragma unroll
-            for (int i = 0; i < PA; ++i)
-                {   // unconditional load from a clamped address + select: no exec branch, so the compiler keeps counted vmcnt waits
-                    ra[i] = load4_masked(p.A + (a_ok[i] ? a_base[i] : 0) + k0 + kq * 4, a_ok[i], am[i]);
-                }
-        } else if (MODE == GEMM_CONV_NHWC) {
-            const int tap = k0 / p.Cin, ci0 = k0 - tap * p.Cin;
-            const int ky = tap / p.kw, kx = tap - ky * p.kw;
-            const int dy = ky * p.dil, dx = kx * p.dil;
-#pragma unroll
-            for (int i = 0; i < PA; ++i) {
-                const int iy = a_iy[i] + dy, ix = a_ix[i] + dx;
-                const bool ok = a_ok[i] && (unsigned)iy < (unsigned)p.Hin && (unsigned)ix < (unsigned)p.Win;
-                const long off = ok ? a_base[i] + ((long)iy * p.Win + ix) * p.lda + ci0 : (long)p.a_coff;
-                ra[i] = load4_masked(p.A + off + kq * 4, ok, am[i]);
-            }
+        if constexpr (MODE == GEMM_DENSE || MODE == GEMM_CONV_NHWC) {
+            gather_rows_load<MODE>(&p, k0, kq, a_ok, a_base, a_iy, a_ix, ra, am);
         } else if (MODE == GEMM_GATHER_NCHW && p.kw == 4 && p.stride == 4 && p.pad == 0 && p.dil == 1 && (p.Win & 3) == 0 && (reinterpret_cast<unsigned long long>(p.A) & 15) == 0) {
             // PatchEmbed (swin.rs:677: k 4, s 4, no padding) on an image whose width is a multiple of 4: a lane's four k indices
             // k4 .. k4 + 3 are the four kx of one (channel, ky) = 16 contiguous bytes of the image: one unpredicated float4 load from a
@@ -120,8 +105,8 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_f32_kernel(const GemmParams 
                 { f32x4 t = {v[0], v[1], v[2], v[3]}; ra[i] = t; }
             }
         } else {  // GEMM_DEFORM_NHWC: torchvision deform_conv2d sampling, 1 offset group, modulated
-            const int tap = k0 / p.Cin, ci0 = k0 - tap * p.Cin;
-            const int ky = tap / p.kw, kx = tap - ky * p.kw;
+            const ConvTap t = conv_tap(p, k0);
+            const int tap = t.tap, ci0 = t.ci0;
 #pragma unroll
             for (int i = 0; i < PA; ++i) {
                 f32x4 r = zero4();
@@ -129,8 +114,8 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_f32_kernel(const GemmParams 
                     const float* omr = p.om + om_base[i];
                     const float offy = omr[2 * tap], offx = omr[2 * tap + 1];
                     const float mk = omr[p.om_mask_off + tap];
-                    const float y = (float)(a_iy[i] + ky * p.dil) + offy;
-                    const float x = (float)(a_ix[i] + kx * p.dil) + offx;
+                    const float y = (float)(a_iy[i] + t.ky * p.dil) + offy;
+                    const float x = (float)(a_ix[i] + t.kx * p.dil) + offx;
                     if (y > -1.f && y < (float)p.Hin && x > -1.f && x < (float)p.Win) {
                         const int yl = (int)floorf(y), xl = (int)floorf(x);
                         const int yh = yl + 1, xh = xl + 1;

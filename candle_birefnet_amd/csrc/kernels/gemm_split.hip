@@ -1,9 +1,11 @@
 // gemm_split.hip — the contraction of gemm_f32.hip on the bf16 / fp16 matrix cores with fp32-class accuracy (compute modes f32_split3,
-// f32_split2, f32_half2; one plane = mode bf16_operands, diag build only): gemm_split_kernel (4-wave 64x64 / 128x64 / 128x128 tiles)
-// and the warp-specialised gemm_split_ws_kernel (128x128).  launch_gemm (gemm_f32.hip) validates, plans split-K and calls
-// launch_gemm_split; split-K partial sums are reduced by gemm_f32.hip's splitk_reduce_kernel.
+// f32_split2, f32_half2; one plane = mode bf16_operands, diag build only): gemm_split_kernel (4-wave 64x64 / 128x64 tiles) and the
+// warp-specialised gemm_split_ws_kernel (128x128), and their launcher.  What the kernels are made of — plane products, operand staging, the
+// deformable loader, the warp-specialised kernel's layout and roles — is gemm_split_stages.h.  launch_gemm (gemm_f32.hip) validates, plans
+// split-K and calls launch_gemm_split; split-K partial sums are reduced by gemm_f32.hip's splitk_reduce_kernel.
 #include "../brn_kernels.h"
 #include "gemm_common.h"
+#include "gemm_split_stages.h"
 
 namespace brn {
 
@@ -17,140 +19,12 @@ namespace brn {
 // NP = 2 keeps hh, hm, mh (~2^-16 relative); NP = 1 is plain bf16 x bf16 -> fp32 (the bf16 throughput mode).
 // LDS: per plane [rows][40 bf16] (80-byte rows: conflict-free for the ds_read_b128 lane groups).
 // =====================================================================================================================
-constexpr int SLD = 40;   // bf16 elements per LDS row
-
-// ---------------------------------------------------------------------------------------------------------------------
-// DeformLoader — the modulated-deformable A loader of both kernels below (MODE == GEMM_DEFORM_NHWC): the bilinear gather x modulator of
-// gemm_f32_kernel's loader (torchvision deform_conv2d, one offset group; a sample counts when y > -1 && y < Hin && x > -1 && x < Win, every
-// corner is tested on its own, rows >= M are zero), computed in fp32 while A is staged and handed to split4 / split4h like any other A value.
-// A staging thread holds one float4 (4 channels) of PA tile rows; the LPR lanes of a row are neighbours in the wave.
-//   * Sampling parameters are computed ONCE per (pixel, tap): lane q of a row's lane group owns (tile row q % PA, tap TPB blk + q / PA) of the
-//     current block of TPB = LPR / PA taps — offsets and modulator loaded one block ahead, floor / clamp / validity / four weights x modulator
-//     worked out once per block — and keeps ONE packed corner word and four weights.  Whoever stages a K tile of that (row, tap) fetches them
-//     with ds_bpermute (lanes of its own wave: no LDS bytes, no barrier), for each of the tap's Cin / KS K tiles.
-//   * Corners are clamped into the map and carry a zero weight when they are not real corners: no exec branch around a load (see
-//     load4_masked), so the corner loads of a later K tile stay in flight while an earlier one is blended, split and stored.  All four are
-//     buffer loads off one resource (the whole batch of maps: launch_gemm checks it spans < 2 GiB); the K tile's channel offset is uniform.
-//     The packed word is the byte offset of corner (yl, xl) — a multiple of 16 — with bit 0 / bit 1 saying whether the x / y neighbour is
-//     one pixel / one map row further or (clamped at a border) the same pixel.
-//   * The blend happens when the registers are consumed (finish), with the weights of the tile's tap: those live in two buffers by block
-//     parity, because the tile being blended may belong to the block before the one whose corners are being issued.
-// (A clamped corner's value is multiplied by a zero weight, not masked: a non-finite value there gives NaN, never a wrong finite number.
-// A NaN offset poisons its sample where gemm_f32_kernel's loader drops it: see param_compute.)
-// ---------------------------------------------------------------------------------------------------------------------
-template <int PA, int LPR>
-struct DeformLoader {
-    static constexpr int TPB = LPR / PA;
-    static_assert(TPB >= 1 && TPB * PA == LPR, "a row's lanes share out (tile row, tap) pairs evenly");
-    __amdgpu_buffer_rsrc_t rsrc;
-    int kq16, grp4;               // this lane's 16 bytes inside a K tile; 4 x the first lane of the row's lane group (ds_bpermute addresses bytes)
-    int pixb, rowb, ntaps;
-    // owner role (kept small: the staging waves of the warp-specialised kernel live within 128 VGPRs)
-    int o_yx;                     // the row's window origin, (iy << 16) | (ix & 0xffff)
-    unsigned o_img, o_om;         // byte offset of its image; element offset of its offsets / modulator row
-    float om_y, om_x, om_m;       // offsets / modulator of the owner's tap in the next block
-    unsigned own_off;
-    float own_w[2][4];
-    int cur_blk;
-
-    __device__ __forceinline__ void init(const GemmParams& p, int m0, int lrow, int rpp, int kq, int lane) {
-        rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.A + p.a_coff), 0, 0x7fffffff, 0x00020000);
-        kq16 = kq * 16;
-        grp4 = (lane & ~(LPR - 1)) * 4;
-        pixb = p.lda * 4;
-        rowb = p.Win * pixb;
-        ntaps = p.kh * p.kw;
-        const int m = m0 + lrow + (kq % PA) * rpp;
-        const int mm = min(m, p.M - 1);
-        const int hw = p.Hout * p.Wout;
-        const int b = mm / hw, rem = mm - b * hw;
-        const int oy = rem / p.Wout, ox = rem - oy * p.Wout;
-        // a row >= M reads row M - 1's offsets from an origin far above the map: never inside, so it is staged as zeros (launch_gemm bounds the geometry)
-        const int iy = m < p.M ? oy * p.stride - p.pad : -32768, ix = ox * p.stride - p.pad;
-        o_yx = (int)(((unsigned)iy << 16) | ((unsigned)ix & 0xffffu));
-        o_img = (unsigned)b * (unsigned)(p.Hin * rowb);
-        o_om = (unsigned)mm * (unsigned)p.om_ld;
-        om_y = om_x = om_m = 0.f;
-        own_off = 0;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) own_w[0][c] = own_w[1][c] = 0.f;
-        cur_blk = -1;
-    }
-    __device__ __forceinline__ void param_load(const GemmParams& p, int blk) {
-        const int tap = min(blk * TPB + (kq16 >> 4) / PA, ntaps - 1);
-        const float* om = p.om + o_om;
-        om_y = om[2 * tap]; om_x = om[2 * tap + 1]; om_m = om[p.om_mask_off + tap];
-    }
-    __device__ __forceinline__ void param_compute(const GemmParams& p, int blk) {
-        const int tap = min(blk * TPB + (kq16 >> 4) / PA, ntaps - 1);
-        const int ky = tap / p.kw, kx = tap - ky * p.kw;
-        const float y = (float)((o_yx >> 16) + ky * p.dil) + om_y;
-        const float x = (float)((short)o_yx + kx * p.dil) + om_x;
-        const bool inside = y > -1.f && y < (float)p.Hin && x > -1.f && x < (float)p.Win;
-        const float yf = floorf(y), xf = floorf(x);
-        const float ly = y - yf, lx = x - xf, hy = 1.f - ly, hx = 1.f - lx;
-        // (an inside sample has yl in [-1, Hin - 1]; the clamps tame NaN and huge offsets: such a sample is not inside, every weight is zero)
-        const int yl = (int)fminf(fmaxf(yf, -1.f), (float)(p.Hin - 1)), xl = (int)fminf(fmaxf(xf, -1.f), (float)(p.Win - 1));
-        const bool yl_ok = yl >= 0, yh_ok = yl + 1 <= p.Hin - 1, xl_ok = xl >= 0, xh_ok = xl + 1 <= p.Win - 1;
-        // (selects, not a multiply by 0: ly / lx of a sample that is not inside may be NaN.)  A NaN position is not "outside": the offsets come
-        // from a conv of the same mode, and beyond f32_half2's range that conv answers NaN — the sample is poisoned, not dropped, so that the
-        // result stays non-finite instead of silently losing a tap.
-        const float out = (y != y || x != x) ? __builtin_nanf("") : 0.f;
-        const float w0 = (inside && yl_ok && xl_ok) ? om_m * (hy * hx) : out;
-        const float w1 = (inside && yl_ok && xh_ok) ? om_m * (hy * lx) : out;
-        const float w2 = (inside && yh_ok && xl_ok) ? om_m * (ly * hx) : out;
-        const float w3 = (inside && yh_ok && xh_ok) ? om_m * (ly * lx) : out;
-        const bool odd = blk & 1;
-        own_w[0][0] = odd ? own_w[0][0] : w0; own_w[1][0] = odd ? w0 : own_w[1][0];
-        own_w[0][1] = odd ? own_w[0][1] : w1; own_w[1][1] = odd ? w1 : own_w[1][1];
-        own_w[0][2] = odd ? own_w[0][2] : w2; own_w[1][2] = odd ? w2 : own_w[1][2];
-        own_w[0][3] = odd ? own_w[0][3] : w3; own_w[1][3] = odd ? w3 : own_w[1][3];
-        const int ylc = max(yl, 0), xlc = max(xl, 0);
-        // x / y neighbour distinct from the clamped low corner: only when both are real pixels
-        own_off = (o_img + (unsigned)(ylc * p.Win + xlc) * (unsigned)pixb) | ((xl_ok && xh_ok) ? 1u : 0u) | ((yl_ok && yh_ok) ? 2u : 0u);
-    }
-    // the four corner loads of K tile [k0, k0 + KS) for tile rows [I0, I1) of this thread; called with ascending k0
-    template <int I0, int I1>
-    __device__ __forceinline__ void issue(const GemmParams& p, int k0, f32x4 (&qc)[PA][4]) {
-        const int tap = k0 / p.Cin, ci0 = k0 - tap * p.Cin;
-        const int blk = tap / TPB;
-        if (blk != cur_blk) {                       // uniform: a new block of taps
-            if (cur_blk < 0) param_load(p, blk);    // (the first tile of a split-K slice)
-            param_compute(p, blk);
-            cur_blk = blk;
-            if ((blk + 1) * TPB < ntaps) param_load(p, blk + 1);
-        }
-        const int src = grp4 + (tap - blk * TPB) * (PA * 4);
-#pragma unroll
-        for (int i = I0; i < I1; ++i) {
-            const unsigned v = (unsigned)__builtin_amdgcn_ds_bpermute(src + i * 4, (int)own_off);
-            const unsigned o = (v & ~3u) + (unsigned)kq16;
-            const unsigned sx = (v & 1u) ? (unsigned)pixb : 0u, sy = (v & 2u) ? (unsigned)rowb : 0u;
-            qc[i][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, o, ci0 * 4, 0));
-            qc[i][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, o + sx, ci0 * 4, 0));
-            qc[i][2] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, o + sy, ci0 * 4, 0));
-            qc[i][3] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, o + sx + sy, ci0 * 4, 0));
-        }
-    }
-    // modulator x bilinear blend of row i of the K tile that starts at k0 (its corners: qc)
-    __device__ __forceinline__ f32x4 finish(const GemmParams& p, int k0, int i, const f32x4 (&qc)[4]) const {
-        const int tap = k0 / p.Cin, blk = tap / TPB;
-        const int src = grp4 + (tap - blk * TPB) * (PA * 4) + i * 4;
-        const bool odd = blk & 1;
-        float w[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-            w[c] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src, __builtin_bit_cast(int, odd ? own_w[1][c] : own_w[0][c])));
-        f32x4 r;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) r[e] = fmaf(w[3], qc[3][e], fmaf(w[2], qc[2][e], fmaf(w[1], qc[1][e], w[0] * qc[0][e])));
-        return r;
-    }
-};
+constexpr int SPLIT_LD = 40;   // bf16 elements per LDS row of gemm_split_kernel
 
 template <int BM, int BN, int WM, int WN, int MODE, int NP, bool H = false>   // H: the two planes are fp16 (mode f32_half2)
 __global__ void __launch_bounds__(WM* WN * 64) gemm_split_kernel(const GemmParams p) {
     static_assert(!H || NP == 2, "fp16 planes come in pairs");
+    constexpr int SLD = SPLIT_LD;
     constexpr int NT = WM * WN * 64;
     constexpr int RPP = NT / 8;           // A rows per pass (8 float4 per 32-float row)
     constexpr int PA = BM / RPP;
@@ -205,42 +79,18 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_split_kernel(const GemmParam
         if constexpr (DEFORM) {
             rk = k0;
             dl.template issue<0, PA>(p, k0, rc);
-        } else if (MODE == GEMM_DENSE) {
-#pragma unroll
-            for (int i = 0; i < PA; ++i)
-                {
-                    qa[i] = load4_masked(p.A + (a_ok[i] ? a_base[i] : 0) + k0 + kq * 4, a_ok[i], qm[i]);
-                }
         } else {
-            const int tap = k0 / p.Cin, ci0 = k0 - tap * p.Cin;
-            const int ky = tap / p.kw, kx = tap - ky * p.kw;
-            const int dy = ky * p.dil, dx = kx * p.dil;
-#pragma unroll
-            for (int i = 0; i < PA; ++i) {
-                const int iy = a_iy[i] + dy, ix = a_ix[i] + dx;
-                const bool ok = a_ok[i] && (unsigned)iy < (unsigned)p.Hin && (unsigned)ix < (unsigned)p.Win;
-                const long off = ok ? a_base[i] + ((long)iy * p.Win + ix) * p.lda + ci0 : (long)p.a_coff;
-                qa[i] = load4_masked(p.A + off + kq * 4, ok, qm[i]);
-            }
+            gather_rows_load<MODE>(&p, k0, kq, a_ok, a_base, a_iy, a_ix, qa, qm);
         }
     };
     auto lds_store = [&](const f32x4 (&qa)[PA], const bf16x8 (&qb)[NP][PB], const unsigned (&qm)[PA]) {
 #pragma unroll
         for (int i = 0; i < PA; ++i) {
-            bf16x4 sp[NP];
-            if constexpr (DEFORM) {
-                const f32x4 v = dl.finish(p, rk, i, rc[i]);
-                if constexpr (H) split4h<false>(v, 0xffffffffu, p.a_scale, sp); else split4<NP, false>(v, 0xffffffffu, sp);
-            } else if constexpr (H) split4h<true>(qa[i], qm[i], p.a_scale, sp); else split4<NP>(qa[i], qm[i], sp);
-#pragma unroll
-            for (int pl = 0; pl < NP; ++pl)
-                *reinterpret_cast<bf16x4*>(As + (pl * BM + lrow + i * RPP) * SLD + kq * 4) = sp[pl];
+            auto at = [&](int pl) { return As + (pl * BM + lrow + i * RPP) * SLD + kq * 4; };
+            if constexpr (DEFORM) stage_a_row<NP, H>(dl.finish(p, rk, i, rc[i]), 0xffffffffu, false, p.a_scale, at);
+            else stage_a_row<NP, H>(qa[i], qm[i], true, p.a_scale, at);
         }
-#pragma unroll
-        for (int pl = 0; pl < NP; ++pl)
-#pragma unroll
-            for (int i = 0; i < PB; ++i)
-                *reinterpret_cast<bf16x8*>(Bs + (pl * BN + wrow + i * WRPP) * SLD + wc * 8) = qb[pl][i];
+        stage_w_planes<NP, PB>(qb, [&](int pl, int i) { return Bs + (pl * BN + wrow + i * WRPP) * SLD + wc * 8; });
     };
 
     f32x16 acc[TM][TN];
@@ -266,20 +116,7 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_split_kernel(const GemmParam
 #pragma unroll
                 for (int j = 0; j < TN; ++j) bf[pl][j] = *reinterpret_cast<const bf16x8*>(b_frag + (pl * BN + j * 32) * SLD + ks * 16);
             }
-            // smallest plane products first
-#pragma unroll
-            for (int sum = NP - 1; sum >= 0; --sum)
-#pragma unroll
-                for (int pa = 0; pa < NP; ++pa) {
-                    const int pb = sum - pa;
-                    if (pb < 0 || pb >= NP) continue;
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int j = 0; j < TN; ++j)
-                            if constexpr (H) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, af[pa][i]), __builtin_bit_cast(f16x8, bf[pb][j]), acc[i][j], 0, 0, 0);
-                            else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[pa][i], bf[pb][j], acc[i][j], 0, 0, 0);
-                }
+            plane_products<NP, H, false>(af, bf, acc);
         }
     };
 
@@ -305,7 +142,9 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_split_kernel(const GemmParam
         lds_store(ra[0], rb[0], am[0]);
     }
     __syncthreads();
-    // body for one K tile whose successor sits in register set NXT; the set just consumed (CUR) is refilled 2 tiles ahead
+    // body for one K tile whose successor sits in register set NXT; the set just consumed (CUR) is refilled 2 tiles ahead.  (A macro: CUR and
+    // NXT have to be compile-time indices, and a generic lambda taking them as integral_constants compiled to other code with other register
+    // counts, profiles/isa_parity_gemm_split.md.)
 #define BRN_SPLIT_STEP(KT, CUR, NXT)                                  \
     {                                                                 \
         if ((KT) + 2 < nk) gload((KT) + 2, ra[CUR], rb[CUR], am[CUR]);         \
@@ -326,59 +165,31 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_split_kernel(const GemmParam
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// gemm_split_ws_kernel — warp-specialised form of gemm_split_kernel for the 128x128 tile: 8 waves, two per SIMD.
-// Waves 0-3 (consumers) own the 2x2 grid of 64x64 sub-tiles: fragment reads + MFMA only.  Waves 4-7 (producers) stage:
-// global loads four K tiles ahead (two register sets), operand split, LDS writes into a ring of NBUF = 3 K-tile buffers,
-// two tiles ahead of the consumers.  ONE workgroup barrier per K tile.  Because tile kt+1 is already complete while tile kt
-// is multiplied, a consumer prefetches the next tile's first fragments before the barrier and double-buffers fragments in
-// registers: at bf16 MFMA rates an exposed LDS read (~250 cycles) per 32-deep K tile (768 MFMA cycles) was a third of the
+// gemm_split_ws_kernel — warp-specialised form of gemm_split_kernel for the 128x128 tile: 8 waves, two per SIMD.  LDS layout and the
+// producers' thread map: WsLayout (gemm_split_stages.h).  Top to bottom: the tile slice; the producers (waves 4-7), register-staged or
+// deformable; the consumers (waves 0-3), 16x16x32 or 32x32x16 MFMAs; one barrier; the epilogue on all eight waves.
+// Producers stage: global loads into two register sets, three K tiles ahead of the consumers, operand split, LDS writes into the ring of two
+// K-tile buffers, one tile ahead.  Consumers own the 2x2 grid of 64x64 sub-tiles: fragment reads + MFMA only.  ONE workgroup barrier per
+// K tile.  Tile t + 1 is complete only after step t's barrier, so a consumer reads its first fragments right after it and double-buffers
+// fragments in registers: at bf16 MFMA rates an exposed LDS read (~250 cycles) per 32-deep K tile (768 MFMA cycles) was a third of the
 // loop (measured by ablation: staging and MFMA phases added up, then the fragment-read stall did).
-// ---------------------------------------------------------------------------------------------------------------------
-template <int MODE, int NP, int KS, bool DIAG, bool APL, bool H = false>   // APL: A arrives in the P2 layout (its producer already split it): the staging waves only copy
-// H: the two planes are fp16 planes of the scaled operands (mode f32_half2; split4h / v_mfma_f32_32x32x16_f16), same bytes and layouts
-// DIAG: ablation switches + per-K-tile cycle stamps (brn_gemm_microbench only; costs registers)
-// KS = k elements per LDS stage (32, or 16 to halve the stage when 3 planes must fit twice per CU)
-#ifndef BRN_WS_M16
-#define BRN_WS_M16 1          // 2-plane, 32-deep stages: the consumers issue 16 x 16 x 32 MFMAs (0: 32 x 32 x 16, same-box A/B builds)
-#endif
+//   APL:  A arrives in the P layout (its producer already split it): the staging waves only copy
+//   H:    the two planes are fp16 planes of the scaled operands (mode f32_half2; split4h / the f16 MFMAs), same bytes and layouts
+//   DIAG: ablation switches (p.abl) + per-K-tile cycle stamps (WsTrace; brn_gemm_microbench only; costs registers)
+//   KS:   k elements per LDS stage (32, or 16 to halve the stage when 3 planes must fit twice per CU)
 // (the deformable producers hold four corners per staged row: the 2-plane form is told to stay within the 128 VGPRs of two workgroups per CU)
+// ---------------------------------------------------------------------------------------------------------------------
+template <int MODE, int NP, int KS, bool DIAG, bool APL, bool H = false>
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MODE == GEMM_DEFORM_NHWC && NP == 2 ? 4 : 1)))
 gemm_split_ws_kernel(const GemmParams p) {
-    constexpr int BM = 128, BN = 128, WTM = 64, WTN = 64, TM = 2, TN = 2;
+    using L = WsLayout<NP, KS, APL>;
+    constexpr int BM = L::BM, BN = L::BN, WTM = L::WTM, WTN = L::WTN, TM = 2, TN = 2;
     static_assert(!APL || ((NP == 2 || NP == 3) && MODE == GEMM_DENSE), "the P input layout is the NP-plane split of a dense A");
     static_assert(!H || NP == 2, "fp16 planes come in pairs");
-    // LDS rows (round 4): UNPADDED KS-element rows with the 16-byte chunks of a row XOR-permuted by the row — key (row >> 3) & 1 for the
-    // 32-byte rows of a 16-deep stage (8 rows per 256-byte bank row), (row >> 2) & 3 for 64-byte rows (4 per bank row).  A ds_read_b128
-    // lane group (16 consecutive rows, one logical chunk) then touches 16 different 16-byte slots, AND a producer store instruction
-    // (8-byte pieces: 4 or 8 lanes per row, 32 lanes = 8 or 4 whole rows) covers one bank row exactly once.  The padded rows this
-    // replaces (KS + 8 elements: 48 / 80 bytes) were conflict-free for the reads only: the producers' ds_write_b64 halves wrapped onto
-    // banks of the first rows (rows 0 / 5, 1 / 6, 2 / 7 of a 32-lane half at 48 bytes) — the 4 % SQ_LDS_BANK_CONFLICT of
-    // profiles/r03_pmc_sq_c2_f32_split3.csv, paid by the staging waves, which are this kernel's critical path.  BRN_WS_SWZ=0 builds the
-    // padded layout (same-box A/B of two libraries: tools/ab_lib.sh).
-#ifndef BRN_WS_SWZ
-#define BRN_WS_SWZ 1
-#endif
-    constexpr bool SWZ = BRN_WS_SWZ != 0;
-    constexpr int SLD = SWZ ? KS : KS + 8;          // bf16 per LDS row
-    auto swz_key = [](int row) { return SWZ ? (KS == 16 ? (row >> 3) & 1 : (row >> 2) & 3) : 0; };
-    constexpr int KSTEPS = KS / 16;                 // MFMA k-steps per stage
-    constexpr int NBUF = 2;                         // 2 x NP x 20 KB: two workgroups per CU at NP <= 2 (a 3-deep ring was slower: 1 WG/CU exposes each tile's prologue + epilogue)
-    constexpr int AQ = KS / 4, RPP = 256 / AQ;                  // producers: 256 threads, AQ float4 per KS-float row
-    constexpr int PA = APL ? 2 * NP : BM / RPP;                 // P-layout input: 4 NP 16-byte chunks per (row, K tile), 128 rows / 256 threads
-    constexpr int WQ = KS / 8, WRPP = 256 / WQ, PB = BN / WRPP; // WQ 16-byte chunks per KS-bf16 row
-    // P-layout input: ONE ds_write_b128 instruction covers both planes of a row (lanes c = 0..3 plane 0, 4..7 plane 1), and BM x SLD x 2 bytes is a
-    // multiple of the 256-byte bank row: the two planes of a row would sit on the same banks (2-way conflict on every staging write: 2.5 % of
-    // wave cycles in profiles/r04_pmc_sq_c2_f32_half2.csv).  Plane p of A is therefore shifted by p x 128 bytes: rows r, r + 1 of both planes then
-    // cover the four 64-byte quarters of a bank row.  (The fragment reads stay conflict-free: a constant shift per plane.)
-#ifndef BRN_APL_PAD
-#define BRN_APL_PAD 1
-#endif
-    constexpr int APAD = (BRN_APL_PAD && APL && KS == 32) ? 64 : 0;            // elements (BRN_APL_PAD=0 builds the unshifted layout: tools/ab_lib.sh)
-    constexpr int AREG = NP * BM * SLD + (NP - 1) * APAD;       // A region of a buffer
-    constexpr int BUF = AREG + NP * BN * SLD;       // bf16 elements per LDS buffer
-    constexpr int EP_LD = BN + 4;                   // floats per row of the epilogue's LDS image of the C tile
-    constexpr int SMEM_MAIN = NBUF * BUF * 2, SMEM_EPI = BM * EP_LD * 4;   // bytes
-    __shared__ __attribute__((aligned(16))) char smem_raw[SMEM_MAIN > SMEM_EPI ? SMEM_MAIN : SMEM_EPI];
+    static_assert(L::NBUF == 2, "the producers stage one tile ahead of the consumers; a tile's first fragments are read after the step's barrier");
+    constexpr int SLD = L::ROW, KSTEPS = L::KSTEPS, NBUF = L::NBUF, AQ = L::AQ, RPP = L::RPP, PA = L::PA, WQ = L::WQ, WRPP = L::WRPP, PB = L::PB;
+    constexpr int APAD = L::APAD, AREG = L::AREG, BUF = L::BUF, EP_LD = L::EP_LD;
+    __shared__ __attribute__((aligned(16))) char smem_raw[L::SMEM];
     __bf16* smem = reinterpret_cast<__bf16*>(smem_raw);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -388,16 +199,8 @@ gemm_split_ws_kernel(const GemmParams p) {
     const int slice = ts.slice, m0 = ts.m0, n0 = ts.n0, kt0 = ts.kt0, nk = ts.nk;
     const int nt = nk > kt0 ? nk - kt0 : 0;         // K tiles of this slice; local tile index t = kt - kt0
 
-    unsigned long long* trc = (DIAG && p.trace) ? p.trace + (long)blockIdx.x * 256 : nullptr;
-    if (trc && (tid == 0 || tid == 256)) {
-        unsigned hwid;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        trc[(tid >> 8) * 8 + 0] = clock64();
-        trc[(tid >> 8) * 8 + 1] = wall_clock64();
-        trc[(tid >> 8) * 8 + 2] = ((unsigned long long)xcc << 32) | hwid;
-    }
+    const WsTrace<DIAG> tr(p);
+    tr.start(tid);
     f32x16 acc[TM][TN];
     if (producer) {
         const int pt = tid - 256;
@@ -411,16 +214,14 @@ gemm_split_ws_kernel(const GemmParams p) {
             p_lds[i] = 0;
             if (APL) {
                 const int q = i * 256 + pt, row = q / (4 * NP), c = q - row * (4 * NP);   // chunk c of the row: plane c / 4, k = 8 (c % 4)
-                p_lds[i] = ((c >> 2) * BM + row) * SLD + (c >> 2) * APAD + ((c & 3) ^ swz_key(row)) * 8;
+                p_lds[i] = ((c >> 2) * BM + row) * SLD + (c >> 2) * APAD + ((c & 3) ^ L::swz_key(row)) * 8;
             }
             gather_row_init<MODE>(p, m0 + lrow + i * RPP, a_ok[i], a_base[i], a_iy[i], a_ix[i]);
         }
         const int wc = pt % WQ, wrow = pt / WQ;
         // element offsets inside an LDS row of this thread's pieces (RPP and WRPP are multiples of 32 rows: the key is that of lrow / wrow)
-        const int a_sw = ((kq >> 1) ^ swz_key(lrow)) * 8 + (kq & 1) * 4;
-        const int w_sw = (wc ^ swz_key(wrow)) * 8;
-        static_assert(KS == 32 || KS == 16, "the interleaved W plane layout is per 32-deep K tile; a 16-deep stage takes one half of it");
-        static_assert(!APL || KS == 32, "P-layout input is staged in whole 32-deep K tiles");
+        const int a_sw = ((kq >> 1) ^ L::swz_key(lrow)) * 8 + (kq & 1) * 4;
+        const int w_sw = (wc ^ L::swz_key(wrow)) * 8;
         const long wrow_stride = (long)p.K * NP;         // W planes interleaved per K tile: [row][K/32][plane][32] bf16
         // Dense operands are buffer-addressed: a resource per tile (A: based at row m0, num_records = the tile's valid rows, so rows
         // >= M come back as zeros without a mask; W planes: based at row n0), a 32-bit lane offset fixed for the tile, the K tile in the
@@ -481,11 +282,10 @@ gemm_split_ws_kernel(const GemmParams p) {
                 }
                 return;
             }
-            const int tap = k0 / p.Cin, ci0 = k0 - tap * p.Cin;
-            const int ky = tap / p.kw, kx = tap - ky * p.kw;
-            const int dy = ky * p.dil, dx = kx * p.dil;
+            const ConvTap tp = conv_tap(p, k0);
+            const int dy = tp.ky * p.dil, dx = tp.kx * p.dil;
             if (bufc_ok) {
-                const int tap_off = ((dy * p.Win + dx) * p.lda + ci0) * 4;        // uniform
+                const int tap_off = ((dy * p.Win + dx) * p.lda + tp.ci0) * 4;        // uniform
 #pragma unroll
                 for (int i = 0; i < PA; ++i) {
                     const int iy = a_iy[i] + dy, ix = a_ix[i] + dx;
@@ -495,18 +295,22 @@ gemm_split_ws_kernel(const GemmParams p) {
                 }
                 return;
             }
-            // maps too large for 32-bit offsets: 64-bit addresses, clamped + masked (split4<NP, true> / split4h<true> in lds_store)
+            // maps too large for 32-bit offsets: 64-bit addresses, clamped + masked, as gather_rows_load does it (written out here: that helper
+            // inside this lambda changes the code of the buffer-addressed paths as well, profiles/isa_parity_gemm_split.md)
 #pragma unroll
             for (int i = 0; i < PA; ++i) {
                 const int iy = a_iy[i] + dy, ix = a_ix[i] + dx;
                 const bool ok = a_ok[i] && (unsigned)iy < (unsigned)p.Hin && (unsigned)ix < (unsigned)p.Win;
-                const long off = ok ? a_base[i] + ((long)iy * p.Win + ix) * p.lda + ci0 : (long)p.a_coff;
+                const long off = ok ? a_base[i] + ((long)iy * p.Win + ix) * p.lda + tp.ci0 : (long)p.a_coff;
                 qa[i] = load4_masked(p.A + off + kq * 4, ok, qm[i]);
             }
         };
+        auto w_store = [&](int t, const bf16x8 (&qb)[NP][PB]) {
+            __bf16* Bs = smem + (t % NBUF) * BUF + AREG;
+            stage_w_planes<NP, PB>(qb, [&](int pl, int i) { return Bs + (pl * BN + wrow + i * WRPP) * SLD + w_sw; });
+        };
         auto lds_store = [&](int t, const f32x4 (&qa)[PA], const bf16x8 (&qb)[NP][PB], const unsigned (&qm)[PA]) {
             __bf16* As = smem + (t % NBUF) * BUF;
-            __bf16* Bs = As + AREG;
             if (APL) {
                 // 16 bytes = 8 bf16 of plane kq >> 2 at k = 8 (kq & 3): one ds_write_b128, no arithmetic (rows beyond M were
                 // loaded from row 0 and are zeroed by an integer AND with the row's 0 / ~0 mask)
@@ -517,20 +321,10 @@ gemm_split_ws_kernel(const GemmParams p) {
                 }
             } else {
 #pragma unroll
-            for (int i = 0; i < PA; ++i) {
-                bf16x4 sp[NP];
-                if constexpr (H) { if (BUFA || (BUFC && bufc_ok)) split4h<false>(qa[i], qm[i], p.a_scale, sp); else split4h<true>(qa[i], qm[i], p.a_scale, sp); }
-                else if (BUFA || (BUFC && bufc_ok)) split4<NP, false>(qa[i], qm[i], sp); else split4<NP>(qa[i], qm[i], sp);
-#pragma unroll
-                for (int pl = 0; pl < NP; ++pl)
-                    *reinterpret_cast<bf16x4*>(As + (pl * BM + lrow + i * RPP) * SLD + a_sw) = sp[pl];
+                for (int i = 0; i < PA; ++i)
+                    stage_a_row<NP, H>(qa[i], qm[i], !(BUFA || (BUFC && bufc_ok)), p.a_scale, [&](int pl) { return As + (pl * BM + lrow + i * RPP) * SLD + a_sw; });
             }
-            }
-#pragma unroll
-            for (int pl = 0; pl < NP; ++pl)
-#pragma unroll
-                for (int i = 0; i < PB; ++i)
-                    *reinterpret_cast<bf16x8*>(Bs + (pl * BN + wrow + i * WRPP) * SLD + w_sw) = qb[pl][i];
+            w_store(t, qb);
         };
         if constexpr (MODE == GEMM_DEFORM_NHWC) {
         // The deformable loader (DeformLoader above).  A staged row is four corner float4s: two register sets of those are more than the
@@ -544,18 +338,8 @@ gemm_split_ws_kernel(const GemmParams p) {
         f32x4 rc[PA][4];
         auto a_store = [&](int t, int i, const f32x4 v) {
             __bf16* As = smem + (t % NBUF) * BUF;
-            bf16x4 sp[NP];
-            if constexpr (H) split4h<false>(v, 0xffffffffu, p.a_scale, sp); else split4<NP, false>(v, 0xffffffffu, sp);
-#pragma unroll
-            for (int pl = 0; pl < NP; ++pl) *reinterpret_cast<bf16x4*>(As + (pl * BM + lrow + i * RPP) * SLD + a_sw) = sp[pl];
+            stage_a_row<NP, H>(v, 0xffffffffu, false, p.a_scale, [&](int pl) { return As + (pl * BM + lrow + i * RPP) * SLD + a_sw; });
             __builtin_amdgcn_sched_barrier(0);      // one row at a time: interleaved rows' temporaries do not fit beside the corners in flight
-        };
-        auto w_store = [&](int t, const bf16x8 (&qb)[NP][PB]) {
-            __bf16* Bs = smem + (t % NBUF) * BUF + AREG;
-#pragma unroll
-            for (int pl = 0; pl < NP; ++pl)
-#pragma unroll
-                for (int i = 0; i < PB; ++i) *reinterpret_cast<bf16x8*>(Bs + (pl * BN + wrow + i * WRPP) * SLD + w_sw) = qb[pl][i];
         };
         // prologue: LDS tile 0 stored, the corners and the W planes of tile 1 in flight
         if (nt > 0) { wload(kt0, rb[0]); dl.template issue<0, PA>(p, kt0 * KS, rc); }
@@ -583,40 +367,39 @@ gemm_split_ws_kernel(const GemmParams p) {
             __syncthreads();
         }
         } else {
-        constexpr int AHEAD = NBUF - 1;     // LDS tiles the producers run ahead of the consumers
-        // prologue: LDS tiles 0 .. AHEAD-1 stored, register sets hold the next two tiles
+        // prologue: LDS tile 0 stored, the register sets hold tiles 1 and 2
         if (nt > 0) gload(0, ra[0], rb[0], am[0]);
         if (nt > 1) gload(1, ra[1], rb[1], am[1]);
         if (nt > 0 && !(abl & 2)) lds_store(0, ra[0], rb[0], am[0]);
         if (nt > 2) gload(2, ra[0], rb[0], am[0]);
-        if (AHEAD > 1) {
-            if (nt > 1 && !(abl & 2)) lds_store(1, ra[1], rb[1], am[1]);
-            if (nt > 3) gload(3, ra[1], rb[1], am[1]);
-        }
-        if (trc && tid == 256) trc[8 + 3] = clock64();
+        tr.cycles(tid == 256, 8 + 3);
         __syncthreads();
-        // step t: store tile t+AHEAD (register set (t+AHEAD)&1), refill that set with tile t+AHEAD+2
-#define BRN_PROD_STEP(T, SET)                                                              \
-        {                                                                                  \
-            if (trc && tid == 256 && (T) < 24) trc[16 + (T) * 4 + 0] = clock64();          \
-            if (trc) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); if (tid == 256 && (T) < 24) trc[16 + (T) * 4 + 3] = clock64(); } \
-            if ((T) + AHEAD < nt) {                                                        \
-                if (!(abl & 2)) lds_store((T) + AHEAD, ra[SET], rb[SET], am[SET]);                \
-                if (trc && tid == 256 && (T) < 24) trc[16 + (T) * 4 + 1] = clock64();      \
-                if ((T) + AHEAD + 2 < nt && !(abl & 1)) gload((T) + AHEAD + 2, ra[SET], rb[SET], am[SET]); \
-            }                                                                              \
-            if (trc && tid == 256 && (T) < 24) trc[16 + (T) * 4 + 2] = clock64();          \
-            if (!(abl & 16)) __syncthreads();                                            \
+        // step T (the consumers multiply tile T): store tile T + 1 from register set SET, refill that set with tile T + 3.  (A macro, like
+        // BRN_SPLIT_STEP above: SET has to be a compile-time index, and a generic lambda taking it as an integral_constant compiled to other
+        // code with other register counts, profiles/isa_parity_gemm_split.md.)
+#define BRN_PROD_STEP(T, SET)                                                                      \
+        {                                                                                          \
+            tr.cycles(tid == 256 && (T) < 24, 16 + (T) * 4 + 0);                                   \
+            tr.drain_loads();                                                                      \
+            tr.cycles(tid == 256 && (T) < 24, 16 + (T) * 4 + 3);                                   \
+            if ((T) + 1 < nt) {                                                                \
+                if (!(abl & 2)) lds_store((T) + 1, ra[SET], rb[SET], am[SET]);                 \
+                tr.cycles(tid == 256 && (T) < 24, 16 + (T) * 4 + 1);                               \
+                if ((T) + 3 < nt && !(abl & 1)) gload((T) + 3, ra[SET], rb[SET], am[SET]); \
+            }                                                                                      \
+            tr.cycles(tid == 256 && (T) < 24, 16 + (T) * 4 + 2);                                   \
+            if (!(abl & 16)) __syncthreads();                                                      \
         }
         for (int t = 0; t < nt; t += 2) {
-            BRN_PROD_STEP(t, AHEAD & 1)
-            if (t + 1 < nt) BRN_PROD_STEP(t + 1, (AHEAD + 1) & 1)
+            BRN_PROD_STEP(t, 1)
+            if (t + 1 < nt) BRN_PROD_STEP(t + 1, 0)
         }
 #undef BRN_PROD_STEP
         }   // (the register-staged producers)
-        if (trc && tid == 256) { trc[8 + 4] = clock64(); trc[8 + 5] = wall_clock64(); }
-    } else if constexpr (BRN_WS_M16 != 0 && KS == 32 && NP == 2 && !DIAG) {
-    // ---- consumers, 16 x 16 x 32 MFMAs (round 4): the same cycles per flop as 32 x 32 x 16, but the chip holds a higher clock under the smaller
+        tr.cycles(tid == 256, 8 + 4);
+        tr.wall(tid == 256, 8 + 5);
+    } else if constexpr (KS == 32 && NP == 2 && !DIAG) {
+    // ---- consumers, 16 x 16 x 32 MFMAs: the same cycles per flop as 32 x 32 x 16, but the chip holds a higher clock under the smaller
     // shape (MI355X_MICROARCH.md, DVFS; gemm_bf16.hip measured + 5 ... 13 % on its LDS-fed tiles).  One MFMA k = the whole 32-deep stage; a wave's
     // 64 x 64 is 4 x 4 blocks, multiplied as four 2 x 2 quadrants.  Fragment of a 16-row block: lane l reads row l & 15, 16-byte k chunk l >> 4 (XOR the row's key).
     f32x4 acc4[4][4];
@@ -626,7 +409,7 @@ gemm_split_ws_kernel(const GemmParams p) {
         for (int j = 0; j < 4; ++j) acc4[i][j] = zero4();
     const int wm = wave >> 1, wn = wave & 1;
     const int r16 = lane & 15, kc = lane >> 4;
-    const int fch = (kc ^ swz_key(r16)) * 8;           // (the key of a row depends on its bits 2, 3: the same in every 16-row block)
+    const int fch = (kc ^ L::swz_key(r16)) * 8;           // (the key of a row depends on its bits 2, 3: the same in every 16-row block)
     const int a_row = (wm * WTM + r16) * SLD + fch, b_row = AREG + (wn * WTN + r16) * SLD + fch;
     auto read_a = [&](int t, int half, bf16x8 (&af)[NP][2]) {
         const __bf16* buf = smem + (t % NBUF) * BUF;
@@ -642,35 +425,18 @@ gemm_split_ws_kernel(const GemmParams p) {
 #pragma unroll
             for (int j = 0; j < 2; ++j) bf[pl][j] = *reinterpret_cast<const bf16x8*>(buf + b_row + (pl * BN + (half * 2 + j) * 16) * SLD);
     };
-    auto mfma_quad = [&](const bf16x8 (&af)[NP][2], const bf16x8 (&bf)[NP][2], const int ih, const int jh) {
-#pragma unroll
-        for (int sum = NP - 1; sum >= 0; --sum)        // smallest plane products first
-#pragma unroll
-            for (int pa = 0; pa < NP; ++pa) {
-                const int pb = sum - pa;
-                if (pb < 0 || pb >= NP) continue;
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {       // transposed product (W fragment first): a lane holds ONE row of a block and 4 consecutive columns
-                        f32x4& d = acc4[ih * 2 + i][jh * 2 + j];
-                        if constexpr (H) d = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, bf[pb][j]), __builtin_bit_cast(f16x8, af[pa][i]), d, 0, 0, 0);
-                        else d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[pb][j], af[pa][i], d, 0, 0, 0);
-                    }
-            }
-    };
     // per stage: the first quadrant's fragments (A blocks 0, 1; W blocks 0, 1: 8 reads) are fetched right after the barrier, the other 8 reads ride
     // under the first quadrant's 12 MFMAs
     bf16x8 fa0[NP][2], fa1[NP][2], fb0[NP][2], fb1[NP][2];
-    __syncthreads();   // prologue barrier: LDS tiles 0 .. AHEAD-1 are complete
+    __syncthreads();   // prologue barrier: LDS tile 0 is complete
     if (nt > 0) { read_a(0, 0, fa0); read_b(0, 0, fb0); }
     for (int t = 0; t < nt; ++t) {
         read_a(t, 1, fa1);
         read_b(t, 1, fb1);
-        mfma_quad(fa0, fb0, 0, 0);
-        mfma_quad(fa1, fb0, 1, 0);
-        mfma_quad(fa0, fb1, 0, 1);
-        mfma_quad(fa1, fb1, 1, 1);
+        plane_products<NP, H, true>(fa0, fb0, acc4, 0, 0);
+        plane_products<NP, H, true>(fa1, fb0, acc4, 2, 0);
+        plane_products<NP, H, true>(fa0, fb1, acc4, 0, 2);
+        plane_products<NP, H, true>(fa1, fb1, acc4, 2, 2);
         __syncthreads();
         if (t + 1 < nt) { read_a(t + 1, 0, fa0); read_b(t + 1, 0, fb0); }
     }
@@ -691,7 +457,7 @@ gemm_split_ws_kernel(const GemmParams p) {
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
     const int wm = wave >> 1, wn = wave & 1;
     // (the swizzle key of a fragment row depends on its low five bits only: every block offset below is a multiple of 32 rows)
-    const int fkey = swz_key(lane & 31);
+    const int fkey = L::swz_key(lane & 31);
     const int a_row = (wm * WTM + (lane & 31)) * SLD, b_row = AREG + (wn * WTN + (lane & 31)) * SLD;
     int f_chunk[KSTEPS];
 #pragma unroll
@@ -706,44 +472,26 @@ gemm_split_ws_kernel(const GemmParams p) {
             for (int j = 0; j < TN; ++j) bf[pl][j] = *reinterpret_cast<const bf16x8*>(buf + b_row + (pl * BN + j * 32) * SLD + f_chunk[ks]);
         }
     };
-    auto mfma_all = [&](const bf16x8 (&af)[NP][TM], const bf16x8 (&bf)[NP][TN]) {
-        // smallest plane products first
-#pragma unroll
-        for (int sum = NP - 1; sum >= 0; --sum)
-#pragma unroll
-            for (int pa = 0; pa < NP; ++pa) {
-                const int pb = sum - pa;
-                if (pb < 0 || pb >= NP) continue;
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j)
-                        if constexpr (H) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, bf[pb][j]), __builtin_bit_cast(f16x8, af[pa][i]), acc[i][j], 0, 0, 0);
-                        else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[pb][j], af[pa][i], acc[i][j], 0, 0, 0);   // transposed product: see the C tile image below
-            }
-    };
     bf16x8 fa0[NP][TM], fb0[NP][TN], fa1[NP][TM], fb1[NP][TN];
-    __syncthreads();   // prologue barrier: LDS tiles 0 .. AHEAD-1 are complete
-    if (trc && tid == 0) trc[3] = clock64();
-    constexpr bool XPREFETCH = NBUF >= 3;   // tile t+1 is complete during step t only with a 3-deep ring
+    __syncthreads();   // prologue barrier: LDS tile 0 is complete
+    tr.cycles(tid == 0, 3);
     if (nt > 0 && !(abl & 4)) read_frags(0, 0, fa0, fb0);
     for (int t = 0; t < nt; ++t) {
-        if (trc && tid == 0 && t < 24) trc[128 + t * 4 + 0] = clock64();
+        tr.cycles(tid == 0 && t < 24, 128 + t * 4 + 0);
         if (!(abl & 4)) {
             if (KSTEPS == 2) {
                 read_frags(t, 1, fa1, fb1);
-                mfma_all(fa0, fb0);
-                if (XPREFETCH && t + 1 < nt) read_frags(t + 1, 0, fa0, fb0);
-                mfma_all(fa1, fb1);
+                plane_products<NP, H, true>(fa0, fb0, acc);
+                plane_products<NP, H, true>(fa1, fb1, acc);
             } else {
-                mfma_all(fa0, fb0);
+                plane_products<NP, H, true>(fa0, fb0, acc);
             }
         }
-        if (trc && tid == 0 && t < 24) trc[128 + t * 4 + 1] = clock64();
+        tr.cycles(tid == 0 && t < 24, 128 + t * 4 + 1);
         if (!(abl & 16)) __syncthreads();
-        if ((!XPREFETCH || KSTEPS == 1) && t + 1 < nt && !(abl & 4)) read_frags(t + 1, 0, fa0, fb0);
+        if (t + 1 < nt && !(abl & 4)) read_frags(t + 1, 0, fa0, fb0);
     }
-    if (trc && tid == 0) trc[4] = clock64();
+    tr.cycles(tid == 0, 4);
     // the staging LDS is dead (every fragment read retired at the last barrier): the consumers lay their accumulators down as a
     // row-major image of the C tile
     float* ctile = reinterpret_cast<float*>(smem_raw);
@@ -767,43 +515,35 @@ gemm_split_ws_kernel(const GemmParams p) {
     // latency per tile.  Each pass moves 16 rows x 512 B: one wave = two full rows, float4 per lane ----
     __syncthreads();
     gemm_epilogue_tile<BM, BN, EP_LD>(p, reinterpret_cast<const float*>(smem_raw), m0, n0, tid, slice);
-    if (trc && tid == 0) { trc[5] = clock64(); trc[6] = wall_clock64(); }
+    tr.cycles(tid == 0, 5);
+    tr.wall(tid == 0, 6);
 }
 
-template <int NP, int KS>
+// ---- launcher ----
+// The warp-specialised kernel for NP planes (H: the fp16 pair) and KS-deep stages, by A mode and A layout.
+template <int NP, int KS, bool H>
 static hipError_t launch_split_ws_ks(const GemmParams& p, dim3 grid, hipStream_t s) {
     const dim3 block(512);
-    if (p.h2) {                           // mode f32_half2: two fp16 planes, 32-deep stages, plain or P-layout A
-        if constexpr (NP == 2 && KS == 32) {
-            if (p.a_planes) {
-                if (p.mode != GEMM_DENSE || p.a_planes != 2) return hipErrorInvalidValue;
-                hipLaunchKernelGGL((gemm_split_ws_kernel<GEMM_DENSE, 2, 32, false, true, true>), grid, block, 0, s, p);
-            } else if (p.mode == GEMM_DENSE) hipLaunchKernelGGL((gemm_split_ws_kernel<GEMM_DENSE, 2, 32, false, false, true>), grid, block, 0, s, p);
-            else if (p.mode == GEMM_CONV_NHWC) hipLaunchKernelGGL((gemm_split_ws_kernel<GEMM_CONV_NHWC, 2, 32, false, false, true>), grid, block, 0, s, p);
-            else if (p.mode == GEMM_DEFORM_NHWC) hipLaunchKernelGGL((gemm_split_ws_kernel<GEMM_DEFORM_NHWC, 2, 32, false, false, true>), grid, block, 0, s, p);
-            else return hipErrorInvalidValue;
-            return hipGetLastError();
-        }
-        return hipErrorInvalidValue;
-    }
     if (p.a_planes) {
         if constexpr (NP == 2 && KS == 32) {   // (the 3-plane form works too, but was 2 % slower per forward: rows 1.5x as long)
             if (p.mode != GEMM_DENSE || p.a_planes != NP) return hipErrorInvalidValue;
 #ifdef BRN_DIAG_BUILD
-            if (p.abl || p.trace) { hipLaunchKernelGGL((gemm_split_ws_kernel<GEMM_DENSE, 2, 32, true, true>), grid, block, 0, s, p); return hipGetLastError(); }
+            if constexpr (!H)
+                if (p.abl || p.trace) { hipLaunchKernelGGL((gemm_split_ws_kernel<GEMM_DENSE, 2, 32, true, true>), grid, block, 0, s, p); return hipGetLastError(); }
 #endif
-            hipLaunchKernelGGL((gemm_split_ws_kernel<GEMM_DENSE, 2, 32, false, true>), grid, block, 0, s, p);
+            hipLaunchKernelGGL((gemm_split_ws_kernel<GEMM_DENSE, 2, 32, false, true, H>), grid, block, 0, s, p);
             return hipGetLastError();
         }
         return hipErrorInvalidValue;
     }
 #ifdef BRN_DIAG_BUILD
-    if (p.mode == GEMM_DENSE && KS == 32 && (p.abl || p.trace)) { hipLaunchKernelGGL((gemm_split_ws_kernel<GEMM_DENSE, NP, 32, true, false>), grid, block, 0, s, p); return hipGetLastError(); }
+    if constexpr (!H)
+        if (p.mode == GEMM_DENSE && KS == 32 && (p.abl || p.trace)) { hipLaunchKernelGGL((gemm_split_ws_kernel<GEMM_DENSE, NP, 32, true, false>), grid, block, 0, s, p); return hipGetLastError(); }
 #endif
-    if (p.mode == GEMM_DENSE) hipLaunchKernelGGL((gemm_split_ws_kernel<GEMM_DENSE, NP, KS, false, false>), grid, block, 0, s, p);
-    else if (p.mode == GEMM_CONV_NHWC) hipLaunchKernelGGL((gemm_split_ws_kernel<GEMM_CONV_NHWC, NP, KS, false, false>), grid, block, 0, s, p);
+    if (p.mode == GEMM_DENSE) hipLaunchKernelGGL((gemm_split_ws_kernel<GEMM_DENSE, NP, KS, false, false, H>), grid, block, 0, s, p);
+    else if (p.mode == GEMM_CONV_NHWC) hipLaunchKernelGGL((gemm_split_ws_kernel<GEMM_CONV_NHWC, NP, KS, false, false, H>), grid, block, 0, s, p);
     else if (p.mode == GEMM_DEFORM_NHWC) {
-        if constexpr (NP >= 2 && KS == 32) hipLaunchKernelGGL((gemm_split_ws_kernel<GEMM_DEFORM_NHWC, NP, 32, false, false>), grid, block, 0, s, p);
+        if constexpr (NP >= 2 && KS == 32) hipLaunchKernelGGL((gemm_split_ws_kernel<GEMM_DEFORM_NHWC, NP, 32, false, false, H>), grid, block, 0, s, p);
         else return hipErrorInvalidValue;
     }
     else return hipErrorInvalidValue;
@@ -813,46 +553,46 @@ template <int NP>
 static hipError_t launch_split_ws(const GemmParams& p, hipStream_t s) {
     const int tiles = ((p.M + 127) / 128) * ((p.N + 127) / 128) * p.splitk;
     const dim3 grid(tiles);
+    if (p.h2) {                           // mode f32_half2: two fp16 planes, 32-deep stages
+        if constexpr (NP == 2) return launch_split_ws_ks<2, 32, true>(p, grid, s);
+        else return hipErrorInvalidValue;
+    }
     // 3 planes: 32-deep stages need 120 KB of LDS (one workgroup per CU); 16-deep stages (2 x 36 KB) let two share a CU like the
     // 2-plane kernel's do, at twice the barriers per K: worth it as soon as there is more than one workgroup per CU to place
     // (the deformable loader is built for 32-deep stages only)
-    if (NP == 3 && tiles > 256 && !(p.abl || p.trace) && p.mode != GEMM_DEFORM_NHWC) return launch_split_ws_ks<NP, 16>(p, grid, s);
-    return launch_split_ws_ks<NP, 32>(p, grid, s);
+    if constexpr (NP == 3)
+        if (tiles > 256 && !(p.abl || p.trace) && p.mode != GEMM_DEFORM_NHWC) return launch_split_ws_ks<3, 16, false>(p, grid, s);
+    return launch_split_ws_ks<NP, 32, false>(p, grid, s);
 }
 
-template <int BM, int BN, int WM, int WN, int NP>
+template <int BM, int BN, int WM, int WN, int NP, bool H>
 static hipError_t launch_split_cfg(const GemmParams& p, hipStream_t s) {
     const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN) * p.splitk;
     dim3 grid(tiles), block(WM * WN * 64);
-    if (p.h2) {
-        if constexpr (NP == 2) {
-            if (p.mode == GEMM_DENSE) hipLaunchKernelGGL((gemm_split_kernel<BM, BN, WM, WN, GEMM_DENSE, 2, true>), grid, block, 0, s, p);
-            else if (p.mode == GEMM_CONV_NHWC) hipLaunchKernelGGL((gemm_split_kernel<BM, BN, WM, WN, GEMM_CONV_NHWC, 2, true>), grid, block, 0, s, p);
-            else if (p.mode == GEMM_DEFORM_NHWC) {
-                if constexpr (BM == 64 && BN == 64) hipLaunchKernelGGL((gemm_split_kernel<64, 64, WM, WN, GEMM_DEFORM_NHWC, 2, true>), grid, block, 0, s, p);
-                else return hipErrorInvalidValue;
-            }
-            else return hipErrorInvalidValue;
-            return hipGetLastError();
-        }
-        return hipErrorInvalidValue;
-    }
-    if (p.mode == GEMM_DENSE) hipLaunchKernelGGL((gemm_split_kernel<BM, BN, WM, WN, GEMM_DENSE, NP>), grid, block, 0, s, p);
-    else if (p.mode == GEMM_CONV_NHWC) hipLaunchKernelGGL((gemm_split_kernel<BM, BN, WM, WN, GEMM_CONV_NHWC, NP>), grid, block, 0, s, p);
+    if (p.mode == GEMM_DENSE) hipLaunchKernelGGL((gemm_split_kernel<BM, BN, WM, WN, GEMM_DENSE, NP, H>), grid, block, 0, s, p);
+    else if (p.mode == GEMM_CONV_NHWC) hipLaunchKernelGGL((gemm_split_kernel<BM, BN, WM, WN, GEMM_CONV_NHWC, NP, H>), grid, block, 0, s, p);
     else if (p.mode == GEMM_DEFORM_NHWC) {
-        if constexpr (NP >= 2 && BM == 64 && BN == 64) hipLaunchKernelGGL((gemm_split_kernel<64, 64, WM, WN, GEMM_DEFORM_NHWC, NP>), grid, block, 0, s, p);   // (launch_gemm's deformable tiles: this one and the warp-specialised kernel)
+        if constexpr (NP >= 2 && BM == 64 && BN == 64) hipLaunchKernelGGL((gemm_split_kernel<64, 64, WM, WN, GEMM_DEFORM_NHWC, NP, H>), grid, block, 0, s, p);   // (launch_gemm's deformable tiles: this one and the warp-specialised kernel)
         else return hipErrorInvalidValue;
     }
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
+// the 4-wave tiles: 128x64 for cfg 1, 64x64 for every other plan that is not warp-specialised (as launch_gemm's fp32 ladder treats an unknown cfg)
+template <int NP, bool H>
+static hipError_t launch_split_tile(const GemmParams& p, int cfg, hipStream_t s) {
+    if (cfg == 1) return launch_split_cfg<128, 64, 2, 2, NP, H>(p, s);
+    return launch_split_cfg<64, 64, 2, 2, NP, H>(p, s);
+}
 
 template <int NP>
 static hipError_t launch_split_np(const GemmParams& p, int cfg, hipStream_t s) {
     if (gemm_split_is_ws(cfg)) return launch_split_ws<NP>(p, s);
-    if (cfg == 2) return launch_split_cfg<64, 64, 2, 2, NP>(p, s);
-    if (cfg == 1) return launch_split_cfg<128, 64, 2, 2, NP>(p, s);
-    return launch_split_cfg<128, 128, 2, 2, NP>(p, s);
+    if (p.h2) {
+        if constexpr (NP == 2) return launch_split_tile<2, true>(p, cfg, s);
+        else return hipErrorInvalidValue;
+    }
+    return launch_split_tile<NP, false>(p, cfg, s);
 }
 hipError_t launch_gemm_split(const GemmParams& p, int cfg, hipStream_t s) {
     if (p.planes == 3) return launch_split_np<3>(p, cfg, s);

@@ -91,6 +91,8 @@ def _tile_cases():
                 out += [Case(form, cfg=cfg, N=n, splitk=sk, **geo) for n, sk in _nsk(cfg)]
     # the 16-deep three-plane stage: more than 256 workgroups (17 x 16 tiles; 6 x 7 tiles x 7 slices)
     out += [Case("bf16x3", M=2100, N=2048, K=64, cfg=0), Case("bf16x3", M=700, N=896, K=224, cfg=0, splitk=7)]
+    # the same stage on implicit-GEMM rows: 3 x 16 tiles x 6 slices of three 16-deep K tiles
+    out.append(Case("bf16x3", cfg=0, N=2048, splitk=6, **CONV))
     # an empty last slice: 25 K tiles in 6 slices of 5
     out += [Case(form, M=64, N=64, K=800, cfg=cfg, splitk=6) for form, cfg in [("f32", 2), ("bf16x2", 2), ("bf16x2", 0), ("bf16x3", 0)]]
     return out
