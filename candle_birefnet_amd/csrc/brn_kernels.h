@@ -172,9 +172,9 @@ struct AttentionBiasParams {
 hipError_t launch_attention_bias(const AttentionBiasParams& p, hipStream_t s);
 
 // q/k/v attention for long sequences, online softmax over K / V tiles (kernels/flash_attention.hip; brn_flash_attention_forward and, with
-// a bias, brn_flash_attention_bias_forward):
-// y[b,h] = softmax_rows(scale * (q[b,h] k[b,h]^T [+ bias[b % n_bias, h]]) [causal: key j <= query i]) v[b,h], head_dim 32 / 64 / 128,
-// 1 <= seq_q, seq_kv <= 65536
+// a bias, brn_flash_attention_bias_forward; with grouped K / V heads or a causal mask over a cache, brn_flash_attention_gqa_forward):
+// y[b,h] = softmax_rows(scale * (q[b,h] k[b,h / G]^T [+ bias[b % n_bias, h]]) [causal: key j <= query i + causal_off]) v[b,h / G],
+// G = heads / kv_heads, head_dim 32 / 64 / 128, 1 <= seq_q, seq_kv <= 65536
 struct FlashAttentionParams {
     const float* q; const float* k; const float* v;   // 16-byte aligned; head_dim contiguous
     float* y;             // q's shape and strides
@@ -188,6 +188,9 @@ struct FlashAttentionParams {
     const float* bias;    // [n_bias, heads, seq_q, seq_kv] fp32, 16-byte aligned, added to the UNSCALED scores (-inf: the key is excluded); or null
     int n_bias;           // batch entry b reads pattern b % n_bias (batch % n_bias == 0); 0 exactly when bias is null
     long b_sp, b_sh;      // element strides of bias: pattern, head (heads-major whatever the layout of q / k / v)
+    // brn_flash_attention_gqa_forward; kv_heads == heads and causal_off == 0 = the kernels of the two entries above, untouched
+    int kv_heads;         // K / V heads (k, v strides are theirs): query head h reads K / V head h / (heads / kv_heads); heads % kv_heads == 0
+    int causal_off;       // causal: seq_kv - seq_q >= 0, key j takes part in query i's row exactly when j <= i + causal_off; 0 when not causal
 };
 hipError_t launch_flash_attention(const FlashAttentionParams& p, hipStream_t s);
 

@@ -271,29 +271,39 @@ brn_status brn_attention_forward(const float* q, const float* k, const float* v,
     });
 }
 
-// brn_flash_attention_forward and brn_flash_attention_bias_forward: one body.  who = the message prefix; with_bias = the bias entry, whose
-// bias / n_bias are checked (the bias-free entry passes null / 0)
-static void flash_attention_body(const char* who, bool with_bias, const float* q, const float* k, const float* v, int batch, int seq_q, int seq_kv,
-                                 int heads, int head_dim, int layout, int causal, const float* bias, int n_bias, float scale, float* y,
-                                 brn_mem loc, int device, void* stream) {
+// brn_flash_attention_forward, brn_flash_attention_bias_forward and brn_flash_attention_gqa_forward: one body.  who = the message prefix;
+// with_bias = an entry with a bias, whose bias / n_bias are checked (the bias-free entry passes null / 0); gqa = the grouped entry, whose
+// kv_heads is checked (the other two pass heads) and whose causal mask ends at the last key
+static void flash_attention_body(const char* who, bool with_bias, bool gqa, const float* q, const float* k, const float* v, int batch, int seq_q,
+                                 int seq_kv, int heads, int kv_heads, int head_dim, int layout, int causal, const float* bias, int n_bias,
+                                 float scale, float* y, brn_mem loc, int device, void* stream) {
     if (!q || !k || !v || !y) fail(BRN_ERR_INVALID_ARG, "%s: null q, k, v or y", who);
     if (!(head_dim == 32 || head_dim == 64 || head_dim == 128))
         fail(BRN_ERR_INVALID_ARG, "%s: head_dim %d unsupported (head_dim must be 32, 64 or 128)", who, head_dim);
     if (seq_q < 1 || seq_q > 65536 || seq_kv < 1 || seq_kv > 65536)
         fail(BRN_ERR_INVALID_ARG, "%s: seq_q %d, seq_kv %d unsupported (1 <= seq_q, seq_kv <= 65536)", who, seq_q, seq_kv);
     if (batch < 1 || heads < 1) fail(BRN_ERR_INVALID_ARG, "%s: batch %d, heads %d unsupported (batch >= 1, heads >= 1)", who, batch, heads);
-    if ((long long)batch * heads * ((seq_q + 15) / 16) > 0x7fffffffLL)
+    if (gqa) {
+        if (kv_heads < 1 || kv_heads > heads || heads % kv_heads)
+            fail(BRN_ERR_INVALID_ARG, "%s: kv_heads %d unsupported with heads %d (1 <= kv_heads <= heads, heads %% kv_heads == 0)", who, kv_heads, heads);
+        // the grid: a workgroup per (batch entry, K / V head, 64 packed rows of the group's G * seq_q)
+        const long long rows = (long long)(heads / kv_heads) * seq_q;
+        if (rows > 0x7fffffffLL || (long long)batch * kv_heads * ((rows + 63) / 64) > 0x7fffffffLL)
+            fail(BRN_ERR_INVALID_ARG, "%s: batch %d, heads %d, kv_heads %d, seq_q %d too large (G = heads / kv_heads, G * seq_q < 2^31, batch * kv_heads * ceil(G * seq_q / 64) < 2^31)",
+                 who, batch, heads, kv_heads, seq_q);
+    } else if ((long long)batch * heads * ((seq_q + 15) / 16) > 0x7fffffffLL)
         fail(BRN_ERR_INVALID_ARG, "%s: batch %d, heads %d, seq_q %d too large (batch * heads * ceil(seq_q / 16) < 2^31)", who, batch, heads, seq_q);
     if (layout != BRN_ATTN_BSHD && layout != BRN_ATTN_BHSD) fail(BRN_ERR_INVALID_ARG, "%s: layout %d unknown (layout must be 0 = BSHD or 1 = BHSD)", who, layout);
     if (causal != 0 && causal != 1) fail(BRN_ERR_INVALID_ARG, "%s: causal %d (causal must be 0 or 1)", who, causal);
-    if (causal && seq_q != seq_kv) fail(BRN_ERR_INVALID_ARG, "%s: causal requires seq_q == seq_kv (seq_q %d, seq_kv %d)", who, seq_q, seq_kv);
+    if (causal && gqa && seq_kv < seq_q) fail(BRN_ERR_INVALID_ARG, "%s: causal requires seq_kv >= seq_q (seq_q %d, seq_kv %d)", who, seq_q, seq_kv);
+    if (causal && !gqa && seq_q != seq_kv) fail(BRN_ERR_INVALID_ARG, "%s: causal requires seq_q == seq_kv (seq_q %d, seq_kv %d)", who, seq_q, seq_kv);
     if (with_bias) {
         if (n_bias < 0) fail(BRN_ERR_INVALID_ARG, "%s: n_bias %d is negative (n_bias >= 0)", who, n_bias);
         if ((bias == nullptr) != (n_bias == 0)) fail(BRN_ERR_INVALID_ARG, "%s: bias must be NULL exactly when n_bias == 0 (n_bias %d)", who, n_bias);
         if (n_bias > 0 && batch % n_bias) fail(BRN_ERR_INVALID_ARG, "%s: batch %d is not a multiple of n_bias %d (batch %% n_bias == 0)", who, batch, n_bias);
     }
     if (!scale_arg_ok(scale)) fail(BRN_ERR_INVALID_ARG, "%s: scale must be finite and >= 0 (0 = head_dim^-0.5)", who);
-    const size_t nq = (size_t)batch * heads * seq_q * head_dim, nkv = (size_t)batch * heads * seq_kv * head_dim;
+    const size_t nq = (size_t)batch * heads * seq_q * head_dim, nkv = (size_t)batch * kv_heads * seq_kv * head_dim;
     const size_t nb = (size_t)n_bias * heads * seq_q * seq_kv;
     if (floats_overlap(q, nq, y, nq) || floats_overlap(k, nkv, y, nq) || floats_overlap(v, nkv, y, nq))
         fail(BRN_ERR_INVALID_ARG, "%s: y must not overlap an input", who);
@@ -309,17 +319,18 @@ static void flash_attention_body(const char* who, bool with_bias, const float* q
         p.b_sh = (long)seq_q * seq_kv; p.b_sp = heads * p.b_sh;     // heads-major whatever the layout
     }
     p.y = st.out(y, nq);
-    p.batch = batch; p.heads = heads; p.seq_q = seq_q; p.seq_kv = seq_kv; p.head_dim = head_dim;
-    // one kernel for both layouts: element strides of (batch entry, head, sequence position)
+    p.batch = batch; p.heads = heads; p.kv_heads = kv_heads; p.seq_q = seq_q; p.seq_kv = seq_kv; p.head_dim = head_dim;
+    // one kernel for both layouts: element strides of (batch entry, head, sequence position); k and v have kv_heads heads
     const long d = head_dim;
     if (layout == BRN_ATTN_BSHD) {
         p.q_ss = heads * d; p.q_sh = d; p.q_sb = seq_q * p.q_ss;
-        p.kv_ss = heads * d; p.kv_sh = d; p.kv_sb = seq_kv * p.kv_ss;
+        p.kv_ss = kv_heads * d; p.kv_sh = d; p.kv_sb = seq_kv * p.kv_ss;
     } else {
         p.q_ss = d; p.q_sh = seq_q * d; p.q_sb = heads * p.q_sh;
-        p.kv_ss = d; p.kv_sh = seq_kv * d; p.kv_sb = heads * p.kv_sh;
+        p.kv_ss = d; p.kv_sh = seq_kv * d; p.kv_sb = kv_heads * p.kv_sh;
     }
     p.causal = causal;
+    p.causal_off = causal ? seq_kv - seq_q : 0;
     p.scale = scale_or_default(scale, head_dim);
     p.s16 = attention_op_s16();
     BRN_HIP(launch_flash_attention(p, (hipStream_t)stream));
@@ -329,7 +340,7 @@ static void flash_attention_body(const char* who, bool with_bias, const float* q
 brn_status brn_flash_attention_forward(const float* q, const float* k, const float* v, int batch, int seq_q, int seq_kv, int heads, int head_dim,
                                        int layout, int causal, float scale, float* y, brn_mem loc, int device, void* stream) {
     return guarded([&] {
-        flash_attention_body("flash attention", false, q, k, v, batch, seq_q, seq_kv, heads, head_dim, layout, causal, nullptr, 0, scale, y, loc, device, stream);
+        flash_attention_body("flash attention", false, false, q, k, v, batch, seq_q, seq_kv, heads, heads, head_dim, layout, causal, nullptr, 0, scale, y, loc, device, stream);
     });
 }
 
@@ -337,7 +348,15 @@ brn_status brn_flash_attention_bias_forward(const float* q, const float* k, cons
                                             int layout, int causal, const float* bias, int n_bias, float scale, float* y, brn_mem loc, int device,
                                             void* stream) {
     return guarded([&] {
-        flash_attention_body("flash attention bias", true, q, k, v, batch, seq_q, seq_kv, heads, head_dim, layout, causal, bias, n_bias, scale, y, loc, device, stream);
+        flash_attention_body("flash attention bias", true, false, q, k, v, batch, seq_q, seq_kv, heads, heads, head_dim, layout, causal, bias, n_bias, scale, y, loc, device, stream);
+    });
+}
+
+brn_status brn_flash_attention_gqa_forward(const float* q, const float* k, const float* v, int batch, int seq_q, int seq_kv, int heads, int kv_heads,
+                                           int head_dim, int layout, int causal, const float* bias, int n_bias, float scale, float* y, brn_mem loc,
+                                           int device, void* stream) {
+    return guarded([&] {
+        flash_attention_body("flash attention gqa", true, true, q, k, v, batch, seq_q, seq_kv, heads, kv_heads, head_dim, layout, causal, bias, n_bias, scale, y, loc, device, stream);
     });
 }
 

@@ -46,7 +46,7 @@ void window_generic_route(Ctx& c, const SwinBlockW& blk, const float* qkv, float
             BRN_LAUNCH(launch_window_bias_build(p, c.stream));
         }
         FlashAttentionParams f{};
-        f.heads = heads; f.seq_q = N; f.seq_kv = N; f.head_dim = 32;
+        f.heads = heads; f.kv_heads = heads; f.seq_q = N; f.seq_kv = N; f.head_dim = 32;
         f.q_ss = 32; f.q_sh = (long)N * 32; f.q_sb = (long)heads * f.q_sh;                    // BHSD
         f.kv_ss = f.q_ss; f.kv_sh = f.q_sh; f.kv_sb = f.q_sb;
         f.scale = p.scale; f.s16 = c.bf16;

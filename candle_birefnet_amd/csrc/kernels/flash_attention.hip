@@ -30,6 +30,14 @@
 // before, and become the initial accumulators of S^T = K . Q^T: the bias joins the unscaled fp32 scores at no instruction, and an
 // all-zero bias gives the bits of BIAS = false.  A -inf entry excludes its key (exp2(-inf - m) = 0; it never raises m).  BIAS = false is
 // the kernel as it was, instruction for instruction.  No additional LDS.  DESIGN.md 3.2d.
+// GQA = true (brn_flash_attention_gqa_forward with kv_heads < heads, or a causal mask over a cache, seq_q < seq_kv): a group of
+// G = heads / kv_heads query heads reads one K / V head, and the causal diagonal ends at the last key (key j <= query i + causal_off,
+// causal_off = seq_kv - seq_q >= 0, so key 0 stays visible to every row).  One workgroup = one (batch entry, K / V head, tile of 64
+// PACKED rows); packed row r of the group's G * seq_q is query r / G of query head (K / V head) * G + r % G (fa_block_gqa, fa_lane).
+// Only what a row IS changes — a lane's q and y row, its bias slab and row, its limit; the wave's mask flag; the workgroup's nkt — the
+// walk, the LDS images and the arithmetic are those of GQA = false, whose instantiations serve the two older entries as before.  A row's
+// bits do not depend on which rows share its tile: a K / V tile wholly past a row's limit leaves alpha = exp2(m - m) = 1 and numerators
+// exp2(-3e38 - m) = 0, so the results are those of the plain kernels on K / V repeated G times.  DESIGN.md 3.2f.
 #include "../brn_kernels.h"
 #include "attention_mfma.h"
 #include <type_traits>
@@ -46,11 +54,44 @@ constexpr int FA_VT_LD = 72;         // 16-bit kernel: elements per LDS row of V
 struct FaBlock {
     const float* q; const float* k; const float* v; float* y;
     const float* bias;    // BIAS: the [seq_q, seq_kv] slab of this (bias pattern = batch entry % n_bias, head)
-    int q0;               // first query of the tile
+    int q0;               // first query of the tile (GQA: first packed row)
     int nkt;              // K / V tiles to walk: all of them, or (causal) those that reach the tile's last query
+    int G, h0, rem;       // GQA: query heads per K / V head, the group's first query head, real rows after q0 (the tile's last real row is q0 + min(63, rem))
 };
+// GQA: the workgroup is (batch entry, K / V head, tile of 64 packed rows); q, y and bias point at the batch entry (pattern), the head is a
+// lane's own (fa_lane); k and v at the K / V head
 template <bool BIAS>
+__device__ __forceinline__ FaBlock fa_block_gqa(const FlashAttentionParams& p) {
+    FaBlock r;
+    r.G = p.heads / p.kv_heads;
+    const int rows = r.G * p.seq_q;                      // < 2^31 (launch_flash_attention)
+    const int nqt = (rows - 1) / FA_BQ + 1;
+    // the grid order of fa_block, over (batch entry, K / V head): causal = longest tiles first
+    int bh, qt;
+    if (p.causal) {
+        const unsigned nbh = (unsigned)(p.batch * p.kv_heads);
+        qt = nqt - 1 - (int)(blockIdx.x / nbh); bh = (int)(blockIdx.x % nbh);
+    } else {
+        bh = (int)(blockIdx.x / (unsigned)nqt); qt = (int)(blockIdx.x - (unsigned)bh * (unsigned)nqt);
+    }
+    const int b = bh / p.kv_heads, kvh = bh - b * p.kv_heads;
+    r.q = p.q + b * p.q_sb;
+    r.y = p.y + b * p.q_sb;
+    r.k = p.k + b * p.kv_sb + kvh * p.kv_sh;
+    r.v = p.v + b * p.kv_sb + kvh * p.kv_sh;
+    r.bias = nullptr;
+    if constexpr (BIAS) r.bias = p.bias + (b % p.n_bias) * p.b_sp;
+    r.h0 = kvh * r.G;
+    r.q0 = qt * FA_BQ;
+    r.rem = rows - 1 - r.q0;
+    r.nkt = (p.seq_kv + FA_T - 1) / FA_T;
+    // the tile's last real row holds its last query, whose last visible key is query + causal_off <= seq_kv - 1
+    if (p.causal) r.nkt = min(r.nkt, ((r.q0 + min(FA_BQ - 1, r.rem)) / r.G + p.causal_off) / FA_T + 1);
+    return r;
+}
+template <bool BIAS, bool GQA>
 __device__ __forceinline__ FaBlock fa_block(const FlashAttentionParams& p) {
+    if constexpr (GQA) return fa_block_gqa<BIAS>(p);
     const int nqt = (p.seq_q + FA_BQ - 1) / FA_BQ;
     // not causal: the query tiles of a (batch entry, head) are neighbours in the grid (they walk the same K and V).  Causal: tile qt walks
     // qt + 1 K / V tiles, so the grid is ordered by query tile, last (longest) first: the launch ends on the short workgroups
@@ -72,7 +113,55 @@ __device__ __forceinline__ FaBlock fa_block(const FlashAttentionParams& p) {
     r.q0 = qt * FA_BQ;
     r.nkt = (p.seq_kv + FA_T - 1) / FA_T;
     if (p.causal) r.nkt = min(r.nkt, min(r.q0 + FA_BQ - 1, p.seq_q - 1) / FA_T + 1);
+    r.G = 1; r.h0 = h; r.rem = p.seq_q - 1 - r.q0;         // (not read)
     return r;
+}
+
+// What a lane's row of the workgroup's tile is.  Row = the query q0 + 16 wave + li of the workgroup's head; GQA: the PACKED row of that
+// number among the G * seq_q rows of the K / V head's group, query-major: query = row / G, query head = h0 + row % G, so a wave's 16
+// rows may straddle queries and heads, the K / V tile in LDS serves all G heads, and the causal diagonal of a tile spans 64 / G queries.
+// A pad row (past the last real one) computes on the last real row and is never stored.
+struct FaLane {
+    const float* q;       // the row of q (head_dim floats)
+    int yrow;             // where the row goes in y (fa_lane_y, after the walk): the UNCLAMPED query; GQA: the packed row, -1 for a pad row
+    const float* bias;    // BIAS: the [seq_q, seq_kv] slab of the row's own head, and
+    long brow;            //       the row's offset in it: query * seq_kv
+    int limit;            // the row's first excluded key: seq_kv, or (causal) query + causal_off + 1
+    int wave_row0;        // the first query of the wave's 16 rows (clamped; GQA: + causal_off): the wave's smallest limit - 1 under the causal mask (fa_tile_masks)
+};
+template <bool GQA>
+__device__ __forceinline__ FaLane fa_lane(const FlashAttentionParams& p, const FaBlock& blk, int wave, int li) {
+    FaLane r;
+    if constexpr (GQA) {
+        const int lr = wave * 16 + li;
+        const int row = blk.q0 + min(lr, blk.rem);
+        const int query = row / blk.G, head = blk.h0 + (row - query * blk.G);
+        const long off = head * p.q_sh + query * p.q_ss;
+        r.q = blk.q + off;
+        r.yrow = lr <= blk.rem ? row : -1;
+        r.bias = blk.bias + head * p.b_sh;
+        r.brow = (long)query * p.seq_kv;
+        r.limit = p.causal ? min(p.seq_kv, query + p.causal_off + 1) : p.seq_kv;
+        r.wave_row0 = (blk.q0 + min(wave * 16, blk.rem)) / blk.G + p.causal_off;
+    } else {
+        const int query = blk.q0 + wave * 16 + li, qrow = min(query, p.seq_q - 1);
+        r.q = blk.q + qrow * p.q_ss;
+        r.yrow = query;
+        r.bias = blk.bias;
+        r.brow = (long)qrow * p.seq_kv;
+        r.limit = p.causal ? min(p.seq_kv, qrow + 1) : p.seq_kv;
+        r.wave_row0 = min(blk.q0 + wave * 16, p.seq_q - 1);
+    }
+    return r;
+}
+// the row of y, null for a pad row
+template <bool GQA>
+__device__ __forceinline__ float* fa_lane_y(const FlashAttentionParams& p, const FaBlock& blk, const FaLane& ln) {
+    if constexpr (GQA) {
+        // (query and head are taken from the row a second time: one register across the walk, as the plain kernels have)
+        const int row = max(ln.yrow, 0), query = row / blk.G, head = blk.h0 + (row - query * blk.G);
+        return ln.yrow >= 0 ? blk.y + (head * p.q_sh + query * p.q_ss) : nullptr;
+    } else return ln.yrow < p.seq_q ? blk.y + ln.yrow * p.q_ss : nullptr;
 }
 
 // The bias values a lane adds to its scores of the K / V tile at key0: for sub-tile s the 4 consecutive floats of keys
@@ -83,6 +172,9 @@ __device__ __forceinline__ FaBlock fa_block(const FlashAttentionParams& p) {
 // excluded key and is replaced before the maximum.  No address depends on a bias value.
 // A/B switch (make EXTRA_CXXFLAGS=-DFA_BIAS_NONTEMPORAL=1): the 16-byte bias loads as non-temporal loads.  Every bias element is read once by
 // one lane, so it has nothing to gain from the caches; DESIGN.md 3.2d has what the two builds measured.
+#ifndef FA_FORCE_PACKED
+#define FA_FORCE_PACKED 0
+#endif
 #ifndef FA_BIAS_NONTEMPORAL
 #define FA_BIAS_NONTEMPORAL 0
 #endif
@@ -147,23 +239,19 @@ __device__ __forceinline__ void fa_finish(float* yrow, int g, const f32x4 (&o)[N
 
 // ---- fp32: v_mfma_f32_16x16x4_f32, an exact fmaf chain per score and per output ----
 // LDS: Ks, Vs [64][D + 4] floats (D 128: 66 KB).  Staging item = (key, 4-wide d chunk), D / 16 items of K and of V per thread.
-template <int D, bool BIAS>
+template <int D, bool BIAS, bool GQA>
 __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const FlashAttentionParams p) {
     constexpr int LD = D + 4, NI = D / 16, ND = D / 16, NC = D / 32;
     __shared__ __attribute__((aligned(16))) float Ks[FA_T * LD];
     __shared__ __attribute__((aligned(16))) float Vs[FA_T * LD];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, g = lane >> 4;
-    const FaBlock blk = fa_block<BIAS>(p);
-
-    const int query = blk.q0 + wave * 16 + li, qrow = min(query, p.seq_q - 1);
-    const int wave_row0 = min(blk.q0 + wave * 16, p.seq_q - 1);
-    const int limit = p.causal ? min(p.seq_kv, qrow + 1) : p.seq_kv;
-    const long brow = (long)qrow * p.seq_kv;       // BIAS: the query's row of the bias slab
+    const FaBlock blk = fa_block<BIAS, GQA>(p);
+    const FaLane ln = fa_lane<GQA>(p, blk, wave, li);
     // Q fragment: chunk c of 32 d's -> d = 32 c + 8 g .. + 7 of the query's row (the MFMA k order is a permutation of d; K uses the same)
     f32x4 qv[2 * NC];
     {
-        const float* qp = blk.q + qrow * p.q_ss + g * 8;
+        const float* qp = ln.q + g * 8;
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             qv[2 * c] = *reinterpret_cast<const f32x4*>(qp + c * 32);
@@ -181,7 +269,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
             vr[i] = *reinterpret_cast<const f32x4*>(blk.v + src);
             if (t >= p.seq_kv) { kr[i] = f32x4{0.f, 0.f, 0.f, 0.f}; vr[i] = kr[i]; }
         }
-        if constexpr (BIAS) fa_load_bias(bn, blk.bias, brow, key0, g, p.seq_kv);
+        if constexpr (BIAS) fa_load_bias(bn, ln.bias, ln.brow, key0, g, p.seq_kv);
     };
     f32x4 o[ND];
 #pragma unroll
@@ -214,7 +302,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
             for (int c = 0; c < NC; ++c) acc = att_score_f32(Ks + (s * 16 + li) * LD + c * 32 + g * 8, qv[2 * c], qv[2 * c + 1], acc);
             st[s] = acc;
         }
-        const float alpha = fa_softmax_tile(st, sc2, fa_tile_masks(p, kt * FA_T, wave_row0), kt * FA_T, g, limit, m, l);
+        const float alpha = fa_softmax_tile(st, sc2, fa_tile_masks(p, kt * FA_T, ln.wave_row0), kt * FA_T, g, ln.limit, m, l);
 #pragma unroll
         for (int dt = 0; dt < ND; ++dt) o[dt] *= alpha;
         // O^T += V^T . P^T
@@ -228,7 +316,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
             }
         }
     }
-    fa_finish<ND, BIAS>(query < p.seq_q ? blk.y + query * p.q_ss : nullptr, g, o, l, m);
+    fa_finish<ND, BIAS>(fa_lane_y<GQA>(p, blk, ln), g, o, l, m);
 }
 
 // ---- 16-bit: q, k, v rounded to E (round to nearest even) as they are loaded; v_mfma_f32_16x16x32_{bf16,f16} with fp32 accumulation.
@@ -236,7 +324,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
 // LDS: Kp[key][D] and Vt[d][72 keys] (kernels/attention_mfma.h): D 128 = 16 + 18 KB.
 // Staging item = (key pair, 4-wide d chunk): thread -> (d chunk low 2 bits, key pair, d chunk high bits), so a quad of lanes reads 64
 // contiguous bytes of a row and the 4-byte transposed V writes of a wave fall 2-way on the 32 banks. ----
-template <typename E, int D, bool BIAS>
+template <typename E, int D, bool BIAS, bool GQA>
 __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const FlashAttentionParams p) {
     constexpr bool F16 = std::is_same<E, _Float16>::value;
     constexpr int NP = D / 32, ND = D / 16;       // staging passes = MFMA k steps of a score tile; d tiles of O^T
@@ -246,16 +334,12 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
     __shared__ __attribute__((aligned(16))) E Vt[D * FA_VT_LD];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, g = lane >> 4;
-    const FaBlock blk = fa_block<BIAS>(p);
-
-    const int query = blk.q0 + wave * 16 + li, qrow = min(query, p.seq_q - 1);
-    const int wave_row0 = min(blk.q0 + wave * 16, p.seq_q - 1);
-    const int limit = p.causal ? min(p.seq_kv, qrow + 1) : p.seq_kv;
-    const long brow = (long)qrow * p.seq_kv;       // BIAS: the query's row of the bias slab
+    const FaBlock blk = fa_block<BIAS, GQA>(p);
+    const FaLane ln = fa_lane<GQA>(p, blk, wave, li);
     // Q fragment of MFMA k step c: d = 32 c + 8 g .. + 7 of the query's row
     ex8 qf[NP];
     {
-        const float* qp = blk.q + qrow * p.q_ss + g * 8;
+        const float* qp = ln.q + g * 8;
 #pragma unroll
         for (int c = 0; c < NP; ++c) qf[c] = att_round8<E>(*reinterpret_cast<const f32x4*>(qp + c * 32), *reinterpret_cast<const f32x4*>(qp + c * 32 + 4));
     }
@@ -276,7 +360,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
                 if (t >= p.seq_kv) { kr[ps][u] = f32x4{0.f, 0.f, 0.f, 0.f}; vr[ps][u] = kr[ps][u]; }
             }
         }
-        if constexpr (BIAS) fa_load_bias(bn, blk.bias, brow, key0, g, p.seq_kv);
+        if constexpr (BIAS) fa_load_bias(bn, ln.bias, ln.brow, key0, g, p.seq_kv);
     };
     f32x4 o[ND];
 #pragma unroll
@@ -318,7 +402,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
             for (int c = 0; c < NP; ++c) acc = att_mfma<F16>(att_k_frag<D>(Kp + key * D, key, c * 4 + g), qf[c], acc);
             st[s] = acc;
         }
-        const float alpha = fa_softmax_tile(st, sc2, fa_tile_masks(p, kt * FA_T, wave_row0), kt * FA_T, g, limit, m, l);
+        const float alpha = fa_softmax_tile(st, sc2, fa_tile_masks(p, kt * FA_T, ln.wave_row0), kt * FA_T, g, ln.limit, m, l);
 #pragma unroll
         for (int dt = 0; dt < ND; ++dt) o[dt] *= alpha;
         // O^T += V^T . P^T: k step t = key sub-tiles (2t, 2t+1)
@@ -329,35 +413,48 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
             for (int dt = 0; dt < ND; ++dt) o[dt] = att_mfma<F16>(att_vt_frag(Vt + (dt * 16 + li) * FA_VT_LD + g * 4, t), pf, o[dt]);
         }
     }
-    fa_finish<ND, BIAS>(query < p.seq_q ? blk.y + query * p.q_ss : nullptr, g, o, l, m);
+    fa_finish<ND, BIAS>(fa_lane_y<GQA>(p, blk, ln), g, o, l, m);
 }
 
-template <int D, bool BIAS>
+template <int D, bool BIAS, bool GQA>
 void fa_launch(const FlashAttentionParams& p, dim3 grid, hipStream_t s) {
     const dim3 block(FA_THREADS);
-    if (p.s16 == 0) hipLaunchKernelGGL((flash_attention_f32_kernel<D, BIAS>), grid, block, 0, s, p);
-    else if (p.s16 == 1) hipLaunchKernelGGL((flash_attention_s16_kernel<__bf16, D, BIAS>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((flash_attention_s16_kernel<_Float16, D, BIAS>), grid, block, 0, s, p);
+    if (p.s16 == 0) hipLaunchKernelGGL((flash_attention_f32_kernel<D, BIAS, GQA>), grid, block, 0, s, p);
+    else if (p.s16 == 1) hipLaunchKernelGGL((flash_attention_s16_kernel<__bf16, D, BIAS, GQA>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((flash_attention_s16_kernel<_Float16, D, BIAS, GQA>), grid, block, 0, s, p);
 }
 template <int D>
-void fa_launch(const FlashAttentionParams& p, dim3 grid, hipStream_t s) {
-    if (p.bias) fa_launch<D, true>(p, grid, s);
-    else fa_launch<D, false>(p, grid, s);
+void fa_launch(const FlashAttentionParams& p, bool gqa, dim3 grid, hipStream_t s) {
+    if (gqa) {
+        if (p.bias) fa_launch<D, true, true>(p, grid, s);
+        else fa_launch<D, false, true>(p, grid, s);
+    } else {
+        if (p.bias) fa_launch<D, true, false>(p, grid, s);
+        else fa_launch<D, false, false>(p, grid, s);
+    }
 }
 
 }  // namespace
 
 hipError_t launch_flash_attention(const FlashAttentionParams& p, hipStream_t s) {
     if (!(p.head_dim == 32 || p.head_dim == 64 || p.head_dim == 128) || p.seq_q < 1 || p.seq_kv < 1 || p.seq_q > 65536 || p.seq_kv > 65536 ||
-        p.batch < 1 || p.heads < 1 || (p.causal && p.seq_q != p.seq_kv) || p.s16 < 0 || p.s16 > 2 || !(p.scale > 0.f) ||
+        p.batch < 1 || p.heads < 1 || p.kv_heads < 1 || p.kv_heads > p.heads || p.heads % p.kv_heads ||
+        p.causal_off != (p.causal ? p.seq_kv - p.seq_q : 0) || p.causal_off < 0 || p.s16 < 0 || p.s16 > 2 || !(p.scale > 0.f) ||
         p.n_bias < 0 || (p.bias == nullptr) != (p.n_bias == 0) || (p.n_bias > 0 && p.batch % p.n_bias))
         return hipErrorInvalidValue;
-    const long nwg = (long)p.batch * p.heads * ((p.seq_q + FA_BQ - 1) / FA_BQ);
+    // one K / V head per query head and the diagonal at key = query: the kernels of the two older entries, a workgroup per (batch entry,
+    // head, 64 queries).  Otherwise the packed-row kernels, a workgroup per (batch entry, K / V head, 64 packed rows)
+    // A/B switch (make EXTRA_CXXFLAGS=-DFA_FORCE_PACKED=1): the packed-row kernels also where G == 1 and the diagonal is at key = query — the
+    // same rows, grid order and addresses as the plain kernels, so the two builds differ by the kernels' code alone.  DESIGN.md 3.2f
+    const bool gqa = FA_FORCE_PACKED || p.kv_heads != p.heads || p.causal_off != 0;
+    const long rows = (long)(p.heads / p.kv_heads) * p.seq_q;
+    if (rows > 0x7fffffffL) return hipErrorInvalidValue;
+    const long nwg = (long)p.batch * p.kv_heads * ((rows + FA_BQ - 1) / FA_BQ);
     if (nwg > 0x7fffffffL) return hipErrorInvalidValue;
     const dim3 grid((unsigned)nwg);
-    if (p.head_dim == 32) fa_launch<32>(p, grid, s);
-    else if (p.head_dim == 64) fa_launch<64>(p, grid, s);
-    else fa_launch<128>(p, grid, s);
+    if (p.head_dim == 32) fa_launch<32>(p, gqa, grid, s);
+    else if (p.head_dim == 64) fa_launch<64>(p, gqa, grid, s);
+    else fa_launch<128>(p, gqa, grid, s);
     return hipGetLastError();
 }
 

@@ -158,6 +158,34 @@ def flash_attention(q, k, v, causal=False, scale=None, layout="bshd", device=0, 
     return y
 
 
+def flash_attention_gqa(q, k, v, kv_heads=None, causal=False, scale=None, layout="bshd", bias=None, device=0):
+    """brn_flash_attention_gqa_forward: flash_attention with K / V heads shared by groups of G = heads / kv_heads query heads (query head h
+    reads K / V head h // G, the repeat_interleave(G) convention) and a causal mask that ends at the last key (key j <= query i +
+    seq_kv - seq_q; seq_kv >= seq_q: attention over a K / V cache).  layout "bshd": q [batch, seq_q, heads, head_dim], k, v
+    [batch, seq_kv, kv_heads, head_dim]; "bhsd": [batch, heads, seq_q, head_dim] and [batch, kv_heads, seq_kv, head_dim].  kv_heads None =
+    taken from k's shape.  bias: as in flash_attention, [n_bias, heads, seq_q, seq_kv] fp32 indexed by QUERY head, or None.  y has q's
+    shape.  The limits are the library's (include/birefnet_hip.h): nothing is checked here."""
+    lay = _ATTN_LAYOUT[layout]
+    seq_axis, head_axis = (1, 2) if lay == _ffi.BRN_ATTN_BSHD else (2, 1)
+    batch, hd = int(q.shape[0]), int(q.shape[3])
+    seq_q, heads, seq_kv = int(q.shape[seq_axis]), int(q.shape[head_axis]), int(k.shape[seq_axis])
+    if kv_heads is None:
+        kv_heads = int(k.shape[head_axis])
+    kv_shape = (batch, seq_kv, kv_heads, hd) if lay == _ffi.BRN_ATTN_BSHD else (batch, kv_heads, seq_kv, hd)
+    pq, loc, keep, _ = T.as_arg(q)
+    pk, kloc, kkeep, _ = T.as_arg(k, kv_shape)
+    pv, vloc, vkeep, _ = T.as_arg(v, kv_shape)
+    n_bias = int(bias.shape[0]) if bias is not None else 0
+    pb, bloc, bkeep, _ = T.as_arg(bias, (n_bias, heads, seq_q, seq_kv)) if bias is not None else (None, loc, None, None)
+    if not (kloc == vloc == bloc == loc):
+        raise ValueError("q, k, v and bias must live on the same side")
+    y = T.alloc_like(keep, tuple(int(s) for s in q.shape))
+    _ffi.check(_ffi.lib.brn_flash_attention_gqa_forward(pq, pk, pv, batch, seq_q, seq_kv, heads, int(kv_heads), hd, lay, int(bool(causal)), pb, n_bias,
+                                                        float(scale) if scale is not None else 0.0, T.ptr_of(y), loc, T.device_of(keep, device),
+                                                        T.stream_of(keep)))
+    return y
+
+
 def patch_merging(x, H, W, norm_g, norm_b, reduction_w, device=0):
     """PatchMerging::forward (swin.rs:491-527): x [B,H*W,C] -> [B, ceil(H/2)*ceil(W/2), 2C]."""
     B, L, Cc = (int(v) for v in x.shape)

@@ -329,12 +329,44 @@ brn_status brn_flash_attention_forward(const float* q, const float* k, const flo
  * y overlaps neither an input nor the bias; a BRN_MEM_DEVICE bias is 16-byte aligned.
  * The invariants of the bias-free entry hold: no split over keys, no atomics; an output row depends only on its own (batch entry, head)
  * and its bias pattern; the bits depend neither on `batch` nor on the launch grid, and a repeated call repeats its bits.
- * Not provided: a bias broadcast over heads; 16-bit bias storage; a causal mask with seq_q != seq_kv. */
+ * Not provided: a bias broadcast over heads; 16-bit bias storage; a causal mask with seq_q != seq_kv (brn_flash_attention_gqa_forward
+ * below has it for seq_q < seq_kv, and K / V heads shared by a group of query heads). */
 brn_status brn_flash_attention_bias_forward(const float* q, const float* k, const float* v,
                                             int batch, int seq_q, int seq_kv, int heads, int head_dim,
                                             int layout, int causal,
                                             const float* bias, int n_bias, float scale,
                                             float* y, brn_mem loc, int device_ordinal, void* stream);
+/* brn_flash_attention_bias_forward for the attention of current decoders: a group of G = heads / kv_heads query heads shares one K / V
+ * head (grouped-query attention; kv_heads 1 = multi-query), and the causal mask may lie over a K / V cache (seq_q < seq_kv: chunked
+ * prefill, speculative or single-token decode):
+ *   y[b,h] = softmax_rows( scale * (q[b,h] k[b, h / G]^T + bias[b % n_bias, h])  [causal mask] ) v[b, h / G]
+ * q, y: [batch, seq_q, heads, head_dim] (BRN_ATTN_BSHD) or [batch, heads, seq_q, head_dim] (BRN_ATTN_BHSD); k, v: the same with seq_kv
+ * and kv_heads.  Query head h reads K / V head h / G (the repeat_interleave(G) convention); K and V are never repeated in memory, and
+ * a K / V tile is staged once for the G heads of its group.
+ * bias: optional, [n_bias, heads, seq_q, seq_kv] fp32 indexed by QUERY head, with the rules of brn_flash_attention_bias_forward: added
+ * to the unscaled scores, never rounded, -inf excludes a key, a row whose every visible key is -inf comes back NaN; n_bias 0 with bias
+ * NULL selects the bias-free kernels.
+ * causal 1: key j takes part in query i's row exactly when j <= i + (seq_kv - seq_q): the diagonal ends at the last key, so the last
+ * query sees every key and query 0 sees keys 0 .. seq_kv - seq_q.  It requires seq_kv >= seq_q (every row sees key 0); with
+ * seq_q == seq_kv it is the mask of the two entries above.  A masked key is a real exclusion, as there.
+ * layout, scale, loc, the stream rules and the arithmetic by brn_set_op_compute are those of the two entries above: one exact fp32
+ * kernel for BRN_F32 and the three plane modes, the 16-bit kernels for BRN_BF16 / BRN_F16.  No split over keys, no atomics; a row's
+ * bits depend only on its own (batch entry, query head, bias pattern), neither on `batch` nor on the launch grid nor on which rows
+ * share its workgroup; a repeated call repeats its bits.  The result carries the bits of brn_flash_attention_forward /
+ * brn_flash_attention_bias_forward called on k, v repeated G times along heads (and, over a cache, with the causal mask written into the
+ * bias as -inf).  With kv_heads == heads and seq_q == seq_kv (or causal 0) the call runs the kernels of those entries.
+ * Limits (each violation is BRN_ERR_INVALID_ARG with the prefix "flash attention gqa:" and a message naming the limit, checked before
+ * the device): every limit of brn_flash_attention_bias_forward except its causal one and its grid limit, which become: causal requires
+ * seq_kv >= seq_q; G * seq_q < 2^31 and batch * kv_heads * ceil(G * seq_q / 64) < 2^31.  1 <= kv_heads <= heads and
+ * heads % kv_heads == 0.
+ * Not provided: a split over keys for single-token decode at long seq_kv (it contradicts the no-split invariant these entries promise:
+ * a decode call is one workgroup per 64 / G .. 64 rows of a K / V head); sliding-window masks; variable-length batches; 16-bit tensors
+ * at the boundary. */
+brn_status brn_flash_attention_gqa_forward(const float* q, const float* k, const float* v,
+                                           int batch, int seq_q, int seq_kv, int heads, int kv_heads, int head_dim,
+                                           int layout, int causal,
+                                           const float* bias, int n_bias, float scale,
+                                           float* y, brn_mem loc, int device_ordinal, void* stream);
 /* PatchMerging::forward (swin.rs:491-527): x [B,H*W,C] -> [B, ceil(H/2)*ceil(W/2), 2C]. */
 brn_status brn_patch_merging_forward(const float* x, int B, int H, int W, int C, const float* norm_g,
                                      const float* norm_b, const float* reduction_w, float* y, brn_mem loc,

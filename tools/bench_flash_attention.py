@@ -15,7 +15,16 @@ Swin windows of 16 and 24 ((64, 256, 6, 32) and (16, 576, 6, 32)), come with it;
 form, n_bias = n_windows = batch.  Per record: ms with and without the bias, their difference, and that difference set against
 bias bytes / 8 TB/s — the share of the HBM roof the bias stream reaches (non-causal: every bias byte is read exactly once).
 
-  python tools/bench_flash_attention.py [--bias] [--row N] [--mode f32|bf16|f16] [--json PATH]"""
+--gqa times brn_flash_attention_gqa_forward beside the route it replaces, on the same values and in the same process, the two sides
+ALTERNATING in 5 rounds of 3 warm-up + 10 timed calls each (median and fastest over the 50 calls of a side; spread = the lowest and the
+highest of its 5 round medians).  Rows (batch, seq_q, seq_kv, heads, kv_heads, head_dim):
+  seq_q == seq_kv   the grouped call, not causal and causal, against brn_flash_attention_forward on K / V materialised G times along heads
+                    (the repeat itself is made once, outside the timed calls: the older route is not charged for it)
+  seq_q <  seq_kv   the causal call over the cache against brn_flash_attention_bias_forward, not causal, on repeated K / V with the mask as
+                    a [1, heads, seq_q, seq_kv] fp32 bias of 0 / -inf
+Each record says whether the two sides returned the same bits.
+
+  python tools/bench_flash_attention.py [--bias | --gqa] [--row N] [--mode f32|bf16|f16] [--json PATH]"""
 import argparse
 import json
 import os
@@ -27,6 +36,8 @@ ROWS = [(484, 144, 6, 32), (1, 144, 484 * 6, 32), (1, 512, 32, 128), (1, 1024, 3
         (1, 8192, 32, 128), (4, 2048, 8, 64)]                      # batch, seq, heads, head_dim
 BIAS_ROWS = ROWS + [(64, 256, 6, 32), (16, 576, 6, 32)]          # + Swin windows of 16 and 24 (Swin-384 / SwinV2 geometries)
 SWIN_ROWS = [(484, 144, 6, 32), (64, 256, 6, 32), (16, 576, 6, 32)]
+GQA_ROWS = [(1, 4096, 4096, 32, 8, 128), (4, 2048, 2048, 32, 8, 64), (1, 512, 4096, 32, 8, 128), (16, 1, 4096, 32, 8, 128)]
+GQA_ROUNDS, GQA_WARMUP, GQA_TIMED = 5, 3, 10
 HBM_BYTES_PER_S = 8.0e12
 MODES = ["f32", "bf16", "f16"]
 WARMUP, TIMED = 5, 20
@@ -147,9 +158,74 @@ def bench_bias(row, mode):
     return out
 
 
+def _time_alternating(fns):
+    """the sides of a comparison, alternating: per side (median ms, fastest ms, lowest round median, highest round median, last result)"""
+    import torch
+    ms = [[] for _ in fns]
+    meds = [[] for _ in fns]
+    ys = [None] * len(fns)
+    for _ in range(GQA_ROUNDS):
+        for i, fn in enumerate(fns):
+            for _ in range(GQA_WARMUP):
+                fn()
+            torch.cuda.synchronize()
+            r = []
+            for _ in range(GQA_TIMED):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                ys[i] = fn()
+                e1.record()
+                e1.synchronize()
+                r.append(e0.elapsed_time(e1))
+            ms[i] += r
+            meds[i].append(sorted(r)[len(r) // 2])
+    return [(sorted(m)[len(m) // 2], min(m), min(md), max(md), y) for m, md, y in zip(ms, meds, ys)]
+
+
+def bench_gqa(row, mode):
+    import torch
+    from candle_birefnet_amd import ops
+    batch, seq_q, seq_kv, heads, kv_heads, hd = row
+    G = heads // kv_heads
+    g = torch.Generator(device="cuda").manual_seed(1)
+    q = torch.randn(batch, seq_q, heads, hd, device="cuda", generator=g)
+    k, v = (torch.randn(batch, seq_kv, kv_heads, hd, device="cuda", generator=g) for _ in range(2))
+    kr, vr = (a.repeat_interleave(G, dim=2).contiguous() for a in (k, v))
+    out = []
+    ops.set_compute(mode)
+    try:
+        for causal in ((False, True) if seq_q == seq_kv else (True,)):
+            if seq_q == seq_kv:
+                old_name, bias = "flash_attention on repeated K/V", None
+                old = lambda: ops.flash_attention(q, kr, vr, causal=causal)
+                flop = 4.0 * batch * heads * seq_q * seq_kv * hd / (2 if causal else 1)
+            else:
+                old_name = "flash_attention + -inf mask bias on repeated K/V"
+                vis = torch.arange(seq_kv, device="cuda")[None, :] <= torch.arange(seq_q, device="cuda")[:, None] + (seq_kv - seq_q)
+                bias = torch.where(vis, 0.0, float("-inf")).to(torch.float32).expand(1, heads, seq_q, seq_kv).contiguous()
+                old = lambda: ops.flash_attention(q, kr, vr, causal=False, bias=bias)
+                flop = 4.0 * batch * heads * hd * float(vis.sum())
+            new = lambda: ops.flash_attention_gqa(q, k, v, causal=causal)
+            (nm, nf, nlo, nhi, yn), (om, of, olo, ohi, yo) = _time_alternating([new, old])
+            assert bool(torch.isfinite(yn).all())
+            rec = {"batch": batch, "seq_q": seq_q, "seq_kv": seq_kv, "heads": heads, "kv_heads": kv_heads, "head_dim": hd, "mode": mode, "causal": int(causal),
+                   "gqa_ms_median": round(nm, 4), "gqa_ms_fastest": round(nf, 4), "gqa_round_medians": [round(nlo, 4), round(nhi, 4)],
+                   "gqa_tflops": round(flop / nm / 1e9, 2), "old_route": old_name, "old_ms_median": round(om, 4), "old_ms_fastest": round(of, 4),
+                   "old_round_medians": [round(olo, 4), round(ohi, 4)], "same_bits": bool(torch.equal(yn, yo))}
+            out.append(rec)
+            print(f"{batch:3d} x {seq_q:5d} / {seq_kv:5d} x {heads:3d} / {kv_heads:2d} x {hd:3d} {mode:4s} causal {int(causal)}: gqa {nm:9.4f} ms [{nlo:.4f} .. {nhi:.4f}] "
+                  f"{rec['gqa_tflops']:7.2f} TF/s | {old_name} {om:9.4f} ms [{olo:.4f} .. {ohi:.4f}] | same bits {rec['same_bits']}", flush=True)
+            del bias
+    finally:
+        ops.set_compute("f32")
+    torch.cuda.empty_cache()
+    return out
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--bias", action="store_true", help="time brn_flash_attention_bias_forward beside the bias-free call and torch + bias")
+    ap.add_argument("--gqa", action="store_true", help="time brn_flash_attention_gqa_forward beside the older entries on repeated K / V (and a -inf mask bias)")
     ap.add_argument("--row", type=int, choices=range(len(BIAS_ROWS)))
     ap.add_argument("--mode", choices=MODES)
     ap.add_argument("--json", help="write the records to this file")
@@ -158,13 +234,16 @@ if __name__ == "__main__":
     if cb.device_count() < 1:
         sys.exit("no HIP device: nothing is measured")
     recs = []
-    rows = BIAS_ROWS if a.bias else ROWS
+    if a.bias and a.gqa:
+        sys.exit("--bias and --gqa are two tables: one at a time")
+    rows = BIAS_ROWS if a.bias else GQA_ROWS if a.gqa else ROWS
     if a.row is not None and a.row >= len(rows):
-        sys.exit(f"--row {a.row}: only {len(rows)} rows without --bias")
+        sys.exit(f"--row {a.row}: only {len(rows)} rows in this table")
     for row in (rows if a.row is None else [rows[a.row]]):
         for mode in (MODES if a.mode is None else [a.mode]):
-            recs += bench_bias(row, mode) if a.bias else bench(row, mode)
+            recs += bench_bias(row, mode) if a.bias else bench_gqa(row, mode) if a.gqa else bench(row, mode)
     if a.json:
         with open(a.json, "w") as f:
-            json.dump({"tool": "tools/bench_flash_attention.py" + (" --bias" if a.bias else ""), "warmup": WARMUP, "timed": TIMED, "rows": recs}, f, indent=1)
+            json.dump({"tool": "tools/bench_flash_attention.py" + (" --bias" if a.bias else " --gqa" if a.gqa else ""), "warmup": GQA_WARMUP if a.gqa else WARMUP,
+                       "timed": GQA_ROUNDS * GQA_TIMED if a.gqa else TIMED, "rows": recs}, f, indent=1)
             f.write("\n")
