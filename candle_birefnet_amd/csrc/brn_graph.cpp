@@ -37,12 +37,12 @@ static void fill_geometry(GemmParams& p, const GemmW& w, int Hin, int Win, int C
 }
 static void fill_epilogue(GemmParams& p, const GemmW& w) { p.bias = w.bias; p.scale = w.scale; p.shift = w.shift; p.act = w.act; }
 // the weights of the fp32 kernels: the fp32 matrix and, in the split modes, its planes
-static void fill_weights_f32(GemmParams& p, const GemmW& w) {
+void fill_weights_f32(GemmParams& p, const GemmW& w) {
     p.W = w.w; p.Wp = w.wp; p.planes = w.planes; p.wp_rows = w.wp_rows;
     p.h2 = w.half;
     if (w.half) { p.a_scale = half2_act_scale(); p.out_scale = 1.f / (p.a_scale * w.w_scale); }
 }
-static GemmParams dense_params(const GemmW& w, const GemmIO& io) {
+GemmParams dense_params(const GemmW& w, const GemmIO& io) {
     GemmParams p{};
     p.A = io.A; p.C = io.C; p.M = io.M; p.N = w.N; p.K = w.K; p.mode = GEMM_DENSE; p.lda = io.lda;
     fill_epilogue(p, w);

@@ -66,6 +66,17 @@ inline void join_branches(Ctx& c, unsigned mask) {
 using WindowGenericRoute = void (*)(Ctx& c, const SwinBlockW& blk, const float* qkv, float* att, int B, int H, int W, int C, int window, int shift);
 extern WindowGenericRoute g_window_generic_route;      // defined in brn_graph_swin.cpp
 
+// ---- GEMM -> LayerNorm with the split-K slices summed by the LayerNorm (brn_gemm_ln.cpp) ---------------------------------------------
+// x_out = io.A w^T + bias + io.R (io.C, which may be io.R: the residual stream in place) and y = LayerNorm(x_out) into `out`, as a GEMM that
+// leaves its raw slices (GemmPlan::raw) and a LayerNorm that sums them (LayerNormParams::part): no splitk_reduce_kernel, and x is not read
+// back.  false = nothing enqueued or allocated (one slice planned, not a split mode, an activation ...): the caller launches the pair.
+// Registered like the generic window route; null = today's launches.  Allocates the slice scratch identically in a dry run.
+using GemmLnRoute = bool (*)(Ctx& c, const GemmW& w, const GemmIO& io, const LNW& ln, const LnOut& out);
+extern GemmLnRoute g_gemm_ln_route;                    // defined in brn_graph_swin.cpp
+// the dense descriptor of run_gemm and its fp32-class weights (brn_graph.cpp)
+GemmParams dense_params(const GemmW& w, const GemmIO& io);
+void fill_weights_f32(GemmParams& p, const GemmW& w);
+
 constexpr int AUX_IPT = 3, AUX_LAT = 4;
 constexpr unsigned AUX_ASPP_MASK = 7u;
 struct ArenaHold { Arena& a; explicit ArenaHold(Arena& a_) : a(a_) { ++a.hold; } ~ArenaHold() { --a.hold; } };

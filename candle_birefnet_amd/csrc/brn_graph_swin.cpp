@@ -5,6 +5,7 @@
 namespace brn {
 
 WindowGenericRoute g_window_generic_route = nullptr;    // set by brn_window_generic.cpp's registrar (brn_graph.h)
+GemmLnRoute g_gemm_ln_route = nullptr;                  // set by brn_gemm_ln.cpp's registrar
 
 void swin_stage_dims(int H, int W, int patch, int hs[4], int ws[4]) {
     int h = (H + patch - 1) / patch, w = (W + patch - 1) / patch;   // PatchEmbed pads to a multiple (swin.rs:696-702)
@@ -66,6 +67,9 @@ static bool swin_attention_multi(Ctx& c, const SwinBlockW& blk, const float* xn,
     // swin.rs:310 (+ shortcut, swin.rs:406); the residual stream y / residual stays fp32 in every mode
     bool ln_done = false;
     if (ln2 && xn2 && !p2 && y == residual) ln_done = linear_residual_ln(c, blk.proj, att, M, ldp, y, *ln2, xn2, ld_xn2);
+    // split modes: where the projection is cut along K, norm2 sums the slices (brn_gemm_ln.cpp)
+    if (!ln_done && ln2 && xn2 && y == residual && g_gemm_ln_route)
+        ln_done = g_gemm_ln_route(c, blk.proj, GemmIO(att, M, ldp).to(y, C).add(residual, C).planes(p2, 0).f32(c.bf16, c.bf16), *ln2, LnOut(xn2, ld_xn2).planes(p2).s16(c.bf16));
     if (!ln_done) run_gemm(c, blk.proj, GemmIO(att, M, ldp).to(y, C).add(residual, C).planes(p2, 0).f32(c.bf16, c.bf16));
     c.arena->release(mk);
     return ln_done;
@@ -121,6 +125,23 @@ void swin_forward_multi(Ctx& c, const SwinW& w, const SwinIn* ins, int nin, int 
         run_layernorm(c, w.patch_norm, t, total(0), E, LnOut(x, E));
         c.arena->release(mk);
     }
+    // P layout (kernels/split_planes.h) of a stage's GEMM inputs in the split modes: 2 planes = the fp32 row size, 3 planes = 1.5x; 0 = plain matrices
+    auto stage_planes = [&](const SwinStageW& sg) {
+        if (sg.blocks.empty()) return 0;
+        const SwinBlockW& b0 = sg.blocks[0];
+        const int np = b0.qkv.planes;
+        // (3 planes = rows 1.5x as long: measured 2 % SLOWER per forward in f32_split3 with the warp-specialised kernel, and the
+        // LDS-DMA plane kernel, kernels/gemm_planes.hip, which needs P3 input, did not beat it at batch 1: 2 planes only by default)
+#ifdef BRN_DIAG_BUILD
+        const bool planes_on = switches().planes_kernel != 0;
+#else
+        constexpr bool planes_on = false;
+#endif
+        if (w.window == 12 && (np == 2 || (np == 3 && planes_on)) && b0.qkv.wp && b0.proj.wp && b0.fc1.wp && b0.fc2.wp && sg.C % 32 == 0 && b0.fc1.N % 32 == 0) return np;
+        return 0;
+    };
+    float* xn_handoff = nullptr;       // the next stage's first norm1 matrix, and whether the reduction's LayerNorm wrote it
+    bool handoff_done = false;
     for (int i = 0; i < 4; ++i) {
         const SwinStageW& st = w.stages[i];
         const int C = st.C, M = total(i);
@@ -128,28 +149,25 @@ void swin_forward_multi(Ctx& c, const SwinW& w, const SwinIn* ins, int nin, int 
         for (int k = 0; k < nin; ++k) { hh[k] = hs[k][i]; ww[k] = wsz[k][i]; }
         float* xnext = nullptr;
         if (st.has_down) xnext = c.arena->alloc((size_t)total(i + 1) * 2 * C);
-        const size_t mk = c.arena->mark();
-        // P layout (kernels/split_planes.h) of the blocks' GEMM inputs in the split modes: 2 planes = the fp32 row size, 3 planes = 1.5x
-        const int hidden = st.blocks.empty() ? 4 * C : st.blocks[0].fc1.N;
-        int stage_pl = 0;
-        if (!st.blocks.empty()) {
-            const SwinBlockW& b0 = st.blocks[0];
-            const int np = b0.qkv.planes;
-            // (3 planes = rows 1.5x as long: measured 2 % SLOWER per forward in f32_split3 with the warp-specialised kernel, and the
-            // LDS-DMA plane kernel, kernels/gemm_planes.hip, which needs P3 input, did not beat it at batch 1: 2 planes only by default)
-#ifdef BRN_DIAG_BUILD
-            const bool planes_on = switches().planes_kernel != 0;
-#else
-            constexpr bool planes_on = false;
-#endif
-            if (w.window == 12 && (np == 2 || (np == 3 && planes_on)) && b0.qkv.wp && b0.proj.wp && b0.fc1.wp && b0.fc2.wp && C % 32 == 0 && hidden % 32 == 0) stage_pl = np;
+        // the PatchMerging reduction may write the next stage's first norm1 itself (g_gemm_ln_route): that matrix outlives this stage's mark
+        float* xn_made = xn_handoff;
+        xn_handoff = nullptr;
+        int next_pl = 0;
+        if (st.has_down && i + 1 < 4 && g_gemm_ln_route && !c.bf16 && !w.stages[i + 1].blocks.empty() && w.stages[i + 1].C == 2 * C) {
+            next_pl = stage_planes(w.stages[i + 1]);
+            xn_handoff = c.act_alloc((size_t)total(i + 1) * (next_pl ? 2 * C * next_pl / 2 : 2 * C));
         }
+        const size_t mk = c.arena->mark();
+        const int hidden = st.blocks.empty() ? 4 * C : st.blocks[0].fc1.N;
+        const int stage_pl = stage_planes(st);
         const int ldx = stage_pl ? C * stage_pl / 2 : C, ldh = stage_pl ? hidden * stage_pl / 2 : hidden;
         c.h2_scale = (stage_pl == 2 && st.blocks[0].qkv.half) ? half2_act_scale() : 0.f;    // mode f32_half2: the P2 planes are fp16 planes of the scaled activations
         // compute mode BRN_BF16: x (the residual stream) stays fp32; every GEMM operand (xn, qkv, att, hid, pm) is bf16
         const int yb = c.bf16;
-        const bool xn_ready = i == 0 && xn0 && !stage_pl && ldx == C;     // block 0's norm1 came out of the PatchEmbed kernel
-        float* xn = xn_ready ? xn0 : c.act_alloc((size_t)M * ldx);
+        // the next norm1 is already in xn: block 0's came out of the PatchEmbed kernel or of the reduction's LayerNorm, block j + 1's out of fc2's
+        bool xn_ready = (i == 0 && xn0 && !stage_pl && ldx == C) || (xn_made && handoff_done);
+        float* xn = (i == 0 && xn_ready) ? xn0 : xn_made ? xn_made : c.act_alloc((size_t)M * ldx);
+        handoff_done = false;
         float* hid = c.act_alloc((size_t)M * ldh);
         for (size_t j = 0; j < st.blocks.size(); ++j) {
             const SwinBlockW& bk = st.blocks[j];
@@ -158,11 +176,15 @@ void swin_forward_multi(Ctx& c, const SwinW& w, const SwinIn* ins, int nin, int 
             // would split out while staging), so the GEMMs' staging waves only copy
             const int p2 = stage_pl;
             const LnOut xn_out = LnOut(xn, ldx).planes(p2).s16(yb);
-            if (!(xn_ready && j == 0)) run_layernorm(c, bk.norm1, x, M, C, xn_out);   // swin.rs:355
+            if (!xn_ready) run_layernorm(c, bk.norm1, x, M, C, xn_out);   // swin.rs:355
+            xn_ready = false;
             const bool ln2_done = swin_attention_multi(c, bk, xn, B, nin, hh, ww, C, shift, x, x, p2, w.window, &bk.norm2, xn, ldx);   // x = shortcut + attn (swin.rs:406)
             if (!ln2_done) run_layernorm(c, bk.norm2, x, M, C, xn_out);               // swin.rs:407
             run_gemm(c, bk.fc1, GemmIO(xn, M, ldx).to(hid, ldh).planes(p2, p2));      // fc1 + gelu_erf (swin.rs:104-105)
-            run_gemm(c, bk.fc2, GemmIO(hid, M, ldh).to(x, C).add(x, C).planes(p2, 0).f32(yb, yb));     // x + fc2(...) (swin.rs:106,407)
+            const GemmIO fc2_io = GemmIO(hid, M, ldh).to(x, C).add(x, C).planes(p2, 0).f32(yb, yb);     // x + fc2(...) (swin.rs:106,407)
+            // ... with the next block's norm1 summing fc2's split-K slices where the route takes the pair (the last fc2 feeds the output norms)
+            if (j + 1 < st.blocks.size() && g_gemm_ln_route) xn_ready = g_gemm_ln_route(c, bk.fc2, fc2_io, st.blocks[j + 1].norm1, xn_out);
+            if (!xn_ready) run_gemm(c, bk.fc2, fc2_io);
         }
         // stage output = norm_i(x_out), pre-downsample (swin.rs:591,784-789); written into its consumer's window
         size_t off = 0, off2 = 0;
@@ -190,7 +212,15 @@ void swin_forward_multi(Ctx& c, const SwinW& w, const SwinIn* ins, int nin, int 
             }
             off += rows(k, i);
         }
-        if (st.has_down) run_gemm(c, st.reduction, GemmIO(pm, total(i + 1), ldpm).to(xnext, 2 * C).planes(pm_pl, 0).f32(yb, 0));
+        if (st.has_down) {
+            const GemmIO red_io = GemmIO(pm, total(i + 1), ldpm).to(xnext, 2 * C).planes(pm_pl, 0).f32(yb, 0);
+            if (xn_handoff) {
+                const SwinBlockW& nb = w.stages[i + 1].blocks[0];
+                c.h2_scale = (next_pl == 2 && nb.qkv.half) ? half2_act_scale() : 0.f;
+                handoff_done = g_gemm_ln_route(c, st.reduction, red_io, nb.norm1, LnOut(xn_handoff, next_pl ? 2 * C * next_pl / 2 : 2 * C).planes(next_pl));
+            }
+            if (!handoff_done) run_gemm(c, st.reduction, red_io);
+        }
         c.h2_scale = 0.f;
         c.arena->release(mk);
         x = xnext;

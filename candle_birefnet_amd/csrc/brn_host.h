@@ -112,6 +112,7 @@ static inline int roundup(int x, int m) { return (x + m - 1) / m * m; }
     X(planes_kernel,    "BRN_PLANES_KERNEL",     0,  "1 = split modes with P-layout A on the LDS-DMA plane kernel (diag build only)")           \
     X(conv_chunk_major, "BRN_CONV_CHUNK_MAJOR",  1,  "0 = tap-major K order of the 16-bit implicit-GEMM conv weights (read when weights are packed)") \
     X(offmod_pad8,      "BRN_OFFMOD_PAD8",       1,  "0 = the offset / modulator conv's N padded to 4 instead of 8")                         \
+    X(gemm_ln,          "BRN_GEMM_LN",           1,  "split modes, GEMM -> LayerNorm with the split-K slices summed by the LayerNorm: 0 = never; 1 = where plan_gemm_ln cuts; 2 = every eligible pair, two slices") \
     X(deform_col_mb,    "BRN_DEFORM_COL_MB",     256, "MiB the column matrix of brn_deform_conv2d_offsets_forward's column route may take (never below 64 rows)")
 struct Switches {
 #define BRN_X(field, name, dflt, doc) int field = dflt;

@@ -56,8 +56,12 @@ struct GemmParams {
     int abl;   // diagnostics only (brn_gemm_microbench): 1 = no global loads in the K loop, 2 = no LDS staging, 4 = no fragment reads / MFMA
 };
 
-struct GemmPlan { int cfg; int splitk; size_t ws_floats; };   // cfg: 0 = 128x128, 1 = 128x64, 2 = 64x64 block tile
+// cfg: 0 = 128x128, 1 = 128x64, 2 = 64x64 block tile.  raw = 1 (splitk > 1, fp32 C, no c_planes / c_bf16): launch_gemm leaves the raw slices
+// part[s][M][N] in ws and launches no splitk_reduce_kernel — the consumer sums them (LayerNormParams::part)
+struct GemmPlan { int cfg; int splitk; size_t ws_floats; int raw = 0; };
 GemmPlan plan_gemm(int M, int N, int K, int planes = 0);   // planes: bf16 planes of the split modes (0 = fp32 kernels)
+// the plan of a split-mode dense GEMM whose slices a LayerNorm sums (raw = 1), or splitk = 1: the pair does not beat GEMM + LayerNorm here
+GemmPlan plan_gemm_ln(int M, int N, int K, int planes);
 // ws: plan.ws_floats floats of scratch when plan.splitk > 1.  Returns the hipError_t of the launch(es).
 hipError_t launch_gemm(const GemmParams& p, const GemmPlan& plan, float* ws, hipStream_t s);
 // the split-bf16 path of launch_gemm (kernels/gemm_split.hip; p as launch_gemm validated it): dispatch over p.planes and the plan's tile.
@@ -134,6 +138,13 @@ struct LayerNormParams {
     int y_planes;         // 2: write y in the P2 layout (kernels/split_planes.h) for a split-bf16 GEMM; 0: fp32
     float y_h2;           // > 0 (with y_planes == 2): the planes are the fp16 planes of y_h2 * y (mode f32_half2)
     int y_bf16;           // 1: y is a bf16 matrix (compute mode BRN_BF16; x stays fp32: the residual stream)
+    // row source "sum of slices" (part != null; mode 0, x unused): the GEMM in front left its raw split-K slices part[s][rows][C]
+    // (GemmPlan::raw) and the row is v = 0; v += part[0] .. part[slices - 1]; v += bias; v += R[row][r_coff ..] — splitk_reduce_kernel's
+    // operand order — stored to x_out[row][xo_coff ..] (may alias R) and normalised from registers.  bias and R may each be null
+    const float* part; int slices;
+    const float* bias;
+    const float* R; int ldr, r_coff;
+    float* x_out; int ldxo, xo_coff;
 };
 hipError_t launch_layernorm(const LayerNormParams& p, hipStream_t s);
 

@@ -2,6 +2,7 @@
 // weights per call, in the arithmetic brn_set_op_compute selected on the calling thread.  Weights are always host pointers; x / y /
 // residual follow `loc`.
 #include "brn_api_util.h"
+#include "brn_graph.h"
 #include "kernels/deform_sample_geometry.h"
 #include <cmath>
 #include <cstring>
@@ -130,8 +131,13 @@ brn_status brn_linear_residual_layer_norm_forward(const float* x, int M, int K, 
             // the residual stream is updated in place inside the model: here x_out starts as a copy of the residual
             if (!c.dry) BRN_HIP(hipMemcpyAsync(dxo, dr, (size_t)M * N * sizeof(float), hipMemcpyDeviceToDevice, c.stream));
             if (!linear_residual_ln(c, g, a, M, K, dxo, ln, yb, N, true)) {
-                run_gemm(c, g, GemmIO(a, M, K).to(dxo, N).add(dxo, N).f32(bf ? 1 : 0, bf ? 1 : 0));
-                run_layernorm(c, ln, dxo, M, N, LnOut(yb, N).s16(bf ? 1 : 0));
+                // split modes: the GEMM's raw split-K slices summed by the LayerNorm, where the planner cuts (brn_gemm_ln.cpp)
+                const GemmIO io = GemmIO(a, M, K).to(dxo, N).add(dxo, N).f32(bf ? 1 : 0, bf ? 1 : 0);
+                const LnOut yo = LnOut(yb, N).s16(bf ? 1 : 0);
+                if (!(g_gemm_ln_route && g_gemm_ln_route(c, g, io, ln, yo))) {
+                    run_gemm(c, g, io);
+                    run_layernorm(c, ln, dxo, M, N, yo);
+                }
             }
             if (bf && !c.dry) BRN_HIP(launch_bf16_to_f32(yb, (size_t)M * N, dyo, c.stream, wb.f16));
         }, op_s16(wb));

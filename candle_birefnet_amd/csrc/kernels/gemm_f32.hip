@@ -289,6 +289,23 @@ GemmPlan plan_gemm(int M, int N, int K, int planes) {
     return pl;
 }
 
+// The plan of a two-plane split-mode dense GEMM whose consumer is a LayerNorm that sums the slices itself (LayerNormParams::part): no reduce
+// pass, so a cut costs only the extra slice traffic (S x M x N floats written and read back, L2-resident at the model's sizes).  Where
+// plan_gemm already cuts, its slices are kept.  Beyond that, a launch of one round with one workgroup per CU (129 .. 256 tiles) is cut in
+// two, so that two workgroups share every CU like in the full-grid launches, with at least LN_SK_MIN_KT K tiles per slice.  Three planes keep
+// plan_gemm's launches: their 32-deep stage is one workgroup per CU whatever the grid, and without the reduce passes alone f32_split3 did not
+// separate from its own run-to-run spread.  Measurements: DESIGN.md 3.1b.
+constexpr int LN_SK_MIN_KT = 48;
+GemmPlan plan_gemm_ln(int M, int N, int K, int planes) {
+    GemmPlan pl = plan_gemm(M, N, K, planes);
+    const long t128 = (long)((M + 127) / 128) * ((N + 127) / 128);
+    const double waste = (double)t128 * 128.0 * 128.0 / ((double)M * N);
+    if (planes != 2 || N < 128 || (N & 3) || waste > 1.35) { pl.splitk = 1; pl.ws_floats = 0; return pl; }    // (not the two-plane warp-specialised kernel's shapes)
+    if (pl.splitk == 1 && t128 > 128 && t128 <= 256 && K / BK / 2 >= LN_SK_MIN_KT) { pl.splitk = 2; pl.ws_floats = (size_t)2 * M * N; }
+    pl.raw = pl.splitk > 1;
+    return pl;
+}
+
 // A deformable conv whose weights carry planes runs on the split kernels too (gemm_split.hip, DeformLoader): fp32 maps in and out, whole
 // K tiles inside a tap, and the batch of sampled maps within the loader's 32-bit byte offsets.  Everything else — mode f32, the 16-bit modes'
 // fallback shapes, the diag build's one-plane mode — keeps gemm_f32_kernel.
@@ -322,6 +339,7 @@ hipError_t launch_gemm(const GemmParams& p_in, const GemmPlan& pl, float* ws, hi
     if (deform_split) deform_cfg = deform_split_plan(p, p.splitk, p.splitk);
     if (p.h2 && !(p.planes == 2 && p.Wp && (p.mode == GEMM_DENSE || p.mode == GEMM_CONV_NHWC || deform_split))) p.h2 = 0;     // (the fp32-MFMA kernel reads W itself: nothing is scaled)
     if (p.h2 && !(p.a_scale > 0.f && p.out_scale > 0.f)) return hipErrorInvalidValue;
+    if (pl.raw && (p.splitk < 2 || p.c_planes || p.c_bf16)) return hipErrorInvalidValue;   // raw slices: fp32 partial sums of a real split only
     if (p.a_planes || p.c_planes) {         // P2 layouts: 2-plane split mode, dense, on the warp-specialised kernel only
         if (!(p.planes == 2 || p.planes == 3) || !p.Wp || p.mode != GEMM_DENSE || !gemm_split_is_ws(pl.cfg)) return hipErrorInvalidValue;
         if (p.a_planes && (p.a_planes != p.planes || p.lda % 16 || p.a_coff)) return hipErrorInvalidValue;
@@ -336,7 +354,7 @@ hipError_t launch_gemm(const GemmParams& p_in, const GemmPlan& pl, float* ws, hi
     else if (pl.cfg == 4) e = launch_cfg<256, 128, 4, 2>(p, s);
     else if (pl.cfg == 5) e = launch_cfg<128, 128, 4, 2>(p, s);
     else e = launch_cfg<64, 64, 2, 2>(p, s);
-    if (e != hipSuccess || p.splitk == 1) return e;
+    if (e != hipSuccess || p.splitk == 1 || pl.raw) return e;      // raw: the slices stay in ws for the LayerNorm that sums them
     long total = (long)p.M * p.N;
     long blocks = (total + 255) / 256;
     if (blocks > 4096) blocks = 4096;
