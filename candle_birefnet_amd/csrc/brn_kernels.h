@@ -185,7 +185,9 @@ hipError_t launch_attention_bias(const AttentionBiasParams& p, hipStream_t s);
 // q/k/v attention for long sequences, online softmax over K / V tiles (kernels/flash_attention.hip; brn_flash_attention_forward and, with
 // a bias, brn_flash_attention_bias_forward; with grouped K / V heads or a causal mask over a cache, brn_flash_attention_gqa_forward):
 // y[b,h] = softmax_rows(scale * (q[b,h] k[b,h / G]^T [+ bias[b % n_bias, h]]) [causal: key j <= query i + causal_off]) v[b,h / G],
-// G = heads / kv_heads, head_dim 32 / 64 / 128, 1 <= seq_q, seq_kv <= 65536
+// G = heads / kv_heads, head_dim 32 / 64 / 128, 1 <= seq_q, seq_kv <= 65536; over a packed batch of sequences with a window mask,
+// brn_flash_attention_varlen_forward (the fields after causal_off)
+struct FaVarlenRecord;      // brn_flash_varlen_plan.h (host-only header)
 struct FlashAttentionParams {
     const float* q; const float* k; const float* v;   // 16-byte aligned; head_dim contiguous
     float* y;             // q's shape and strides
@@ -202,6 +204,13 @@ struct FlashAttentionParams {
     // brn_flash_attention_gqa_forward; kv_heads == heads and causal_off == 0 = the kernels of the two entries above, untouched
     int kv_heads;         // K / V heads (k, v strides are theirs): query head h reads K / V head h / (heads / kv_heads); heads % kv_heads == 0
     int causal_off;       // causal: seq_kv - seq_q >= 0, key j takes part in query i's row exactly when j <= i + causal_off; 0 when not causal
+    // brn_flash_attention_varlen_forward; plan == null = the kernels of the three entries above, untouched.  With a plan: q, y
+    // [total_q, heads, head_dim] and k, v [total_kv, kv_heads, head_dim] (batch 1, the strides of BSHD), no bias, causal 0; seq_q, seq_kv
+    // and causal_off are each workgroup's own, from its record
+    const FaVarlenRecord* plan;   // n_records records on the device (brn_flash_varlen_plan.h), every field validated on the host
+    int n_records;                // the grid is n_records * kv_heads workgroups: workgroup w = (record w / kv_heads, K / V head w % kv_heads)
+    int window_left, window_right;   // key j takes part in query i's row exactly when i + off - window_left <= j <= i + off + window_right,
+                                     // off = len_kv - len_q of the row's sequence; -1 = unbounded on that side
 };
 hipError_t launch_flash_attention(const FlashAttentionParams& p, hipStream_t s);
 

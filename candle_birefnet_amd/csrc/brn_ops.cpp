@@ -2,6 +2,7 @@
 // weights per call, in the arithmetic brn_set_op_compute selected on the calling thread.  Weights are always host pointers; x / y /
 // residual follow `loc`.
 #include "brn_api_util.h"
+#include "brn_flash_varlen_plan.h"
 #include "brn_graph.h"
 #include "kernels/deform_sample_geometry.h"
 #include <cmath>
@@ -363,6 +364,57 @@ brn_status brn_flash_attention_gqa_forward(const float* q, const float* k, const
                                            int device, void* stream) {
     return guarded([&] {
         flash_attention_body("flash attention gqa", true, true, q, k, v, batch, seq_q, seq_kv, heads, kv_heads, head_dim, layout, causal, bias, n_bias, scale, y, loc, device, stream);
+    });
+}
+
+// The packed batch.  Everything the kernels read from the cu arrays reaches them through the record table of brn_flash_varlen_plan.h,
+// built here from values that passed flash_varlen_check.  The table travels through a Staging temporary: the stream is synchronised
+// before the call returns (also for device tensors), so the table and its host copy are free to go when it does.
+brn_status brn_flash_attention_varlen_forward(const float* q, const float* k, const float* v, const int* cu_seqlens_q, const int* cu_seqlens_kv,
+                                              int n_seqs, int heads, int kv_heads, int head_dim, int window_left, int window_right, float scale,
+                                              float* y, brn_mem loc, int device, void* stream) {
+    return guarded([&] {
+        const char* who = "flash attention varlen";
+        if (!q || !k || !v || !y) fail(BRN_ERR_INVALID_ARG, "%s: null q, k, v or y", who);
+        if (!cu_seqlens_q || !cu_seqlens_kv) fail(BRN_ERR_INVALID_ARG, "%s: null cu_seqlens_q or cu_seqlens_kv", who);
+        if (!(head_dim == 32 || head_dim == 64 || head_dim == 128))
+            fail(BRN_ERR_INVALID_ARG, "%s: head_dim %d unsupported (head_dim must be 32, 64 or 128)", who, head_dim);
+        if (heads < 1) fail(BRN_ERR_INVALID_ARG, "%s: heads %d unsupported (heads >= 1)", who, heads);
+        if (kv_heads < 1 || kv_heads > heads || heads % kv_heads)
+            fail(BRN_ERR_INVALID_ARG, "%s: kv_heads %d unsupported with heads %d (1 <= kv_heads <= heads, heads %% kv_heads == 0)", who, kv_heads, heads);
+        if (n_seqs < 1) fail(BRN_ERR_INVALID_ARG, "%s: n_seqs %d unsupported (n_seqs >= 1)", who, n_seqs);
+        if (window_left < -1 || window_right < -1)
+            fail(BRN_ERR_INVALID_ARG, "%s: window (%d, %d) unsupported (window_left >= -1, window_right >= -1; -1 = unbounded)", who, window_left, window_right);
+        if (!scale_arg_ok(scale)) fail(BRN_ERR_INVALID_ARG, "%s: scale must be finite and >= 0 (0 = head_dim^-0.5)", who);
+        // a side that reaches past the longest sequence allowed is that side at 65536 (INT_MAX as "unbounded" included): clamped here,
+        // before the plan and the kernels, whose int arithmetic on it then cannot wrap
+        window_left = fa_varlen_clamp_window(window_left); window_right = fa_varlen_clamp_window(window_right);
+        const std::string bad = flash_varlen_check(cu_seqlens_q, cu_seqlens_kv, n_seqs, heads, kv_heads, window_left, window_right);
+        if (!bad.empty()) fail(BRN_ERR_INVALID_ARG, "%s: %s", who, bad.c_str());
+        const size_t nq = (size_t)cu_seqlens_q[n_seqs] * heads * head_dim, nkv = (size_t)cu_seqlens_kv[n_seqs] * kv_heads * head_dim;
+        if (floats_overlap(q, nq, y, nq) || floats_overlap(k, nkv, y, nq) || floats_overlap(v, nkv, y, nq))
+            fail(BRN_ERR_INVALID_ARG, "%s: y must not overlap an input", who);
+        if (loc == BRN_MEM_DEVICE && !all_aligned16({q, k, v, y})) fail(BRN_ERR_INVALID_ARG, "%s: device q, k, v and y must be 16-byte aligned", who);
+        ensure_device(device);
+        const std::vector<FaVarlenRecord> recs = flash_varlen_plan(cu_seqlens_q, cu_seqlens_kv, n_seqs, heads, kv_heads, window_left, window_right);
+        Staging st(stream, loc);                 // after recs: its destructor synchronises the stream before recs goes
+        FlashAttentionParams p{};
+        p.q = st.in(q, nq); p.k = st.in(k, nkv); p.v = st.in(v, nkv);
+        p.y = st.out(y, nq);
+        static_assert(sizeof(FaVarlenRecord) == 8 * sizeof(float), "a record is 8 dwords");
+        float* dplan = st.dalloc(recs.size() * 8);
+        BRN_HIP(hipMemcpyAsync(dplan, recs.data(), recs.size() * sizeof(FaVarlenRecord), hipMemcpyHostToDevice, (hipStream_t)stream));
+        p.plan = reinterpret_cast<const FaVarlenRecord*>(dplan);
+        p.n_records = (int)recs.size();
+        p.batch = 1; p.heads = heads; p.kv_heads = kv_heads; p.head_dim = head_dim;
+        p.seq_q = p.seq_kv = 1;                  // each workgroup's own, from its record
+        const long d = head_dim;
+        p.q_ss = heads * d; p.q_sh = d; p.kv_ss = kv_heads * d; p.kv_sh = d;
+        p.window_left = window_left; p.window_right = window_right;
+        p.scale = scale_or_default(scale, head_dim);
+        p.s16 = attention_op_s16();
+        BRN_HIP(launch_flash_attention(p, (hipStream_t)stream));
+        st.finish();
     });
 }
 

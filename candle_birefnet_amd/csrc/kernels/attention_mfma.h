@@ -122,6 +122,13 @@ __device__ __forceinline__ void att_exclude4(f32x4& s, int k0, int limit) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) s[r] = (k0 + r < limit) ? s[r] : ATT_NEG;
 }
+// the two-sided sibling (a window): keys before `lo` and keys from `hi` on leave the softmax.  They become -inf, not ATT_NEG: a row may
+// meet wholly excluded tiles BEFORE its first real score, while m is still ATT_NEG, and exp2(-inf - ATT_NEG) is exactly 0 where
+// exp2(ATT_NEG - ATT_NEG) would be 1 (what a -inf bias entry does; -inf never raises the maximum either)
+__device__ __forceinline__ void att_exclude4_window(f32x4& s, int k0, int lo, int hi) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) s[r] = (k0 + r >= lo && k0 + r < hi) ? s[r] : -__builtin_inff();
+}
 __device__ __forceinline__ float att_max4(float mx, const f32x4 s) { return fmaxf(fmaxf(mx, fmaxf(s[0], s[1])), fmaxf(s[2], s[3])); }
 // numerators exp2(s - m) in place, added to sum in register order
 __device__ __forceinline__ void att_exp2_sum4(f32x4& s, float m, float& sum) {

@@ -38,7 +38,24 @@
 // walk, the LDS images and the arithmetic are those of GQA = false, whose instantiations serve the two older entries as before.  A row's
 // bits do not depend on which rows share its tile: a K / V tile wholly past a row's limit leaves alpha = exp2(m - m) = 1 and numerators
 // exp2(-3e38 - m) = 0, so the results are those of the plain kernels on K / V repeated G times.  DESIGN.md 3.2f.
+// FA_VARLEN (brn_flash_attention_varlen_forward): the third form of the packed-row kernels (FaForm; GQA = false / true above are FA_PLAIN /
+// FA_PACKED).  One workgroup = one (record, K / V head); the record (brn_flash_varlen_plan.h, built and validated on the host) names the
+// workgroup's sequence of a packed batch (q_start, len_q, kv_start, len_kv), its first packed row and the K / V tiles kt0 .. kt1 - 1 it
+// walks.  seq_q, seq_kv and causal_off become the record's len_q, len_kv and off = len_kv - len_q (fa_params), the operand bases gain
+// q_start * q_ss and kv_start * kv_ss in 64-bit arithmetic, and every clamp therefore clamps into the row's own sequence.  A row has two
+// limits, lo = max(0, query + off - window_left) and hi = min(len_kv, query + off + window_right + 1) (-1: 0 / len_kv): keys outside
+// lo .. hi - 1 are excluded (att_exclude4_window), and the wave's mask flag is two-sided (fa_tile_masks_window).  No bias.
+// A lower limit breaks "key 0 is visible to every row".  What holds instead: every row sees its diagonal key query + off (the entry
+// requires len_kv >= len_q with a window), and a row's visible keys are contiguous.  A row whose lo lies past the tile's kt0 first meets
+// wholly excluded K / V tiles, while m is still ATT_NEG.  With ATT_NEG as the excluded score their numerators would be
+// exp2(ATT_NEG - ATT_NEG) = 1 and l and O would collect garbage that only alpha = exp2(ATT_NEG - s) = 0 at the row's first real score s
+// wipes, and only while that garbage is finite.  So this form excludes with -inf (att_exclude4_window), as a -inf bias entry does: the
+// tile maximum is -inf, m stays ATT_NEG, alpha = exp2(0) = 1, the numerators are exp2(-inf - ATT_NEG) = 0 exactly, and l and O stay
+// 0 + 0 . V until the row's own first tile; nothing needs wiping (alpha = 0 there multiplies zeros).  Tiles past a row's hi leave
+// alpha = 1 and numerators exp2(-inf - m) = 0, as above.  So a row's bits depend on its sequence, query head and window alone, and equal
+// those of the bias kernels on that sequence with the window written into the bias as -inf, also for large V.  DESIGN.md 3.2g.
 #include "../brn_kernels.h"
+#include "../brn_flash_varlen_plan.h"
 #include "attention_mfma.h"
 #include <type_traits>
 
@@ -48,14 +65,20 @@ namespace {
 constexpr int FA_BQ = 64;            // queries per workgroup: 4 waves x 16
 constexpr int FA_T = 64;             // keys per K / V tile
 constexpr int FA_THREADS = 256;
+static_assert(FA_BQ == FA_VARLEN_ROWS && FA_T == FA_VARLEN_ROWS, "the records of brn_flash_varlen_plan.h are tiles of FA_BQ rows and FA_T keys");
 constexpr int FA_VT_LD = 72;         // 16-bit kernel: elements per LDS row of V^T (36 dwords: conflict-free 8-byte reads, 2-way 4-byte writes)
+
+// the three forms of the kernels: a workgroup per (batch entry, head, 64 queries); per (batch entry, K / V head, 64 packed rows); per
+// (record of a packed batch, K / V head), with a window
+enum FaForm { FA_PLAIN = 0, FA_PACKED = 1, FA_VARLEN = 2 };
 
 // which (batch entry, head, query tile) this workgroup owns, where its operands start and how many K / V tiles it walks
 struct FaBlock {
     const float* q; const float* k; const float* v; float* y;
     const float* bias;    // BIAS: the [seq_q, seq_kv] slab of this (bias pattern = batch entry % n_bias, head)
     int q0;               // first query of the tile (GQA: first packed row)
-    int nkt;              // K / V tiles to walk: all of them, or (causal) those that reach the tile's last query
+    int nkt;              // K / V tiles to walk: all of them, or (causal) those that reach the tile's last query; FA_VARLEN: one past the last (kt1)
+    int kt0;              // FA_VARLEN: the first K / V tile to walk (the other forms start at 0)
     int G, h0, rem;       // GQA: query heads per K / V head, the group's first query head, real rows after q0 (the tile's last real row is q0 + min(63, rem))
 };
 // GQA: the workgroup is (batch entry, K / V head, tile of 64 packed rows); q, y and bias point at the batch entry (pattern), the head is a
@@ -84,14 +107,33 @@ __device__ __forceinline__ FaBlock fa_block_gqa(const FlashAttentionParams& p) {
     r.h0 = kvh * r.G;
     r.q0 = qt * FA_BQ;
     r.rem = rows - 1 - r.q0;
+    r.kt0 = 0;
     r.nkt = (p.seq_kv + FA_T - 1) / FA_T;
     // the tile's last real row holds its last query, whose last visible key is query + causal_off <= seq_kv - 1
     if (p.causal) r.nkt = min(r.nkt, ((r.q0 + min(FA_BQ - 1, r.rem)) / r.G + p.causal_off) / FA_T + 1);
     return r;
 }
-template <bool BIAS, bool GQA>
+// FA_VARLEN: the workgroup is (record, K / V head); the record's sequence is the "batch entry", its own rows of q / y / k / v the only
+// ones any address of the workgroup can reach (64-bit offsets: a pack may hold more than 2^31 elements)
+__device__ __forceinline__ FaBlock fa_block_varlen(const FlashAttentionParams& p, const FaVarlenRecord& rec) {
+    FaBlock r;
+    r.G = p.heads / p.kv_heads;
+    const int kvh = (int)(blockIdx.x % (unsigned)p.kv_heads);
+    r.q = p.q + (long)rec.q_start * p.q_ss;
+    r.y = p.y + (long)rec.q_start * p.q_ss;
+    r.k = p.k + (long)rec.kv_start * p.kv_ss + kvh * p.kv_sh;
+    r.v = p.v + (long)rec.kv_start * p.kv_ss + kvh * p.kv_sh;
+    r.bias = nullptr;
+    r.h0 = kvh * r.G;
+    r.q0 = rec.q0;
+    r.rem = r.G * rec.len_q - 1 - rec.q0;
+    r.kt0 = rec.kt0;
+    r.nkt = rec.kt1;
+    return r;
+}
+template <bool BIAS, FaForm FORM>
 __device__ __forceinline__ FaBlock fa_block(const FlashAttentionParams& p) {
-    if constexpr (GQA) return fa_block_gqa<BIAS>(p);
+    if constexpr (FORM == FA_PACKED) return fa_block_gqa<BIAS>(p);
     const int nqt = (p.seq_q + FA_BQ - 1) / FA_BQ;
     // not causal: the query tiles of a (batch entry, head) are neighbours in the grid (they walk the same K and V).  Causal: tile qt walks
     // qt + 1 K / V tiles, so the grid is ordered by query tile, last (longest) first: the launch ends on the short workgroups
@@ -114,6 +156,7 @@ __device__ __forceinline__ FaBlock fa_block(const FlashAttentionParams& p) {
     r.nkt = (p.seq_kv + FA_T - 1) / FA_T;
     if (p.causal) r.nkt = min(r.nkt, min(r.q0 + FA_BQ - 1, p.seq_q - 1) / FA_T + 1);
     r.G = 1; r.h0 = h; r.rem = p.seq_q - 1 - r.q0;         // (not read)
+    r.kt0 = 0;
     return r;
 }
 
@@ -128,11 +171,29 @@ struct FaLane {
     long brow;            //       the row's offset in it: query * seq_kv
     int limit;            // the row's first excluded key: seq_kv, or (causal) query + causal_off + 1
     int wave_row0;        // the first query of the wave's 16 rows (clamped; GQA: + causal_off): the wave's smallest limit - 1 under the causal mask (fa_tile_masks)
+                          // FA_VARLEN: the wave's smallest limit itself (its first row's; fa_tile_masks_window)
+    int lo, wave_lo;      // FA_VARLEN: the row's first visible key, and the wave's largest (its last row's)
 };
-template <bool GQA>
+template <FaForm FORM>
 __device__ __forceinline__ FaLane fa_lane(const FlashAttentionParams& p, const FaBlock& blk, int wave, int li) {
     FaLane r;
-    if constexpr (GQA) {
+    r.lo = 0; r.wave_lo = 0;
+    if constexpr (FORM == FA_VARLEN) {
+        // p.seq_q / p.seq_kv / p.causal_off: the record's len_q / len_kv / len_kv - len_q (fa_params).  Queries do not fall along
+        // the packed rows, so neither do lo and hi: the wave's smallest hi is its first row's, its largest lo its last row's
+        const int lr = wave * 16 + li;
+        const int row = blk.q0 + min(lr, blk.rem);
+        const int query = row / blk.G, head = blk.h0 + (row - query * blk.G);
+        r.q = blk.q + (head * p.q_sh + query * p.q_ss);
+        r.yrow = lr <= blk.rem ? row : -1;
+        r.bias = nullptr; r.brow = 0;
+        const int wl = p.window_left, wr = p.window_right;
+        r.lo = wl < 0 ? 0 : max(0, query + p.causal_off - wl);
+        r.limit = wr < 0 ? p.seq_kv : min(p.seq_kv, query + p.causal_off + wr + 1);
+        const int qa = (blk.q0 + min(wave * 16, blk.rem)) / blk.G, qb = (blk.q0 + min(wave * 16 + 15, blk.rem)) / blk.G;
+        r.wave_row0 = wr < 0 ? p.seq_kv : min(p.seq_kv, qa + p.causal_off + wr + 1);
+        r.wave_lo = wl < 0 ? 0 : max(0, qb + p.causal_off - wl);
+    } else if constexpr (FORM == FA_PACKED) {
         const int lr = wave * 16 + li;
         const int row = blk.q0 + min(lr, blk.rem);
         const int query = row / blk.G, head = blk.h0 + (row - query * blk.G);
@@ -155,9 +216,9 @@ __device__ __forceinline__ FaLane fa_lane(const FlashAttentionParams& p, const F
     return r;
 }
 // the row of y, null for a pad row
-template <bool GQA>
+template <FaForm FORM>
 __device__ __forceinline__ float* fa_lane_y(const FlashAttentionParams& p, const FaBlock& blk, const FaLane& ln) {
-    if constexpr (GQA) {
+    if constexpr (FORM != FA_PLAIN) {
         // (query and head are taken from the row a second time: one register across the walk, as the plain kernels have)
         const int row = max(ln.yrow, 0), query = row / blk.G, head = blk.h0 + (row - query * blk.G);
         return ln.yrow >= 0 ? blk.y + (head * p.q_sh + query * p.q_ss) : nullptr;
@@ -202,12 +263,16 @@ __device__ __forceinline__ void fa_load_bias(f32x4 (&bv)[FA_T / 16], const float
 // One tile of the online softmax.  st: the lane's raw scores of keys key0 + 16 s + 4 g + r (s = sub-tile, r = register) of its query;
 // limit: the lane's first excluded key (seq_kv, or query + 1 under the causal mask); mask: whether this tile can hold an excluded key
 // for some lane of the wave (wave-uniform).  Leaves the numerators in st, updates m and l, returns alpha.
-__device__ __forceinline__ float fa_softmax_tile(f32x4 (&st)[FA_T / 16], float sc2, bool mask, int key0, int g, int limit, float& m, float& l) {
+// WINDOW (FA_VARLEN): the keys before `lo` are excluded too (att_exclude4_window).
+template <bool WINDOW = false>
+__device__ __forceinline__ float fa_softmax_tile(f32x4 (&st)[FA_T / 16], float sc2, bool mask, int key0, int g, int limit, float& m, float& l, int lo = 0) {
     float mx = ATT_NEG;
 #pragma unroll
     for (int s = 0; s < FA_T / 16; ++s) {
         att_scale4(st[s], sc2);
-        if (mask) att_exclude4(st[s], key0 + s * 16 + g * 4, limit);
+        if constexpr (WINDOW) {
+            if (mask) att_exclude4_window(st[s], key0 + s * 16 + g * 4, lo, limit);
+        } else if (mask) att_exclude4(st[s], key0 + s * 16 + g * 4, limit);
         mx = att_max4(mx, st[s]);
     }
     const float mn = fmaxf(m, att_group_max(mx));
@@ -224,6 +289,25 @@ __device__ __forceinline__ bool fa_tile_masks(const FlashAttentionParams& p, int
     const int lim = p.causal ? min(p.seq_kv, wave_row0 + 1) : p.seq_kv;
     return key0 + FA_T > lim;
 }
+// FA_VARLEN, two-sided: the tile holds a key from the wave's smallest hi on, or one before the wave's largest lo
+__device__ __forceinline__ bool fa_tile_masks_window(int key0, int wave_hi, int wave_lo) { return key0 + FA_T > wave_hi || key0 < wave_lo; }
+// FA_VARLEN: the workgroup's record, and the arguments with the record's sequence in place of the call's: seq_q, seq_kv, causal_off
+// (= off of the window; it may be negative where there is no window, and is then not read)
+template <FaForm FORM>
+__device__ __forceinline__ FlashAttentionParams fa_params(const FlashAttentionParams& pa, FaVarlenRecord& rec) {
+    if constexpr (FORM != FA_VARLEN) return pa;
+    else {
+        rec = pa.plan[blockIdx.x / (unsigned)pa.kv_heads];           // wave-uniform
+        FlashAttentionParams p = pa;
+        p.seq_q = rec.len_q; p.seq_kv = rec.len_kv; p.causal_off = rec.len_kv - rec.len_q;
+        return p;
+    }
+}
+template <bool BIAS, FaForm FORM>
+__device__ __forceinline__ FaBlock fa_block_of(const FlashAttentionParams& p, const FaVarlenRecord& rec) {
+    if constexpr (FORM == FA_VARLEN) return fa_block_varlen(p, rec);
+    else return fa_block<BIAS, FORM>(p);
+}
 // the 4 partial sums of a query are added, and the query's row of y (null: a pad query) is stored
 // BIAS: a row whose every visible key has a -inf bias never saw a real score (m is still ATT_NEG) and comes back NaN, also where excluded
 // keys of its tiles left exp2(ATT_NEG - ATT_NEG) = 1 in l
@@ -239,15 +323,17 @@ __device__ __forceinline__ void fa_finish(float* yrow, int g, const f32x4 (&o)[N
 
 // ---- fp32: v_mfma_f32_16x16x4_f32, an exact fmaf chain per score and per output ----
 // LDS: Ks, Vs [64][D + 4] floats (D 128: 66 KB).  Staging item = (key, 4-wide d chunk), D / 16 items of K and of V per thread.
-template <int D, bool BIAS, bool GQA>
-__global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const FlashAttentionParams p) {
+template <int D, bool BIAS, FaForm FORM>
+__global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const FlashAttentionParams pa) {
     constexpr int LD = D + 4, NI = D / 16, ND = D / 16, NC = D / 32;
     __shared__ __attribute__((aligned(16))) float Ks[FA_T * LD];
     __shared__ __attribute__((aligned(16))) float Vs[FA_T * LD];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, g = lane >> 4;
-    const FaBlock blk = fa_block<BIAS, GQA>(p);
-    const FaLane ln = fa_lane<GQA>(p, blk, wave, li);
+    FaVarlenRecord rec;
+    const FlashAttentionParams p = fa_params<FORM>(pa, rec);
+    const FaBlock blk = fa_block_of<BIAS, FORM>(p, rec);
+    const FaLane ln = fa_lane<FORM>(p, blk, wave, li);
     // Q fragment: chunk c of 32 d's -> d = 32 c + 8 g .. + 7 of the query's row (the MFMA k order is a permutation of d; K uses the same)
     f32x4 qv[2 * NC];
     {
@@ -277,8 +363,9 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
     float m = ATT_NEG, l = 0.f;
     const float sc2 = p.scale * ATT_LOG2E;
 
-    load_tile(0);
-    for (int kt = 0; kt < blk.nkt; ++kt) {
+    const int kt_first = FORM == FA_VARLEN ? blk.kt0 : 0;
+    load_tile(kt_first * FA_T);
+    for (int kt = kt_first; kt < blk.nkt; ++kt) {
         __syncthreads();                                   // every wave is done reading the previous tile
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
@@ -302,7 +389,9 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
             for (int c = 0; c < NC; ++c) acc = att_score_f32(Ks + (s * 16 + li) * LD + c * 32 + g * 8, qv[2 * c], qv[2 * c + 1], acc);
             st[s] = acc;
         }
-        const float alpha = fa_softmax_tile(st, sc2, fa_tile_masks(p, kt * FA_T, ln.wave_row0), kt * FA_T, g, ln.limit, m, l);
+        float alpha;
+        if constexpr (FORM == FA_VARLEN) alpha = fa_softmax_tile<true>(st, sc2, fa_tile_masks_window(kt * FA_T, ln.wave_row0, ln.wave_lo), kt * FA_T, g, ln.limit, m, l, ln.lo);
+        else alpha = fa_softmax_tile(st, sc2, fa_tile_masks(p, kt * FA_T, ln.wave_row0), kt * FA_T, g, ln.limit, m, l);
 #pragma unroll
         for (int dt = 0; dt < ND; ++dt) o[dt] *= alpha;
         // O^T += V^T . P^T
@@ -316,7 +405,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
             }
         }
     }
-    fa_finish<ND, BIAS>(fa_lane_y<GQA>(p, blk, ln), g, o, l, m);
+    fa_finish<ND, BIAS>(fa_lane_y<FORM>(p, blk, ln), g, o, l, m);
 }
 
 // ---- 16-bit: q, k, v rounded to E (round to nearest even) as they are loaded; v_mfma_f32_16x16x32_{bf16,f16} with fp32 accumulation.
@@ -324,8 +413,8 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
 // LDS: Kp[key][D] and Vt[d][72 keys] (kernels/attention_mfma.h): D 128 = 16 + 18 KB.
 // Staging item = (key pair, 4-wide d chunk): thread -> (d chunk low 2 bits, key pair, d chunk high bits), so a quad of lanes reads 64
 // contiguous bytes of a row and the 4-byte transposed V writes of a wave fall 2-way on the 32 banks. ----
-template <typename E, int D, bool BIAS, bool GQA>
-__global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const FlashAttentionParams p) {
+template <typename E, int D, bool BIAS, FaForm FORM>
+__global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const FlashAttentionParams pa) {
     constexpr bool F16 = std::is_same<E, _Float16>::value;
     constexpr int NP = D / 32, ND = D / 16;       // staging passes = MFMA k steps of a score tile; d tiles of O^T
     typedef vec8<E> ex8;
@@ -334,8 +423,10 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
     __shared__ __attribute__((aligned(16))) E Vt[D * FA_VT_LD];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, g = lane >> 4;
-    const FaBlock blk = fa_block<BIAS, GQA>(p);
-    const FaLane ln = fa_lane<GQA>(p, blk, wave, li);
+    FaVarlenRecord rec;
+    const FlashAttentionParams p = fa_params<FORM>(pa, rec);
+    const FaBlock blk = fa_block_of<BIAS, FORM>(p, rec);
+    const FaLane ln = fa_lane<FORM>(p, blk, wave, li);
     // Q fragment of MFMA k step c: d = 32 c + 8 g .. + 7 of the query's row
     ex8 qf[NP];
     {
@@ -368,8 +459,9 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
     float m = ATT_NEG, l = 0.f;
     const float sc2 = p.scale * ATT_LOG2E;
 
-    load_tile(0);
-    for (int kt = 0; kt < blk.nkt; ++kt) {
+    const int kt_first = FORM == FA_VARLEN ? blk.kt0 : 0;
+    load_tile(kt_first * FA_T);
+    for (int kt = kt_first; kt < blk.nkt; ++kt) {
         __syncthreads();                                   // every wave is done reading the previous tile
 #pragma unroll
         for (int ps = 0; ps < NP; ++ps) {
@@ -402,7 +494,9 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
             for (int c = 0; c < NP; ++c) acc = att_mfma<F16>(att_k_frag<D>(Kp + key * D, key, c * 4 + g), qf[c], acc);
             st[s] = acc;
         }
-        const float alpha = fa_softmax_tile(st, sc2, fa_tile_masks(p, kt * FA_T, ln.wave_row0), kt * FA_T, g, ln.limit, m, l);
+        float alpha;
+        if constexpr (FORM == FA_VARLEN) alpha = fa_softmax_tile<true>(st, sc2, fa_tile_masks_window(kt * FA_T, ln.wave_row0, ln.wave_lo), kt * FA_T, g, ln.limit, m, l, ln.lo);
+        else alpha = fa_softmax_tile(st, sc2, fa_tile_masks(p, kt * FA_T, ln.wave_row0), kt * FA_T, g, ln.limit, m, l);
 #pragma unroll
         for (int dt = 0; dt < ND; ++dt) o[dt] *= alpha;
         // O^T += V^T . P^T: k step t = key sub-tiles (2t, 2t+1)
@@ -413,30 +507,44 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
             for (int dt = 0; dt < ND; ++dt) o[dt] = att_mfma<F16>(att_vt_frag(Vt + (dt * 16 + li) * FA_VT_LD + g * 4, t), pf, o[dt]);
         }
     }
-    fa_finish<ND, BIAS>(fa_lane_y<GQA>(p, blk, ln), g, o, l, m);
+    fa_finish<ND, BIAS>(fa_lane_y<FORM>(p, blk, ln), g, o, l, m);
 }
 
-template <int D, bool BIAS, bool GQA>
+template <int D, bool BIAS, FaForm FORM>
 void fa_launch(const FlashAttentionParams& p, dim3 grid, hipStream_t s) {
     const dim3 block(FA_THREADS);
-    if (p.s16 == 0) hipLaunchKernelGGL((flash_attention_f32_kernel<D, BIAS, GQA>), grid, block, 0, s, p);
-    else if (p.s16 == 1) hipLaunchKernelGGL((flash_attention_s16_kernel<__bf16, D, BIAS, GQA>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((flash_attention_s16_kernel<_Float16, D, BIAS, GQA>), grid, block, 0, s, p);
+    if (p.s16 == 0) hipLaunchKernelGGL((flash_attention_f32_kernel<D, BIAS, FORM>), grid, block, 0, s, p);
+    else if (p.s16 == 1) hipLaunchKernelGGL((flash_attention_s16_kernel<__bf16, D, BIAS, FORM>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((flash_attention_s16_kernel<_Float16, D, BIAS, FORM>), grid, block, 0, s, p);
 }
 template <int D>
-void fa_launch(const FlashAttentionParams& p, bool gqa, dim3 grid, hipStream_t s) {
-    if (gqa) {
-        if (p.bias) fa_launch<D, true, true>(p, grid, s);
-        else fa_launch<D, false, true>(p, grid, s);
+void fa_launch(const FlashAttentionParams& p, FaForm form, dim3 grid, hipStream_t s) {
+    if (form == FA_VARLEN) fa_launch<D, false, FA_VARLEN>(p, grid, s);
+    else if (form == FA_PACKED) {
+        if (p.bias) fa_launch<D, true, FA_PACKED>(p, grid, s);
+        else fa_launch<D, false, FA_PACKED>(p, grid, s);
     } else {
-        if (p.bias) fa_launch<D, true, false>(p, grid, s);
-        else fa_launch<D, false, false>(p, grid, s);
+        if (p.bias) fa_launch<D, true, FA_PLAIN>(p, grid, s);
+        else fa_launch<D, false, FA_PLAIN>(p, grid, s);
     }
 }
 
 }  // namespace
 
 hipError_t launch_flash_attention(const FlashAttentionParams& p, hipStream_t s) {
+    if (p.plan) {
+        // the packed batch: the record table was built and every value in it checked by the entry (brn_flash_varlen_plan.h); what is
+        // checked here is what the kernels assume of the other arguments
+        if (!(p.head_dim == 32 || p.head_dim == 64 || p.head_dim == 128) || p.heads < 1 || p.kv_heads < 1 || p.kv_heads > p.heads ||
+            p.heads % p.kv_heads || p.batch != 1 || p.causal || p.causal_off || p.bias || p.n_bias || p.s16 < 0 || p.s16 > 2 || !(p.scale > 0.f) ||
+            p.n_records < 1 || p.window_left < -1 || p.window_right < -1 || p.window_left > FA_VARLEN_MAX_LEN || p.window_right > FA_VARLEN_MAX_LEN || (long)p.n_records * p.kv_heads > 0x7fffffffL)
+            return hipErrorInvalidValue;
+        const dim3 grid((unsigned)(p.n_records * p.kv_heads));
+        if (p.head_dim == 32) fa_launch<32>(p, FA_VARLEN, grid, s);
+        else if (p.head_dim == 64) fa_launch<64>(p, FA_VARLEN, grid, s);
+        else fa_launch<128>(p, FA_VARLEN, grid, s);
+        return hipGetLastError();
+    }
     if (!(p.head_dim == 32 || p.head_dim == 64 || p.head_dim == 128) || p.seq_q < 1 || p.seq_kv < 1 || p.seq_q > 65536 || p.seq_kv > 65536 ||
         p.batch < 1 || p.heads < 1 || p.kv_heads < 1 || p.kv_heads > p.heads || p.heads % p.kv_heads ||
         p.causal_off != (p.causal ? p.seq_kv - p.seq_q : 0) || p.causal_off < 0 || p.s16 < 0 || p.s16 > 2 || !(p.scale > 0.f) ||
@@ -446,7 +554,7 @@ hipError_t launch_flash_attention(const FlashAttentionParams& p, hipStream_t s) 
     // head, 64 queries).  Otherwise the packed-row kernels, a workgroup per (batch entry, K / V head, 64 packed rows)
     // A/B switch (make EXTRA_CXXFLAGS=-DFA_FORCE_PACKED=1): the packed-row kernels also where G == 1 and the diagonal is at key = query — the
     // same rows, grid order and addresses as the plain kernels, so the two builds differ by the kernels' code alone.  DESIGN.md 3.2f
-    const bool gqa = FA_FORCE_PACKED || p.kv_heads != p.heads || p.causal_off != 0;
+    const FaForm gqa = (FA_FORCE_PACKED || p.kv_heads != p.heads || p.causal_off != 0) ? FA_PACKED : FA_PLAIN;
     const long rows = (long)(p.heads / p.kv_heads) * p.seq_q;
     if (rows > 0x7fffffffL) return hipErrorInvalidValue;
     const long nwg = (long)p.batch * p.kv_heads * ((rows + FA_BQ - 1) / FA_BQ);

@@ -1,5 +1,7 @@
 """Op-level entry points of the C ABI (the candle ops the reference's hot path calls), used by the parity tests.
 Weights are host arrays; activations may be numpy (host) or torch-on-GPU (device) tensors."""
+import numpy as np
+
 from . import _ffi
 from . import tensors as T
 
@@ -183,6 +185,41 @@ def flash_attention_gqa(q, k, v, kv_heads=None, causal=False, scale=None, layout
     _ffi.check(_ffi.lib.brn_flash_attention_gqa_forward(pq, pk, pv, batch, seq_q, seq_kv, heads, int(kv_heads), hd, lay, int(bool(causal)), pb, n_bias,
                                                         float(scale) if scale is not None else 0.0, T.ptr_of(y), loc, T.device_of(keep, device),
                                                         T.stream_of(keep)))
+    return y
+
+
+def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_kv, window=(-1, -1), scale=None, kv_heads=None, device=0):
+    """brn_flash_attention_varlen_forward: flash_attention_gqa over a packed batch.  q [total_q, heads, head_dim], k, v
+    [total_kv, kv_heads, head_dim]; sequence s owns rows cu_seqlens[s] .. cu_seqlens[s + 1] - 1 of each.  cu_seqlens_q / cu_seqlens_kv:
+    sequences or integer arrays of n_seqs + 1 offsets, converted to contiguous host int32 (they stay on the host whatever q is).
+    window = (left, right): key j of a row's own sequence takes part in query i's row exactly when i + off - left <= j <= i + off + right,
+    off = len_kv - len_q; -1 = unbounded.  (-1, -1) full, (-1, 0) causal, (W - 1, 0) a causal sliding window of W keys, (w, w) local.
+    kv_heads None = taken from k's shape.  y has q's shape.  What only the wrapper can know is checked here, because the library would
+    write or read past the tensors otherwise: the offsets fit int32, cu_seqlens_q[-1] == q.shape[0] and cu_seqlens_kv[-1] == k.shape[0].
+    Every other limit is the library's (include/birefnet_hip.h)."""
+    cq, ckv = (np.asarray(c.detach().cpu().numpy() if T._is_torch(c) else c).reshape(-1) for c in (cu_seqlens_q, cu_seqlens_kv))
+    if cq.size != ckv.size or cq.size < 2:
+        raise ValueError("cu_seqlens_q and cu_seqlens_kv must hold n_seqs + 1 offsets each, n_seqs >= 1")
+    for c in (cq, ckv):
+        if c.dtype.kind not in "iu" or int(c.min()) < -2 ** 31 or int(c.max()) >= 2 ** 31:
+            raise ValueError("cu_seqlens must be integers that fit int32")
+    cq, ckv = (np.ascontiguousarray(c, dtype=np.int32) for c in (cq, ckv))
+    if int(cq[-1]) != int(q.shape[0]) or int(ckv[-1]) != int(k.shape[0]):
+        raise ValueError(f"cu_seqlens_q[-1] {int(cq[-1])} / cu_seqlens_kv[-1] {int(ckv[-1])} must be the rows of q ({int(q.shape[0])}) / of k and v ({int(k.shape[0])})")
+    window = tuple(min(int(w), 2 ** 31 - 1) for w in window)        # the library takes ints; anything this large is unbounded
+    total_q, heads, hd = (int(s) for s in q.shape)
+    if kv_heads is None:
+        kv_heads = int(k.shape[1])
+    kv_shape = (int(k.shape[0]), int(kv_heads), hd)
+    pq, loc, keep, _ = T.as_arg(q)
+    pk, kloc, kkeep, _ = T.as_arg(k, kv_shape)
+    pv, vloc, vkeep, _ = T.as_arg(v, kv_shape)
+    if not (kloc == vloc == loc):
+        raise ValueError("q, k and v must live on the same side")
+    y = T.alloc_like(keep, (total_q, heads, hd))
+    _ffi.check(_ffi.lib.brn_flash_attention_varlen_forward(pq, pk, pv, cq.ctypes.data, ckv.ctypes.data, int(cq.size) - 1, heads, int(kv_heads), hd,
+                                                           int(window[0]), int(window[1]), float(scale) if scale is not None else 0.0, T.ptr_of(y), loc,
+                                                           T.device_of(keep, device), T.stream_of(keep)))
     return y
 
 

@@ -361,12 +361,53 @@ brn_status brn_flash_attention_bias_forward(const float* q, const float* k, cons
  * heads % kv_heads == 0.
  * Not provided: a split over keys for single-token decode at long seq_kv (it contradicts the no-split invariant these entries promise:
  * a decode call is one workgroup per 64 / G .. 64 rows of a K / V head); sliding-window masks; variable-length batches; 16-bit tensors
- * at the boundary. */
+ * at the boundary.  (Sliding-window masks and variable-length batches, without a bias and in the packed layout, are what
+ * brn_flash_attention_varlen_forward below provides.) */
 brn_status brn_flash_attention_gqa_forward(const float* q, const float* k, const float* v,
                                            int batch, int seq_q, int seq_kv, int heads, int kv_heads, int head_dim,
                                            int layout, int causal,
                                            const float* bias, int n_bias, float scale,
                                            float* y, brn_mem loc, int device_ordinal, void* stream);
+/* brn_flash_attention_gqa_forward over a PACKED batch of sequences of unequal lengths, with a window mask:
+ *   y[i,h] = softmax over the visible keys j of i's own sequence( scale * q[i,h] k[j, h / G]^T ) v[j, h / G]
+ * q, y: [total_q, heads, head_dim]; k, v: [total_kv, kv_heads, head_dim]; contiguous fp32 where `loc` says (the packed "thd" layout: a
+ * [batch, seq, heads, head_dim] tensor is the same memory with cu[b] = b * seq).
+ * cu_seqlens_q, cu_seqlens_kv: n_seqs + 1 int32 values each, always HOST memory (like weights) whatever `loc` says.  Sequence s owns
+ * rows cu[s] .. cu[s + 1] - 1; total_q = cu_seqlens_q[n_seqs], total_kv = cu_seqlens_kv[n_seqs].  Their content is validated on the host
+ * before anything touches the device, and no address in a kernel depends on an unvalidated value.
+ * The mask: with off = len_kv - len_q of the row's own sequence, key j of that sequence takes part in query i's row exactly when
+ *   i + off - window_left <= j <= i + off + window_right;  -1 on a side = unbounded on that side.
+ * (-1, -1) full attention; (-1, 0) the causal mask of the gqa entry, ending at the last key; (W - 1, 0) a causal sliding window of W
+ * keys; (w, w) local bidirectional attention.  An excluded key is a real exclusion (in neither the maximum nor the sum), and a row
+ * never sees a key of another sequence.  A sequence with len_q == 0 computes nothing, and its K / V rows are never read.
+ * Grouping (query head h reads K / V head h / G, G = heads / kv_heads), scale (0 = 1/sqrt(head_dim)), the stream rules and the arithmetic
+ * by brn_set_op_compute are those of brn_flash_attention_gqa_forward: one exact fp32 kernel for BRN_F32 and the three plane modes, the
+ * 16-bit kernels for BRN_BF16 / BRN_F16.  No split over keys, no atomics; a row's bits depend only on its own sequence, query head and
+ * window: not on n_seqs, not on the order of the sequences in the pack, not on the launch grid, not on which rows share its workgroup; a
+ * repeated call repeats its bits.  A workgroup walks only the K / V tiles of 64 keys some row of it can see, so a window costs
+ * O(len * window).  The result carries the bits of brn_flash_attention_gqa_forward on each sequence alone for (-1, -1) and (-1, 0), and
+ * of brn_flash_attention_bias_forward on each sequence with k, v repeated G times and the window written into the bias as -inf.
+ * The workgroup table derived from cu_seqlens is uploaded for the call through a temporary device allocation, so the call synchronises
+ * the stream before it returns, also for BRN_MEM_DEVICE tensors; the cu arrays may be freed when it returns.  This is where its stream
+ * rules differ from the gqa entry's: every call allocates and frees device memory (hipMalloc / hipFree, and hipFree waits for the
+ * whole device, so work on other streams is synchronised too), and the call cannot be made while the stream is being captured into a
+ * graph.
+ * A window side of 65536 or more reaches past every sequence and is treated as 65536, with the bits of -1 on that side where -1 is
+ * allowed (INT_MAX as "unbounded" is safe); it still counts as a window for the len_kv >= len_q rule.
+ * Limits (each violation is BRN_ERR_INVALID_ARG with the prefix "flash attention varlen:" and a message naming the limit, checked
+ * before the device): q, k, v, y, cu_seqlens_q, cu_seqlens_kv not NULL; head_dim 32, 64 or 128; heads >= 1, 1 <= kv_heads <= heads,
+ * heads % kv_heads == 0; n_seqs >= 1; cu_seqlens must start at 0 and be non-decreasing; every len_q, len_kv <= 65536; total_q >= 1;
+ * len_kv >= 1 wherever len_q >= 1; window_left >= -1, window_right >= -1; a window (either side >= 0) requires len_kv >= len_q for
+ * every sequence with queries (every row then sees its diagonal key, and no row is empty); G * len_q < 2^31 and packed-row tiles *
+ * kv_heads < 2^31 (tiles = the sum over sequences of ceil(G * len_q / 64)); scale finite and >= 0; y overlaps no input; BRN_MEM_DEVICE
+ * q, k, v, y 16-byte aligned.
+ * Not provided: a bias with packed sequences; the [batch, heads, seq, head_dim] layout; device-resident cu_seqlens; a split over keys;
+ * 16-bit tensors at the boundary. */
+brn_status brn_flash_attention_varlen_forward(const float* q, const float* k, const float* v,
+                                              const int* cu_seqlens_q, const int* cu_seqlens_kv, int n_seqs,
+                                              int heads, int kv_heads, int head_dim,
+                                              int window_left, int window_right, float scale,
+                                              float* y, brn_mem loc, int device_ordinal, void* stream);
 /* PatchMerging::forward (swin.rs:491-527): x [B,H*W,C] -> [B, ceil(H/2)*ceil(W/2), 2C]. */
 brn_status brn_patch_merging_forward(const float* x, int B, int H, int W, int C, const float* norm_g,
                                      const float* norm_b, const float* reduction_w, float* y, brn_mem loc,

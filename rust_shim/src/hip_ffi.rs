@@ -134,6 +134,10 @@ extern "C" {
                                            heads: c_int, kv_heads: c_int, head_dim: c_int, layout: c_int, causal: c_int, bias: *const c_float,
                                            n_bias: c_int, scale: c_float, y: *mut c_float, loc: c_int, device_ordinal: c_int,
                                            stream: *mut c_void) -> c_int;
+    pub fn brn_flash_attention_varlen_forward(q: *const c_float, k: *const c_float, v: *const c_float, cu_seqlens_q: *const c_int,
+                                              cu_seqlens_kv: *const c_int, n_seqs: c_int, heads: c_int, kv_heads: c_int, head_dim: c_int,
+                                              window_left: c_int, window_right: c_int, scale: c_float, y: *mut c_float, loc: c_int,
+                                              device_ordinal: c_int, stream: *mut c_void) -> c_int;
     pub fn brn_patch_merging_forward(x: *const c_float, b: c_int, h: c_int, w: c_int, c: c_int, norm_g: *const c_float,
                                      norm_b: *const c_float, reduction_w: *const c_float, y: *mut c_float, loc: c_int,
                                      device_ordinal: c_int, stream: *mut c_void) -> c_int;

@@ -24,7 +24,16 @@ highest of its 5 round medians).  Rows (batch, seq_q, seq_kv, heads, kv_heads, h
                     a [1, heads, seq_q, seq_kv] fp32 bias of 0 / -inf
 Each record says whether the two sides returned the same bits.
 
-  python tools/bench_flash_attention.py [--bias | --gqa] [--row N] [--mode f32|bf16|f16] [--json PATH]"""
+--varlen times brn_flash_attention_varlen_forward in the same alternating style, on device tensors, in three groups of rows (--row 0 / 1 / 2):
+  windows   causal sliding windows (W - 1, 0), W = 1024 and 4096, at seq 16384 with 32 / 8 heads of 128, beside the full causal call of the gqa
+            entry on the same values (the window call walks at most ceil((W + 64 / G) / 64) + 1 K / V tiles per workgroup, the full causal call
+            128 on average)
+  ragged    a causal pack of 16 sequences of 128 .. 8192 positions in one call beside a loop of 16 gqa calls, one per sequence
+  uniform   a [batch, seq, heads, head_dim] tensor as a pack with no window beside the gqa entry on it, with a "same bits" column; the packed
+            call uploads its workgroup table through a temporary and synchronises the stream, which the event pair around it sees
+The packed call's cu_seqlens are host arrays, as the entry requires.
+
+  python tools/bench_flash_attention.py [--bias | --gqa | --varlen] [--row N] [--mode f32|bf16|f16] [--json PATH]"""
 import argparse
 import json
 import os
@@ -38,6 +47,10 @@ BIAS_ROWS = ROWS + [(64, 256, 6, 32), (16, 576, 6, 32)]          # + Swin window
 SWIN_ROWS = [(484, 144, 6, 32), (64, 256, 6, 32), (16, 576, 6, 32)]
 GQA_ROWS = [(1, 4096, 4096, 32, 8, 128), (4, 2048, 2048, 32, 8, 64), (1, 512, 4096, 32, 8, 128), (16, 1, 4096, 32, 8, 128)]
 GQA_ROUNDS, GQA_WARMUP, GQA_TIMED = 5, 3, 10
+VARLEN_WINDOW_ROW, VARLEN_WINDOWS = (1, 16384, 16384, 32, 8, 128), (1024, 4096)
+VARLEN_RAGGED = ([128 * n for n in (1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64, 64, 32, 8, 1)], 32, 8, 128)      # lengths, heads, kv_heads, head_dim
+VARLEN_UNIFORM_ROWS = [(4, 4096, 4096, 32, 8, 128), (1, 4096, 4096, 32, 8, 128), (4, 2048, 2048, 32, 8, 64)]
+VARLEN_GROUPS = ["windows", "ragged", "uniform"]
 HBM_BYTES_PER_S = 8.0e12
 MODES = ["f32", "bf16", "f16"]
 WARMUP, TIMED = 5, 20
@@ -222,10 +235,90 @@ def bench_gqa(row, mode):
     return out
 
 
+def _side(prefix, t):
+    med, fastest, lo, hi, _ = t
+    return {prefix + "_ms_median": round(med, 4), prefix + "_ms_fastest": round(fastest, 4), prefix + "_round_medians": [round(lo, 4), round(hi, 4)]}
+
+
+def bench_varlen(group, mode):
+    import numpy as np
+    import torch
+    from candle_birefnet_amd import ops
+    g = torch.Generator(device="cuda").manual_seed(1)
+    out = []
+    ops.set_compute(mode)
+    try:
+        if group == "windows":
+            batch, seq, _, heads, kv_heads, hd = VARLEN_WINDOW_ROW
+            q = torch.randn(batch, seq, heads, hd, device="cuda", generator=g)
+            k, v = (torch.randn(batch, seq, kv_heads, hd, device="cuda", generator=g) for _ in range(2))
+            qp, kp, vp = q.reshape(batch * seq, heads, hd), k.reshape(batch * seq, kv_heads, hd), v.reshape(batch * seq, kv_heads, hd)
+            cu = np.arange(batch + 1) * seq
+            full = lambda: ops.flash_attention_gqa(q, k, v, causal=True)
+            for W in VARLEN_WINDOWS:
+                win = lambda: ops.flash_attention_varlen(qp, kp, vp, cu, cu, window=(W - 1, 0))
+                tw, tf = _time_alternating([win, full])
+                assert bool(torch.isfinite(tw[4]).all())
+                G = heads // kv_heads
+                rec = {"group": group, "batch": batch, "seq": seq, "heads": heads, "kv_heads": kv_heads, "head_dim": hd, "mode": mode, "window": [W - 1, 0],
+                       "tiles_per_workgroup_at_most": -(-(W + 64 // G) // 64) + 1, "full_causal_tiles_per_workgroup_mean": (seq // 64 + 1) / 2}
+                rec.update(_side("window", tw))
+                rec.update(_side("full_causal_gqa", tf))
+                rec["full_over_window"] = round(tf[0] / tw[0], 2)
+                # queries 0 .. W - 1 see keys 0 .. query under both masks
+                rec["first_W_rows_same_bits"] = bool(torch.equal(tw[4][:W], tf[4].reshape(batch * seq, heads, hd)[:W]))
+                out.append(rec)
+                print(f"windows {mode:4s} W {W:5d}: window {tw[0]:9.4f} ms [{tw[2]:.4f} .. {tw[3]:.4f}] | full causal gqa {tf[0]:9.4f} ms [{tf[2]:.4f} .. {tf[3]:.4f}] | "
+                      f"full / window {rec['full_over_window']:.2f} | first W rows same bits {rec['first_W_rows_same_bits']}", flush=True)
+        elif group == "ragged":
+            lens, heads, kv_heads, hd = VARLEN_RAGGED
+            cu = np.concatenate([[0], np.cumsum(lens)])
+            total = int(cu[-1])
+            q = torch.randn(total, heads, hd, device="cuda", generator=g)
+            k, v = (torch.randn(total, kv_heads, hd, device="cuda", generator=g) for _ in range(2))
+            parts = [tuple(a[cu[s]:cu[s + 1]][None] for a in (q, k, v)) for s in range(len(lens))]
+            pack = lambda: ops.flash_attention_varlen(q, k, v, cu, cu, window=(-1, 0))
+            loop = lambda: [ops.flash_attention_gqa(*p, causal=True) for p in parts]
+            tp, tl = _time_alternating([pack, loop])
+            same = all(bool(torch.equal(tp[4][cu[s]:cu[s + 1]], tl[4][s][0])) for s in range(len(lens)))
+            rec = {"group": group, "lengths": lens, "heads": heads, "kv_heads": kv_heads, "head_dim": hd, "mode": mode, "window": [-1, 0]}
+            rec.update(_side("pack", tp))
+            rec.update(_side("loop_of_gqa_calls", tl))
+            rec["loop_over_pack"] = round(tl[0] / tp[0], 2)
+            rec["same_bits"] = same
+            out.append(rec)
+            print(f"ragged  {mode:4s} {len(lens)} sequences, {total} rows: pack {tp[0]:9.4f} ms [{tp[2]:.4f} .. {tp[3]:.4f}] | loop of gqa calls {tl[0]:9.4f} ms "
+                  f"[{tl[2]:.4f} .. {tl[3]:.4f}] | loop / pack {rec['loop_over_pack']:.2f} | same bits {same}", flush=True)
+        else:
+            for batch, seq_q, seq_kv, heads, kv_heads, hd in VARLEN_UNIFORM_ROWS:
+                q = torch.randn(batch, seq_q, heads, hd, device="cuda", generator=g)
+                k, v = (torch.randn(batch, seq_kv, kv_heads, hd, device="cuda", generator=g) for _ in range(2))
+                qp, kp, vp = q.reshape(batch * seq_q, heads, hd), k.reshape(batch * seq_kv, kv_heads, hd), v.reshape(batch * seq_kv, kv_heads, hd)
+                cq, ckv = np.arange(batch + 1) * seq_q, np.arange(batch + 1) * seq_kv
+                pack = lambda: ops.flash_attention_varlen(qp, kp, vp, cq, ckv)
+                gqa = lambda: ops.flash_attention_gqa(q, k, v)
+                tp, tg = _time_alternating([pack, gqa])
+                rec = {"group": group, "batch": batch, "seq_q": seq_q, "seq_kv": seq_kv, "heads": heads, "kv_heads": kv_heads, "head_dim": hd, "mode": mode,
+                       "window": [-1, -1]}
+                rec.update(_side("pack", tp))
+                rec.update(_side("gqa", tg))
+                rec["same_bits"] = bool(torch.equal(tp[4].reshape(tg[4].shape), tg[4]))
+                rec["pack_median_inside_gqa_round_spread"] = bool(tg[2] <= tp[0] <= tg[3])
+                out.append(rec)
+                print(f"uniform {mode:4s} {batch} x {seq_q} / {seq_kv} x {heads} / {kv_heads} x {hd}: pack {tp[0]:9.4f} ms [{tp[2]:.4f} .. {tp[3]:.4f}] | gqa {tg[0]:9.4f} ms "
+                      f"[{tg[2]:.4f} .. {tg[3]:.4f}] | same bits {rec['same_bits']} | inside the gqa spread {rec['pack_median_inside_gqa_round_spread']}", flush=True)
+                del q, k, v, qp, kp, vp
+    finally:
+        ops.set_compute("f32")
+    torch.cuda.empty_cache()
+    return out
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--bias", action="store_true", help="time brn_flash_attention_bias_forward beside the bias-free call and torch + bias")
     ap.add_argument("--gqa", action="store_true", help="time brn_flash_attention_gqa_forward beside the older entries on repeated K / V (and a -inf mask bias)")
+    ap.add_argument("--varlen", action="store_true", help="time brn_flash_attention_varlen_forward: windows, a ragged pack, a uniform pack, beside the gqa entry")
     ap.add_argument("--row", type=int, choices=range(len(BIAS_ROWS)))
     ap.add_argument("--mode", choices=MODES)
     ap.add_argument("--json", help="write the records to this file")
@@ -234,16 +327,17 @@ if __name__ == "__main__":
     if cb.device_count() < 1:
         sys.exit("no HIP device: nothing is measured")
     recs = []
-    if a.bias and a.gqa:
-        sys.exit("--bias and --gqa are two tables: one at a time")
-    rows = BIAS_ROWS if a.bias else GQA_ROWS if a.gqa else ROWS
+    if a.bias + a.gqa + a.varlen > 1:
+        sys.exit("--bias, --gqa and --varlen are separate tables: one at a time")
+    rows = BIAS_ROWS if a.bias else GQA_ROWS if a.gqa else VARLEN_GROUPS if a.varlen else ROWS
     if a.row is not None and a.row >= len(rows):
         sys.exit(f"--row {a.row}: only {len(rows)} rows in this table")
     for row in (rows if a.row is None else [rows[a.row]]):
         for mode in (MODES if a.mode is None else [a.mode]):
-            recs += bench_bias(row, mode) if a.bias else bench_gqa(row, mode) if a.gqa else bench(row, mode)
+            recs += bench_bias(row, mode) if a.bias else bench_gqa(row, mode) if a.gqa else bench_varlen(row, mode) if a.varlen else bench(row, mode)
     if a.json:
         with open(a.json, "w") as f:
-            json.dump({"tool": "tools/bench_flash_attention.py" + (" --bias" if a.bias else " --gqa" if a.gqa else ""), "warmup": GQA_WARMUP if a.gqa else WARMUP,
-                       "timed": GQA_ROUNDS * GQA_TIMED if a.gqa else TIMED, "rows": recs}, f, indent=1)
+            alternating = a.gqa or a.varlen
+            json.dump({"tool": "tools/bench_flash_attention.py" + (" --bias" if a.bias else " --gqa" if a.gqa else " --varlen" if a.varlen else ""),
+                       "warmup": GQA_WARMUP if alternating else WARMUP, "timed": GQA_ROUNDS * GQA_TIMED if alternating else TIMED, "rows": recs}, f, indent=1)
             f.write("\n")
