@@ -211,6 +211,13 @@ struct FlashAttentionParams {
     int n_records;                // the grid is n_records * kv_heads workgroups: workgroup w = (record w / kv_heads, K / V head w % kv_heads)
     int window_left, window_right;   // key j takes part in query i's row exactly when i + off - window_left <= j <= i + off + window_right,
                                      // off = len_kv - len_q of the row's sequence; -1 = unbounded on that side
+    // brn_flash_attention_splitkv_forward; all zero = the kernels above, untouched.  With kv_splits >= 1: the packed-row kernels with the
+    // walk of a workgroup cut into kv_splits ranges of K / V tiles, no bias, no plan (brn_flash_split_plan.h normalises both numbers)
+    int kv_splits;                // S: workgroup w = (packed-row workgroup w / S, split w % S); (S - 1) * tiles_per_split < ceil(seq_kv / 64) <= S * tiles_per_split
+    int tiles_per_split;          // split s walks K / V tiles s * tiles_per_split .. min((s + 1) * tiles_per_split, the row tile's nkt) - 1
+    float* o_part;                // S > 1: [S][R][head_dim] normalised partial outputs, R = batch * heads * seq_q, row r = (b * heads + h) * seq_q + i; null when S == 1
+    float* lse2_part;             // S > 1: [S][R] m + log2(l) of each partial (-inf: no visible key in the split); null when S == 1
+    float* lse;                   // [R] ln sum_j exp(scale q . k_j) over the row's visible keys, or null = not wanted
 };
 hipError_t launch_flash_attention(const FlashAttentionParams& p, hipStream_t s);
 

@@ -2,6 +2,7 @@
 // weights per call, in the arithmetic brn_set_op_compute selected on the calling thread.  Weights are always host pointers; x / y /
 // residual follow `loc`.
 #include "brn_api_util.h"
+#include "brn_flash_split_plan.h"
 #include "brn_flash_varlen_plan.h"
 #include "brn_graph.h"
 #include "kernels/deform_sample_geometry.h"
@@ -278,13 +279,12 @@ brn_status brn_attention_forward(const float* q, const float* k, const float* v,
     });
 }
 
-// brn_flash_attention_forward, brn_flash_attention_bias_forward and brn_flash_attention_gqa_forward: one body.  who = the message prefix;
-// with_bias = an entry with a bias, whose bias / n_bias are checked (the bias-free entry passes null / 0); gqa = the grouped entry, whose
-// kv_heads is checked (the other two pass heads) and whose causal mask ends at the last key
-static void flash_attention_body(const char* who, bool with_bias, bool gqa, const float* q, const float* k, const float* v, int batch, int seq_q,
-                                 int seq_kv, int heads, int kv_heads, int head_dim, int layout, int causal, const float* bias, int n_bias,
-                                 float scale, float* y, brn_mem loc, int device, void* stream) {
-    if (!q || !k || !v || !y) fail(BRN_ERR_INVALID_ARG, "%s: null q, k, v or y", who);
+// brn_flash_attention_forward, brn_flash_attention_bias_forward, brn_flash_attention_gqa_forward and brn_flash_attention_splitkv_forward:
+// one set of checks, one way to fill the kernels' arguments.  who = the message prefix; with_bias = an entry with a bias, whose bias /
+// n_bias are checked (the bias-free entries pass null / 0); gqa = a grouped entry, whose kv_heads is checked (the other two pass heads)
+// and whose causal mask ends at the last key.
+// the sizes alone (what brn_flash_attention_splitkv_plan can check too)
+static void flash_attention_check_sizes(const char* who, bool gqa, int batch, int seq_q, int seq_kv, int heads, int kv_heads, int head_dim) {
     if (!(head_dim == 32 || head_dim == 64 || head_dim == 128))
         fail(BRN_ERR_INVALID_ARG, "%s: head_dim %d unsupported (head_dim must be 32, 64 or 128)", who, head_dim);
     if (seq_q < 1 || seq_q > 65536 || seq_kv < 1 || seq_kv > 65536)
@@ -300,6 +300,13 @@ static void flash_attention_body(const char* who, bool with_bias, bool gqa, cons
                  who, batch, heads, kv_heads, seq_q);
     } else if ((long long)batch * heads * ((seq_q + 15) / 16) > 0x7fffffffLL)
         fail(BRN_ERR_INVALID_ARG, "%s: batch %d, heads %d, seq_q %d too large (batch * heads * ceil(seq_q / 16) < 2^31)", who, batch, heads, seq_q);
+}
+// every check of the three older entries, in their order; nothing here touches the device
+static void flash_attention_check(const char* who, bool with_bias, bool gqa, const float* q, const float* k, const float* v, int batch, int seq_q,
+                                  int seq_kv, int heads, int kv_heads, int head_dim, int layout, int causal, const float* bias, int n_bias,
+                                  float scale, const float* y, brn_mem loc) {
+    if (!q || !k || !v || !y) fail(BRN_ERR_INVALID_ARG, "%s: null q, k, v or y", who);
+    flash_attention_check_sizes(who, gqa, batch, seq_q, seq_kv, heads, kv_heads, head_dim);
     if (layout != BRN_ATTN_BSHD && layout != BRN_ATTN_BHSD) fail(BRN_ERR_INVALID_ARG, "%s: layout %d unknown (layout must be 0 = BSHD or 1 = BHSD)", who, layout);
     if (causal != 0 && causal != 1) fail(BRN_ERR_INVALID_ARG, "%s: causal %d (causal must be 0 or 1)", who, causal);
     if (causal && gqa && seq_kv < seq_q) fail(BRN_ERR_INVALID_ARG, "%s: causal requires seq_kv >= seq_q (seq_q %d, seq_kv %d)", who, seq_q, seq_kv);
@@ -317,8 +324,12 @@ static void flash_attention_body(const char* who, bool with_bias, bool gqa, cons
     if (bias && floats_overlap(bias, nb, y, nq)) fail(BRN_ERR_INVALID_ARG, "%s: y must not overlap the bias", who);
     if (loc == BRN_MEM_DEVICE && !all_aligned16({q, k, v, y})) fail(BRN_ERR_INVALID_ARG, "%s: device q, k, v and y must be 16-byte aligned", who);
     if (loc == BRN_MEM_DEVICE && bias && !all_aligned16({bias})) fail(BRN_ERR_INVALID_ARG, "%s: device bias must be 16-byte aligned", who);
-    ensure_device(device);
-    Staging st(stream, loc);
+}
+// the kernels' arguments of a checked call: operands through st, strides of the layout, mask, scale, arithmetic
+static FlashAttentionParams flash_attention_params(Staging& st, const float* q, const float* k, const float* v, int batch, int seq_q, int seq_kv, int heads,
+                                                   int kv_heads, int head_dim, int layout, int causal, const float* bias, int n_bias, float scale, float* y) {
+    const size_t nq = (size_t)batch * heads * seq_q * head_dim, nkv = (size_t)batch * kv_heads * seq_kv * head_dim;
+    const size_t nb = (size_t)n_bias * heads * seq_q * seq_kv;
     FlashAttentionParams p{};
     p.q = st.in(q, nq); p.k = st.in(k, nkv); p.v = st.in(v, nkv);
     if (bias) {
@@ -340,6 +351,15 @@ static void flash_attention_body(const char* who, bool with_bias, bool gqa, cons
     p.causal_off = causal ? seq_kv - seq_q : 0;
     p.scale = scale_or_default(scale, head_dim);
     p.s16 = attention_op_s16();
+    return p;
+}
+static void flash_attention_body(const char* who, bool with_bias, bool gqa, const float* q, const float* k, const float* v, int batch, int seq_q,
+                                 int seq_kv, int heads, int kv_heads, int head_dim, int layout, int causal, const float* bias, int n_bias,
+                                 float scale, float* y, brn_mem loc, int device, void* stream) {
+    flash_attention_check(who, with_bias, gqa, q, k, v, batch, seq_q, seq_kv, heads, kv_heads, head_dim, layout, causal, bias, n_bias, scale, y, loc);
+    ensure_device(device);
+    Staging st(stream, loc);
+    const FlashAttentionParams p = flash_attention_params(st, q, k, v, batch, seq_q, seq_kv, heads, kv_heads, head_dim, layout, causal, bias, n_bias, scale, y);
     BRN_HIP(launch_flash_attention(p, (hipStream_t)stream));
     st.finish();
 }
@@ -413,6 +433,74 @@ brn_status brn_flash_attention_varlen_forward(const float* q, const float* k, co
         p.window_left = window_left; p.window_right = window_right;
         p.scale = scale_or_default(scale, head_dim);
         p.s16 = attention_op_s16();
+        BRN_HIP(launch_flash_attention(p, (hipStream_t)stream));
+        st.finish();
+    });
+}
+
+// The split over keys.  brn_flash_split_plan.h decides S and tps for both entries below, from the integers alone; the checks the gqa entry
+// makes without a bias are flash_attention_check's, under this entry's prefix.
+static const char* const SPLITKV = "flash attention splitkv";
+static void splitkv_check_splits(int kv_splits) {
+    if (kv_splits < 0 || kv_splits > FA_SPLIT_MAX)
+        fail(BRN_ERR_INVALID_ARG, "%s: kv_splits %d unsupported (0 <= kv_splits <= %d; 0 = the library's rule)", SPLITKV, kv_splits, FA_SPLIT_MAX);
+}
+static FaSplitPlan splitkv_plan_checked(int batch, int seq_q, int seq_kv, int heads, int kv_heads, int head_dim, int kv_splits) {
+    const FaSplitPlan pl = flash_split_plan(batch, seq_q, seq_kv, heads, kv_heads, head_dim, kv_splits);
+    if (pl.base * pl.S > 0x7fffffffLL)
+        fail(BRN_ERR_INVALID_ARG, "%s: %lld workgroups x %d splits too large (batch * kv_heads * ceil(G * seq_q / 64) * S < 2^31)", SPLITKV, pl.base, pl.S);
+    return pl;
+}
+brn_status brn_flash_attention_splitkv_plan(int batch, int seq_q, int seq_kv, int heads, int kv_heads, int head_dim, int kv_splits, int* splits_out,
+                                            int* tiles_per_split_out, size_t* workspace_floats_out) {
+    return guarded([&] {
+        flash_attention_check_sizes(SPLITKV, true, batch, seq_q, seq_kv, heads, kv_heads, head_dim);
+        splitkv_check_splits(kv_splits);
+        const FaSplitPlan pl = splitkv_plan_checked(batch, seq_q, seq_kv, heads, kv_heads, head_dim, kv_splits);
+        if (splits_out) *splits_out = pl.S;
+        if (tiles_per_split_out) *tiles_per_split_out = pl.tps;
+        if (workspace_floats_out) *workspace_floats_out = pl.workspace_floats;
+    });
+}
+
+brn_status brn_flash_attention_splitkv_forward(const float* q, const float* k, const float* v, int batch, int seq_q, int seq_kv, int heads, int kv_heads,
+                                               int head_dim, int layout, int causal, float scale, int kv_splits, float* y, float* lse, float* workspace,
+                                               size_t workspace_floats, brn_mem loc, int device, void* stream) {
+    return guarded([&] {
+        const char* who = SPLITKV;
+        // what the plan entry checks first (a buffer size below means something only once the sizes and the splits are sound), then
+        // every check of the gqa entry without a bias
+        flash_attention_check_sizes(who, true, batch, seq_q, seq_kv, heads, kv_heads, head_dim);
+        splitkv_check_splits(kv_splits);
+        const FaSplitPlan pl = splitkv_plan_checked(batch, seq_q, seq_kv, heads, kv_heads, head_dim, kv_splits);
+        flash_attention_check(who, false, true, q, k, v, batch, seq_q, seq_kv, heads, kv_heads, head_dim, layout, causal, nullptr, 0, scale, y, loc);
+        const size_t nq = (size_t)batch * heads * seq_q * head_dim, nkv = (size_t)batch * kv_heads * seq_kv * head_dim;
+        const size_t R = (size_t)batch * heads * seq_q;
+        // the partials are written, and only they: the workspace counts for what the call needs of it, nothing when S == 1
+        const size_t need = pl.S > 1 ? pl.workspace_floats : 0;
+        if (need && (!workspace || workspace_floats < need))
+            fail(BRN_ERR_INVALID_ARG, "%s: workspace %s for %d splits (it must hold S * batch * heads * seq_q * (head_dim + 1) = %zu floats, workspace_floats %zu)",
+                 who, workspace ? "too small" : "is NULL", pl.S, need, workspace_floats);
+        float* const ws = need ? workspace : nullptr;
+        const struct { const float* p; size_t n; const char* name; } outs[] = {{y, nq, "y"}, {lse, lse ? R : 0, "lse"}, {ws, need, "workspace"}};
+        for (int a = 1; a < 3; ++a) {
+            if (!outs[a].p) continue;
+            if (floats_overlap(q, nq, outs[a].p, outs[a].n) || floats_overlap(k, nkv, outs[a].p, outs[a].n) || floats_overlap(v, nkv, outs[a].p, outs[a].n))
+                fail(BRN_ERR_INVALID_ARG, "%s: %s must not overlap an input", who, outs[a].name);
+            for (int b = 0; b < a; ++b)
+                if (outs[b].p && floats_overlap(outs[b].p, outs[b].n, outs[a].p, outs[a].n))
+                    fail(BRN_ERR_INVALID_ARG, "%s: %s and %s must not overlap", who, outs[b].name, outs[a].name);
+        }
+        if (loc == BRN_MEM_DEVICE && !all_aligned16({lse, ws})) fail(BRN_ERR_INVALID_ARG, "%s: device lse and workspace must be 16-byte aligned", who);
+        ensure_device(device);
+        Staging st(stream, loc);
+        FlashAttentionParams p = flash_attention_params(st, q, k, v, batch, seq_q, seq_kv, heads, kv_heads, head_dim, layout, causal, nullptr, 0, scale, y);
+        p.kv_splits = pl.S; p.tiles_per_split = pl.tps;
+        if (lse) p.lse = st.out(lse, R);
+        if (need) {
+            p.o_part = st.out(ws, need);
+            p.lse2_part = p.o_part + (size_t)pl.S * R * head_dim;
+        }
         BRN_HIP(launch_flash_attention(p, (hipStream_t)stream));
         st.finish();
     });

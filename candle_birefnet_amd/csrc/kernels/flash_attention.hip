@@ -54,6 +54,17 @@
 // 0 + 0 . V until the row's own first tile; nothing needs wiping (alpha = 0 there multiplies zeros).  Tiles past a row's hi leave
 // alpha = 1 and numerators exp2(-inf - m) = 0, as above.  So a row's bits depend on its sequence, query head and window alone, and equal
 // those of the bias kernels on that sequence with the window written into the bias as -inf, also for large V.  DESIGN.md 3.2g.
+// FA_SPLIT (brn_flash_attention_splitkv_forward): the fourth form.  One workgroup = one (batch entry, K / V head, tile of 64 packed rows,
+// split s of S); the rows are those of FA_PACKED (fa_block_gqa on the workgroup's number / S, fa_lane unchanged) and the walk covers K / V
+// tiles s tps .. min((s + 1) tps, the tile's causal nkt) - 1 (fa_block_split), started at kt_first as FA_VARLEN's.  A split
+// other than the first does not hold key 0, so under the causal mask a row may meet wholly excluded tiles while m is still ATT_NEG: the
+// form excludes with -inf exactly as FA_VARLEN does (att_exclude4_window with lo = 0), and such a tile leaves m = ATT_NEG, alpha = 1,
+// l = 0, O = 0.  A workgroup whose range is empty (its tile's causal nkt ends before the split starts) decides so workgroup-uniformly
+// before the first barrier, writes the empty markers of its real rows and returns.  fa_finish_split stores o * (1 / l) with the
+// operations of fa_finish and m + log2(l) from lane group 0: into the workspace (O_part[s][r][d], lse2_part[s][r], r = (batch entry *
+// heads + head) * seq_q + query, 64-bit offsets) when S > 1, straight into y (and lse = ln 2 * that) when S == 1; a row with l == 0 gets
+// 0 and -inf, selected, never computed as 0 * inf.  flash_split_combine_kernel then merges the S partials of a row in the order
+// s = 0 .. S - 1.  No atomics; a row's bits depend on its (batch entry, query head), seq_kv, the mask and tps alone.  DESIGN.md 3.2h.
 #include "../brn_kernels.h"
 #include "../brn_flash_varlen_plan.h"
 #include "attention_mfma.h"
@@ -69,8 +80,8 @@ static_assert(FA_BQ == FA_VARLEN_ROWS && FA_T == FA_VARLEN_ROWS, "the records of
 constexpr int FA_VT_LD = 72;         // 16-bit kernel: elements per LDS row of V^T (36 dwords: conflict-free 8-byte reads, 2-way 4-byte writes)
 
 // the three forms of the kernels: a workgroup per (batch entry, head, 64 queries); per (batch entry, K / V head, 64 packed rows); per
-// (record of a packed batch, K / V head), with a window
-enum FaForm { FA_PLAIN = 0, FA_PACKED = 1, FA_VARLEN = 2 };
+// (record of a packed batch, K / V head), with a window; per (batch entry, K / V head, 64 packed rows, split over keys)
+enum FaForm { FA_PLAIN = 0, FA_PACKED = 1, FA_VARLEN = 2, FA_SPLIT = 3 };
 
 // which (batch entry, head, query tile) this workgroup owns, where its operands start and how many K / V tiles it walks
 struct FaBlock {
@@ -78,13 +89,13 @@ struct FaBlock {
     const float* bias;    // BIAS: the [seq_q, seq_kv] slab of this (bias pattern = batch entry % n_bias, head)
     int q0;               // first query of the tile (GQA: first packed row)
     int nkt;              // K / V tiles to walk: all of them, or (causal) those that reach the tile's last query; FA_VARLEN: one past the last (kt1)
-    int kt0;              // FA_VARLEN: the first K / V tile to walk (the other forms start at 0)
+    int kt0;              // FA_VARLEN, FA_SPLIT: the first K / V tile to walk (the other forms start at 0)
     int G, h0, rem;       // GQA: query heads per K / V head, the group's first query head, real rows after q0 (the tile's last real row is q0 + min(63, rem))
 };
 // GQA: the workgroup is (batch entry, K / V head, tile of 64 packed rows); q, y and bias point at the batch entry (pattern), the head is a
 // lane's own (fa_lane); k and v at the K / V head
 template <bool BIAS>
-__device__ __forceinline__ FaBlock fa_block_gqa(const FlashAttentionParams& p) {
+__device__ __forceinline__ FaBlock fa_block_gqa(const FlashAttentionParams& p, const unsigned wg) {   // wg: blockIdx.x; FA_SPLIT: blockIdx.x / S
     FaBlock r;
     r.G = p.heads / p.kv_heads;
     const int rows = r.G * p.seq_q;                      // < 2^31 (launch_flash_attention)
@@ -93,9 +104,9 @@ __device__ __forceinline__ FaBlock fa_block_gqa(const FlashAttentionParams& p) {
     int bh, qt;
     if (p.causal) {
         const unsigned nbh = (unsigned)(p.batch * p.kv_heads);
-        qt = nqt - 1 - (int)(blockIdx.x / nbh); bh = (int)(blockIdx.x % nbh);
+        qt = nqt - 1 - (int)(wg / nbh); bh = (int)(wg % nbh);
     } else {
-        bh = (int)(blockIdx.x / (unsigned)nqt); qt = (int)(blockIdx.x - (unsigned)bh * (unsigned)nqt);
+        bh = (int)(wg / (unsigned)nqt); qt = (int)(wg - (unsigned)bh * (unsigned)nqt);
     }
     const int b = bh / p.kv_heads, kvh = bh - b * p.kv_heads;
     r.q = p.q + b * p.q_sb;
@@ -131,9 +142,27 @@ __device__ __forceinline__ FaBlock fa_block_varlen(const FlashAttentionParams& p
     r.nkt = rec.kt1;
     return r;
 }
+// FA_SPLIT: the S splits of a (batch entry, K / V head, row tile) are neighbours in the grid; the tile is fa_block_gqa's, the walk the
+// part of it that split s owns: K / V tiles s * tps .. min((s + 1) * tps, nkt) - 1, empty (kt0 >= nkt) where the causal nkt ends before
+__device__ __forceinline__ FaBlock fa_block_split(const FlashAttentionParams& p) {
+    const unsigned S = (unsigned)p.kv_splits, wg = blockIdx.x / S;
+    FaBlock r = fa_block_gqa<false>(p, wg);
+    r.kt0 = (int)(blockIdx.x - wg * S) * p.tiles_per_split;
+    r.nkt = min(r.nkt, r.kt0 + p.tiles_per_split);
+    return r;
+}
+// FA_SPLIT: the workgroup's split and its batch entry (the grid order of fa_block_gqa, restated for the one value FaBlock does not keep)
+struct FaSplit { int b, split; };
+__device__ __forceinline__ FaSplit fa_split_of(const FlashAttentionParams& p) {
+    const unsigned S = (unsigned)p.kv_splits, wg = blockIdx.x / S;
+    const int nqt = (p.heads / p.kv_heads * p.seq_q - 1) / FA_BQ + 1;
+    const int bh = p.causal ? (int)(wg % (unsigned)(p.batch * p.kv_heads)) : (int)(wg / (unsigned)nqt);
+    return FaSplit{bh / p.kv_heads, (int)(blockIdx.x - wg * S)};
+}
 template <bool BIAS, FaForm FORM>
 __device__ __forceinline__ FaBlock fa_block(const FlashAttentionParams& p) {
-    if constexpr (FORM == FA_PACKED) return fa_block_gqa<BIAS>(p);
+    if constexpr (FORM == FA_SPLIT) return fa_block_split(p);
+    if constexpr (FORM == FA_PACKED) return fa_block_gqa<BIAS>(p, blockIdx.x);
     const int nqt = (p.seq_q + FA_BQ - 1) / FA_BQ;
     // not causal: the query tiles of a (batch entry, head) are neighbours in the grid (they walk the same K and V).  Causal: tile qt walks
     // qt + 1 K / V tiles, so the grid is ordered by query tile, last (longest) first: the launch ends on the short workgroups
@@ -193,7 +222,7 @@ __device__ __forceinline__ FaLane fa_lane(const FlashAttentionParams& p, const F
         const int qa = (blk.q0 + min(wave * 16, blk.rem)) / blk.G, qb = (blk.q0 + min(wave * 16 + 15, blk.rem)) / blk.G;
         r.wave_row0 = wr < 0 ? p.seq_kv : min(p.seq_kv, qa + p.causal_off + wr + 1);
         r.wave_lo = wl < 0 ? 0 : max(0, qb + p.causal_off - wl);
-    } else if constexpr (FORM == FA_PACKED) {
+    } else if constexpr (FORM == FA_PACKED || FORM == FA_SPLIT) {             // (FA_SPLIT has no bias: blk.bias is null and never read)
         const int lr = wave * 16 + li;
         const int row = blk.q0 + min(lr, blk.rem);
         const int query = row / blk.G, head = blk.h0 + (row - query * blk.G);
@@ -321,6 +350,36 @@ __device__ __forceinline__ void fa_finish(float* yrow, int g, const f32x4 (&o)[N
     }
 }
 
+// FA_SPLIT: the end of a split's walk.  o * (1 / l) with the operations of fa_finish (a partial carries the bits of the gqa entry on the
+// split's keys), and m + log2(l) in the base-2 scaled-score domain from lane group 0.  A row that saw no key of the split (l == 0: only
+// under the causal mask, or a workgroup with nothing to walk) stores 0 and -inf: inv is SELECTED to 0, 0 * inf is never computed.
+// S > 1 (p.o_part): row r = (batch entry * heads + head) * seq_q + query of the workspace's O_part[split] and lse2_part[split], 64-bit
+// offsets.  S == 1: the row of y, and lse[r] = ln 2 * (m + log2 l) where lse is wanted.
+template <int D>
+__device__ __forceinline__ void fa_finish_split(const FlashAttentionParams& p, const FaBlock& blk, const FaLane& ln, int g, const f32x4 (&o)[D / 16], float l, float m) {
+    const float lsum = att_group_sum(l);
+    const bool empty = !(lsum > 0.f);
+    const float inv = empty ? 0.f : 1.0f / lsum;
+    const float lse2 = empty ? -__builtin_inff() : m + __builtin_amdgcn_logf(lsum);
+    if (ln.yrow < 0) return;
+    const int row = ln.yrow, query = row / blk.G, head = blk.h0 + (row - query * blk.G);
+    const FaSplit sp = fa_split_of(p);
+    const long r = ((long)sp.b * p.heads + head) * p.seq_q + query;
+    float* dst; float* ldst; float lv = lse2;
+    if (p.o_part) {
+        const long R = (long)p.batch * p.heads * p.seq_q;
+        dst = p.o_part + ((long)sp.split * R + r) * D;
+        ldst = p.lse2_part + ((long)sp.split * R + r);
+    } else {
+        dst = blk.y + (head * p.q_sh + query * p.q_ss);
+        ldst = p.lse ? p.lse + r : nullptr;
+        lv = lse2 * 0.6931471805599453f;
+    }
+#pragma unroll
+    for (int dt = 0; dt < D / 16; ++dt) att_store_o(dst + g * 4, dt, o[dt], inv);
+    if (g == 0 && ldst) *ldst = lv;
+}
+
 // ---- fp32: v_mfma_f32_16x16x4_f32, an exact fmaf chain per score and per output ----
 // LDS: Ks, Vs [64][D + 4] floats (D 128: 66 KB).  Staging item = (key, 4-wide d chunk), D / 16 items of K and of V per thread.
 template <int D, bool BIAS, FaForm FORM>
@@ -334,6 +393,16 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
     const FlashAttentionParams p = fa_params<FORM>(pa, rec);
     const FaBlock blk = fa_block_of<BIAS, FORM>(p, rec);
     const FaLane ln = fa_lane<FORM>(p, blk, wave, li);
+    if constexpr (FORM == FA_SPLIT) {
+        // nothing to walk (workgroup-uniform, before the first barrier): the empty markers of the real rows
+        if (blk.kt0 >= blk.nkt) {
+            f32x4 z[D / 16];
+#pragma unroll
+            for (int dt = 0; dt < D / 16; ++dt) z[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+            fa_finish_split<D>(p, blk, ln, g, z, 0.f, ATT_NEG);
+            return;
+        }
+    }
     // Q fragment: chunk c of 32 d's -> d = 32 c + 8 g .. + 7 of the query's row (the MFMA k order is a permutation of d; K uses the same)
     f32x4 qv[2 * NC];
     {
@@ -363,7 +432,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
     float m = ATT_NEG, l = 0.f;
     const float sc2 = p.scale * ATT_LOG2E;
 
-    const int kt_first = FORM == FA_VARLEN ? blk.kt0 : 0;
+    const int kt_first = (FORM == FA_VARLEN || FORM == FA_SPLIT) ? blk.kt0 : 0;
     load_tile(kt_first * FA_T);
     for (int kt = kt_first; kt < blk.nkt; ++kt) {
         __syncthreads();                                   // every wave is done reading the previous tile
@@ -391,6 +460,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
         }
         float alpha;
         if constexpr (FORM == FA_VARLEN) alpha = fa_softmax_tile<true>(st, sc2, fa_tile_masks_window(kt * FA_T, ln.wave_row0, ln.wave_lo), kt * FA_T, g, ln.limit, m, l, ln.lo);
+        else if constexpr (FORM == FA_SPLIT) alpha = fa_softmax_tile<true>(st, sc2, fa_tile_masks(p, kt * FA_T, ln.wave_row0), kt * FA_T, g, ln.limit, m, l, 0);
         else alpha = fa_softmax_tile(st, sc2, fa_tile_masks(p, kt * FA_T, ln.wave_row0), kt * FA_T, g, ln.limit, m, l);
 #pragma unroll
         for (int dt = 0; dt < ND; ++dt) o[dt] *= alpha;
@@ -405,7 +475,8 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
             }
         }
     }
-    fa_finish<ND, BIAS>(fa_lane_y<FORM>(p, blk, ln), g, o, l, m);
+    if constexpr (FORM == FA_SPLIT) fa_finish_split<D>(p, blk, ln, g, o, l, m);
+    else fa_finish<ND, BIAS>(fa_lane_y<FORM>(p, blk, ln), g, o, l, m);
 }
 
 // ---- 16-bit: q, k, v rounded to E (round to nearest even) as they are loaded; v_mfma_f32_16x16x32_{bf16,f16} with fp32 accumulation.
@@ -427,6 +498,16 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
     const FlashAttentionParams p = fa_params<FORM>(pa, rec);
     const FaBlock blk = fa_block_of<BIAS, FORM>(p, rec);
     const FaLane ln = fa_lane<FORM>(p, blk, wave, li);
+    if constexpr (FORM == FA_SPLIT) {
+        // nothing to walk (workgroup-uniform, before the first barrier): the empty markers of the real rows
+        if (blk.kt0 >= blk.nkt) {
+            f32x4 z[D / 16];
+#pragma unroll
+            for (int dt = 0; dt < D / 16; ++dt) z[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+            fa_finish_split<D>(p, blk, ln, g, z, 0.f, ATT_NEG);
+            return;
+        }
+    }
     // Q fragment of MFMA k step c: d = 32 c + 8 g .. + 7 of the query's row
     ex8 qf[NP];
     {
@@ -459,7 +540,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
     float m = ATT_NEG, l = 0.f;
     const float sc2 = p.scale * ATT_LOG2E;
 
-    const int kt_first = FORM == FA_VARLEN ? blk.kt0 : 0;
+    const int kt_first = (FORM == FA_VARLEN || FORM == FA_SPLIT) ? blk.kt0 : 0;
     load_tile(kt_first * FA_T);
     for (int kt = kt_first; kt < blk.nkt; ++kt) {
         __syncthreads();                                   // every wave is done reading the previous tile
@@ -496,6 +577,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
         }
         float alpha;
         if constexpr (FORM == FA_VARLEN) alpha = fa_softmax_tile<true>(st, sc2, fa_tile_masks_window(kt * FA_T, ln.wave_row0, ln.wave_lo), kt * FA_T, g, ln.limit, m, l, ln.lo);
+        else if constexpr (FORM == FA_SPLIT) alpha = fa_softmax_tile<true>(st, sc2, fa_tile_masks(p, kt * FA_T, ln.wave_row0), kt * FA_T, g, ln.limit, m, l, 0);
         else alpha = fa_softmax_tile(st, sc2, fa_tile_masks(p, kt * FA_T, ln.wave_row0), kt * FA_T, g, ln.limit, m, l);
 #pragma unroll
         for (int dt = 0; dt < ND; ++dt) o[dt] *= alpha;
@@ -507,7 +589,59 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
             for (int dt = 0; dt < ND; ++dt) o[dt] = att_mfma<F16>(att_vt_frag(Vt + (dt * 16 + li) * FA_VT_LD + g * 4, t), pf, o[dt]);
         }
     }
-    fa_finish<ND, BIAS>(fa_lane_y<FORM>(p, blk, ln), g, o, l, m);
+    if constexpr (FORM == FA_SPLIT) fa_finish_split<D>(p, blk, ln, g, o, l, m);
+    else fa_finish<ND, BIAS>(fa_lane_y<FORM>(p, blk, ln), g, o, l, m);
+}
+
+// ---- FA_SPLIT, S > 1: the S partials of a row become the row.  One thread = (row r, 4 consecutive d): M = max_s lse2_part[s][r],
+// w_s = exp2(lse2_part[s][r] - M), y = (sum_s w_s O_part[s][r]) / sum_s w_s with both sums in the order s = 0 .. S - 1,
+// lse = ln 2 * (M + log2 sum_s w_s) from the thread of d = 0.  Split 0 holds key 0, which every row sees, so M is finite; an empty partial
+// (-inf) has w = exp2(-inf) = 0 exactly and its O_part is 0.  y has q's strides; every offset into the workspace is 64-bit.
+// A decode call has few rows and many splits, so the kernel is a chain of S load latencies unless the loads are issued together: the
+// partials are fetched FA_COMBINE_CHUNK splits at a time (the index clamped to S - 1, the value of a clamped slot not used), and only
+// the arithmetic runs one split after the other. ----
+constexpr int FA_COMBINE_THREADS = 256;
+constexpr int FA_COMBINE_CHUNK = 8;
+__global__ void __launch_bounds__(FA_COMBINE_THREADS) flash_split_combine_kernel(const FlashAttentionParams p) {
+    const int D4 = p.head_dim / 4;
+    const long R = (long)p.batch * p.heads * p.seq_q;
+    const long idx = (long)blockIdx.x * FA_COMBINE_THREADS + threadIdx.x;
+    if (idx >= R * D4) return;
+    const long r = idx / D4;
+    const int d = (int)(idx - r * D4) * 4;
+    const int S = p.kv_splits;
+    float M = -__builtin_inff();
+    for (int s0 = 0; s0 < S; s0 += FA_COMBINE_CHUNK) {
+        float l2[FA_COMBINE_CHUNK];
+#pragma unroll
+        for (int j = 0; j < FA_COMBINE_CHUNK; ++j) l2[j] = p.lse2_part[(long)min(s0 + j, S - 1) * R + r];
+#pragma unroll
+        for (int j = 0; j < FA_COMBINE_CHUNK; ++j) M = fmaxf(M, l2[j]);          // (a clamped slot repeats split S - 1)
+    }
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    float wsum = 0.f;
+    for (int s0 = 0; s0 < S; s0 += FA_COMBINE_CHUNK) {
+        float l2[FA_COMBINE_CHUNK];
+        f32x4 ov[FA_COMBINE_CHUNK];
+#pragma unroll
+        for (int j = 0; j < FA_COMBINE_CHUNK; ++j) {
+            const long sr = (long)min(s0 + j, S - 1) * R + r;
+            l2[j] = p.lse2_part[sr];
+            ov[j] = *reinterpret_cast<const f32x4*>(p.o_part + sr * p.head_dim + d);
+        }
+#pragma unroll
+        for (int j = 0; j < FA_COMBINE_CHUNK; ++j) {
+            if (s0 + j < S) {                                                      // wave-uniform
+                const float w = __builtin_amdgcn_exp2f(l2[j] - M);
+                acc += ov[j] * w;
+                wsum += w;
+            }
+        }
+    }
+    const long bh = r / p.seq_q;
+    const int query = (int)(r - bh * p.seq_q), b = (int)(bh / p.heads), head = (int)(bh - (long)b * p.heads);
+    *reinterpret_cast<f32x4*>(p.y + (b * p.q_sb + head * p.q_sh + query * p.q_ss + d)) = acc / wsum;
+    if (d == 0 && p.lse) p.lse[r] = (M + __builtin_amdgcn_logf(wsum)) * 0.6931471805599453f;
 }
 
 template <int D, bool BIAS, FaForm FORM>
@@ -520,6 +654,7 @@ void fa_launch(const FlashAttentionParams& p, dim3 grid, hipStream_t s) {
 template <int D>
 void fa_launch(const FlashAttentionParams& p, FaForm form, dim3 grid, hipStream_t s) {
     if (form == FA_VARLEN) fa_launch<D, false, FA_VARLEN>(p, grid, s);
+    else if (form == FA_SPLIT) fa_launch<D, false, FA_SPLIT>(p, grid, s);
     else if (form == FA_PACKED) {
         if (p.bias) fa_launch<D, true, FA_PACKED>(p, grid, s);
         else fa_launch<D, false, FA_PACKED>(p, grid, s);
@@ -550,6 +685,23 @@ hipError_t launch_flash_attention(const FlashAttentionParams& p, hipStream_t s) 
         p.causal_off != (p.causal ? p.seq_kv - p.seq_q : 0) || p.causal_off < 0 || p.s16 < 0 || p.s16 > 2 || !(p.scale > 0.f) ||
         p.n_bias < 0 || (p.bias == nullptr) != (p.n_bias == 0) || (p.n_bias > 0 && p.batch % p.n_bias))
         return hipErrorInvalidValue;
+    if (p.kv_splits) {
+        // the split over keys: S = kv_splits and tps = tiles_per_split as brn_flash_split_plan.h normalises them (no empty trailing split),
+        // the partials in the workspace exactly when S > 1; no bias
+        const int nkt = (p.seq_kv + FA_T - 1) / FA_T, S = p.kv_splits, tps = p.tiles_per_split;
+        const long rows = (long)(p.heads / p.kv_heads) * p.seq_q;
+        const long nwg = (long)p.batch * p.kv_heads * ((rows + FA_BQ - 1) / FA_BQ) * S;
+        const long quads = (long)p.batch * p.heads * p.seq_q * (p.head_dim / 4);
+        if (p.bias || S < 1 || tps < 1 || (long)(S - 1) * tps >= nkt || (long)S * tps < nkt || rows > 0x7fffffffL || nwg > 0x7fffffffL ||
+            (S > 1) != (p.o_part != nullptr) || (S > 1) != (p.lse2_part != nullptr) || (quads + FA_COMBINE_THREADS - 1) / FA_COMBINE_THREADS > 0x7fffffffL)
+            return hipErrorInvalidValue;
+        const dim3 grid((unsigned)nwg);
+        if (p.head_dim == 32) fa_launch<32>(p, FA_SPLIT, grid, s);
+        else if (p.head_dim == 64) fa_launch<64>(p, FA_SPLIT, grid, s);
+        else fa_launch<128>(p, FA_SPLIT, grid, s);
+        if (S > 1) hipLaunchKernelGGL(flash_split_combine_kernel, dim3((unsigned)((quads + FA_COMBINE_THREADS - 1) / FA_COMBINE_THREADS)), dim3(FA_COMBINE_THREADS), 0, s, p);
+        return hipGetLastError();
+    }
     // one K / V head per query head and the diagonal at key = query: the kernels of the two older entries, a workgroup per (batch entry,
     // head, 64 queries).  Otherwise the packed-row kernels, a workgroup per (batch entry, K / V head, 64 packed rows)
     // A/B switch (make EXTRA_CXXFLAGS=-DFA_FORCE_PACKED=1): the packed-row kernels also where G == 1 and the diagonal is at key = query — the

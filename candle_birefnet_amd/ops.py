@@ -223,6 +223,50 @@ def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_kv, window=(-1, -1)
     return y
 
 
+def flash_attention_splitkv_plan(batch, seq_q, seq_kv, heads, kv_heads, head_dim, kv_splits=0):
+    """brn_flash_attention_splitkv_plan: (S, tiles_per_split, workspace_floats) a call with these integers will use; needs no device."""
+    import ctypes as C
+    S, tps, nws = C.c_int(0), C.c_int(0), C.c_size_t(0)
+    _ffi.check(_ffi.lib.brn_flash_attention_splitkv_plan(int(batch), int(seq_q), int(seq_kv), int(heads), int(kv_heads), int(head_dim), int(kv_splits),
+                                                         C.byref(S), C.byref(tps), C.byref(nws)))
+    return S.value, tps.value, nws.value
+
+
+def flash_attention_splitkv(q, k, v, kv_heads=None, causal=False, scale=None, layout="bshd", kv_splits=0, return_lse=False, return_partials=False,
+                            device=0):
+    """brn_flash_attention_splitkv_forward: flash_attention_gqa without a bias, the K / V tiles of a call split between workgroups
+    (kv_splits; 0 = the library's rule) and combined in a fixed order.  Shapes, layout, kv_heads, causal and scale as in
+    flash_attention_gqa.  The workspace is sized by brn_flash_attention_splitkv_plan and allocated beside q.  Returns y; with return_lse
+    (y, lse [batch, heads, seq_q]); with return_partials additionally (O_part [S, R, head_dim], lse2_part [S, R]), views of the
+    workspace, R = batch * heads * seq_q (heads-major rows); S == 1 leaves no partials and returns (None, None).  The limits are the
+    library's (include/birefnet_hip.h): nothing is checked here."""
+    lay = _ATTN_LAYOUT[layout]
+    seq_axis, head_axis = (1, 2) if lay == _ffi.BRN_ATTN_BSHD else (2, 1)
+    batch, hd = int(q.shape[0]), int(q.shape[3])
+    seq_q, heads, seq_kv = int(q.shape[seq_axis]), int(q.shape[head_axis]), int(k.shape[seq_axis])
+    if kv_heads is None:
+        kv_heads = int(k.shape[head_axis])
+    kv_shape = (batch, seq_kv, kv_heads, hd) if lay == _ffi.BRN_ATTN_BSHD else (batch, kv_heads, seq_kv, hd)
+    pq, loc, keep, _ = T.as_arg(q)
+    pk, kloc, kkeep, _ = T.as_arg(k, kv_shape)
+    pv, vloc, vkeep, _ = T.as_arg(v, kv_shape)
+    if not (kloc == vloc == loc):
+        raise ValueError("q, k and v must live on the same side")
+    S, _tps, nws = flash_attention_splitkv_plan(batch, seq_q, seq_kv, heads, kv_heads, hd, kv_splits)
+    R = batch * heads * seq_q
+    y = T.alloc_like(keep, tuple(int(s) for s in q.shape))
+    lse = T.alloc_like(keep, (batch, heads, seq_q)) if return_lse else None
+    ws = T.alloc_like(keep, (nws,)) if S > 1 else None
+    _ffi.check(_ffi.lib.brn_flash_attention_splitkv_forward(pq, pk, pv, batch, seq_q, seq_kv, heads, int(kv_heads), hd, lay, int(bool(causal)),
+                                                            float(scale) if scale is not None else 0.0, int(kv_splits), T.ptr_of(y),
+                                                            T.ptr_of(lse) if lse is not None else None, T.ptr_of(ws) if ws is not None else None,
+                                                            nws if ws is not None else 0, loc, T.device_of(keep, device), T.stream_of(keep)))
+    out = (y,) + ((lse,) if return_lse else ())
+    if return_partials:
+        out += ((ws[:S * R * hd].reshape(S, R, hd), ws[S * R * hd:].reshape(S, R)) if ws is not None else (None, None),)
+    return out[0] if len(out) == 1 else out
+
+
 def patch_merging(x, H, W, norm_g, norm_b, reduction_w, device=0):
     """PatchMerging::forward (swin.rs:491-527): x [B,H*W,C] -> [B, ceil(H/2)*ceil(W/2), 2C]."""
     B, L, Cc = (int(v) for v in x.shape)

@@ -362,7 +362,8 @@ brn_status brn_flash_attention_bias_forward(const float* q, const float* k, cons
  * Not provided: a split over keys for single-token decode at long seq_kv (it contradicts the no-split invariant these entries promise:
  * a decode call is one workgroup per 64 / G .. 64 rows of a K / V head); sliding-window masks; variable-length batches; 16-bit tensors
  * at the boundary.  (Sliding-window masks and variable-length batches, without a bias and in the packed layout, are what
- * brn_flash_attention_varlen_forward below provides.) */
+ * brn_flash_attention_varlen_forward below provides; the split over keys, as an entry with its own promise,
+ * brn_flash_attention_splitkv_forward.) */
 brn_status brn_flash_attention_gqa_forward(const float* q, const float* k, const float* v,
                                            int batch, int seq_q, int seq_kv, int heads, int kv_heads, int head_dim,
                                            int layout, int causal,
@@ -402,12 +403,49 @@ brn_status brn_flash_attention_gqa_forward(const float* q, const float* k, const
  * kv_heads < 2^31 (tiles = the sum over sequences of ceil(G * len_q / 64)); scale finite and >= 0; y overlaps no input; BRN_MEM_DEVICE
  * q, k, v, y 16-byte aligned.
  * Not provided: a bias with packed sequences; the [batch, heads, seq, head_dim] layout; device-resident cu_seqlens; a split over keys;
- * 16-bit tensors at the boundary. */
+ * 16-bit tensors at the boundary.  (The split over keys, for dense batches, is brn_flash_attention_splitkv_forward below.) */
 brn_status brn_flash_attention_varlen_forward(const float* q, const float* k, const float* v,
                                               const int* cu_seqlens_q, const int* cu_seqlens_kv, int n_seqs,
                                               int heads, int kv_heads, int head_dim,
                                               int window_left, int window_right, float scale,
                                               float* y, brn_mem loc, int device_ordinal, void* stream);
+/* brn_flash_attention_gqa_forward without a bias, with the K / V tiles of a call SPLIT between workgroups and the log-sum-exp of every
+ * row: the entry for single-token or few-token decode over a long cache, where the gqa entry's grid of batch * kv_heads *
+ * ceil(G * seq_q / 64) workgroups leaves most of the device idle, and for callers who merge attention over key ranges computed elsewhere.
+ *   y[b,h] = softmax_rows( scale * q[b,h] k[b, h / G]^T  [causal mask] ) v[b, h / G],   lse[b,h,i] = ln sum_j exp(scale * q[b,h,i] . k[b, h / G, j])
+ * q, k, v, y, layout, G = heads / kv_heads and scale (0 = head_dim^-0.5) are those of brn_flash_attention_gqa_forward; causal 1 ends the
+ * mask at the last key and requires seq_kv >= seq_q.  lse: [batch, heads, seq_q] fp32, heads-major in either layout (like a bias), the sum
+ * over the row's visible keys; NULL = not wanted.  Arithmetic by brn_set_op_compute: one exact fp32 kernel for BRN_F32 and the three
+ * plane modes, the 16-bit kernels for BRN_BF16 / BRN_F16.
+ * The split: nkt = ceil(seq_kv / 64) K / V tiles, tps = ceil(nkt / kv_splits), S = ceil(nkt / tps) (no empty trailing split, S <=
+ * kv_splits); split s owns tiles s * tps .. min((s + 1) * tps, nkt) - 1, so the boundaries are tile boundaries and functions of seq_kv and
+ * kv_splits alone.  kv_splits 0 lets the library choose, by a rule that is a pure function of the call's integer arguments (never of a
+ * queried device property); brn_flash_attention_splitkv_plan returns the S, tps and workspace size a call will use, without a device,
+ * and the explicit kv_splits = S repeats the bits.
+ * workspace: where `loc` says, workspace_floats >= S * R * (head_dim + 1) floats with R = batch * heads * seq_q; NULL / 0 is allowed when
+ * S == 1 (it is then not touched).  On return it holds the partials, and the layout is part of the contract:
+ *   O_part[s][r][d] at float (s * R + r) * head_dim + d, then lse2_part[s][r] at float S * R * head_dim + s * R + r, r = (b * heads + h) * seq_q + i.
+ * O_part[s][r] is the softmax-weighted V over the keys of split s alone, normalised; lse2_part[s][r] is m + log2(l) of that split in the
+ * kernels' base-2 domain (scores times scale * log2 e).  A row with no visible key in split s (under the causal mask) gets O_part = 0
+ * and lse2_part = -inf.  Floats past S * R * (head_dim + 1) are not touched.
+ * The promise: no atomics; the partials of a row are combined in the fixed order s = 0 .. S - 1; a row's bits depend only on its own
+ * (batch entry, query head), seq_kv, the mask and tps, neither on `batch` nor on the launch grid nor on which rows share its workgroup;
+ * a repeated call repeats its bits; with S == 1 the result carries the bits of brn_flash_attention_gqa_forward.  With BRN_MEM_DEVICE the
+ * call allocates nothing and does not synchronise the stream (unlike brn_flash_attention_varlen_forward, whose table upload does both):
+ * it may be captured into a graph.
+ * Limits (each violation is BRN_ERR_INVALID_ARG with the prefix "flash attention splitkv:" and a message naming the limit, checked before
+ * the device): every limit of brn_flash_attention_gqa_forward without a bias; 0 <= kv_splits <= 1024; workspace not NULL and
+ * workspace_floats large enough when S > 1 (the message names the float count needed); batch * kv_heads * ceil(G * seq_q / 64) * S < 2^31;
+ * y, lse and workspace overlap neither each other nor an input; BRN_MEM_DEVICE pointers 16-byte aligned.
+ * Not provided: a bias; packed or paged K / V; 16-bit tensors at the boundary; a split for the four older entries. */
+brn_status brn_flash_attention_splitkv_plan(int batch, int seq_q, int seq_kv, int heads, int kv_heads, int head_dim,
+                                            int kv_splits, int* splits_out, int* tiles_per_split_out,
+                                            size_t* workspace_floats_out);
+brn_status brn_flash_attention_splitkv_forward(const float* q, const float* k, const float* v,
+                                               int batch, int seq_q, int seq_kv, int heads, int kv_heads, int head_dim,
+                                               int layout, int causal, float scale, int kv_splits,
+                                               float* y, float* lse, float* workspace, size_t workspace_floats,
+                                               brn_mem loc, int device_ordinal, void* stream);
 /* PatchMerging::forward (swin.rs:491-527): x [B,H*W,C] -> [B, ceil(H/2)*ceil(W/2), 2C]. */
 brn_status brn_patch_merging_forward(const float* x, int B, int H, int W, int C, const float* norm_g,
                                      const float* norm_b, const float* reduction_w, float* y, brn_mem loc,

@@ -138,6 +138,14 @@ extern "C" {
                                               cu_seqlens_kv: *const c_int, n_seqs: c_int, heads: c_int, kv_heads: c_int, head_dim: c_int,
                                               window_left: c_int, window_right: c_int, scale: c_float, y: *mut c_float, loc: c_int,
                                               device_ordinal: c_int, stream: *mut c_void) -> c_int;
+    pub fn brn_flash_attention_splitkv_plan(batch: c_int, seq_q: c_int, seq_kv: c_int, heads: c_int, kv_heads: c_int, head_dim: c_int,
+                                            kv_splits: c_int, splits_out: *mut c_int, tiles_per_split_out: *mut c_int,
+                                            workspace_floats_out: *mut usize) -> c_int;
+    pub fn brn_flash_attention_splitkv_forward(q: *const c_float, k: *const c_float, v: *const c_float, batch: c_int, seq_q: c_int,
+                                               seq_kv: c_int, heads: c_int, kv_heads: c_int, head_dim: c_int, layout: c_int, causal: c_int,
+                                               scale: c_float, kv_splits: c_int, y: *mut c_float, lse: *mut c_float,
+                                               workspace: *mut c_float, workspace_floats: usize, loc: c_int, device_ordinal: c_int,
+                                               stream: *mut c_void) -> c_int;
     pub fn brn_patch_merging_forward(x: *const c_float, b: c_int, h: c_int, w: c_int, c: c_int, norm_g: *const c_float,
                                      norm_b: *const c_float, reduction_w: *const c_float, y: *mut c_float, loc: c_int,
                                      device_ordinal: c_int, stream: *mut c_void) -> c_int;

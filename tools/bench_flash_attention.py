@@ -33,7 +33,16 @@ Each record says whether the two sides returned the same bits.
             call uploads its workgroup table through a temporary and synchronises the stream, which the event pair around it sees
 The packed call's cu_seqlens are host arrays, as the entry requires.
 
-  python tools/bench_flash_attention.py [--bias | --gqa | --varlen] [--row N] [--mode f32|bf16|f16] [--json PATH]"""
+--splitkv times brn_flash_attention_splitkv_forward in the same alternating style (all sides of a row take turns in each of the 5 rounds),
+modes bf16 and f32, at 32 / 8 heads of 128: the decode rows 16 x 1 / 4096, 1 x 1 / 4096, 1 x 1 / 32768, 1 x 1 / 65536, the causal row
+1 x 8 / 16384 and 64 x 1 / 4096, whose unsplit grid is already 512 workgroups.  Sides per row: brn_flash_attention_gqa_forward (the
+baseline) and the new entry at kv_splits 1, 2, 4, 8, 16, 32, 64 and 0 (the library's rule); the timed new call includes the combine
+launch.  Both sides are raw library calls on preallocated device tensors (y, lse and the workspace are allocated once per side, outside
+the timed calls), so an event pair sees the library call and nothing of a wrapper.  Per record: the S each side really used, the best
+explicit side, whether the rule's median lies inside that side's round spread, and whether the rule is slower than the gqa call beyond
+the gqa call's round spread.  Without --json the records go to profiles/flash_attention_splitkv_bench.json.
+
+  python tools/bench_flash_attention.py [--bias | --gqa | --varlen | --splitkv] [--row N] [--mode f32|bf16|f16] [--json PATH]"""
 import argparse
 import json
 import os
@@ -51,6 +60,12 @@ VARLEN_WINDOW_ROW, VARLEN_WINDOWS = (1, 16384, 16384, 32, 8, 128), (1024, 4096)
 VARLEN_RAGGED = ([128 * n for n in (1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64, 64, 32, 8, 1)], 32, 8, 128)      # lengths, heads, kv_heads, head_dim
 VARLEN_UNIFORM_ROWS = [(4, 4096, 4096, 32, 8, 128), (1, 4096, 4096, 32, 8, 128), (4, 2048, 2048, 32, 8, 64)]
 VARLEN_GROUPS = ["windows", "ragged", "uniform"]
+# (batch, seq_q, seq_kv, heads, kv_heads, head_dim, causal)
+SPLITKV_ROWS = [(16, 1, 4096, 32, 8, 128, 0), (1, 1, 4096, 32, 8, 128, 0), (1, 1, 32768, 32, 8, 128, 0), (1, 1, 65536, 32, 8, 128, 0),
+                (1, 8, 16384, 32, 8, 128, 1), (64, 1, 4096, 32, 8, 128, 0)]
+SPLITKV_SPLITS = [1, 2, 4, 8, 16, 32, 64, 0]
+SPLITKV_MODES = ["bf16", "f32"]
+SPLITKV_JSON = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "flash_attention_splitkv_bench.json")
 HBM_BYTES_PER_S = 8.0e12
 MODES = ["f32", "bf16", "f16"]
 WARMUP, TIMED = 5, 20
@@ -314,11 +329,76 @@ def bench_varlen(group, mode):
     return out
 
 
+def bench_splitkv(row, mode):
+    import torch
+    import candle_birefnet_amd as cb
+    from candle_birefnet_amd import ops
+    lib = cb._ffi.lib
+    batch, seq_q, seq_kv, heads, kv_heads, hd, causal = row
+    g = torch.Generator(device="cuda").manual_seed(1)
+    q = torch.randn(batch, seq_q, heads, hd, device="cuda", generator=g)
+    k, v = (torch.randn(batch, seq_kv, kv_heads, hd, device="cuda", generator=g) for _ in range(2))
+    stream = torch.cuda.current_stream().cuda_stream
+    R = batch * heads * seq_q
+    yg = torch.empty_like(q)
+
+    def gqa():
+        cb._ffi.check(lib.brn_flash_attention_gqa_forward(q.data_ptr(), k.data_ptr(), v.data_ptr(), batch, seq_q, seq_kv, heads, kv_heads, hd, 0, causal, None, 0, 0.0,
+                                                          yg.data_ptr(), 1, 0, stream))
+        return yg
+
+    def split_side(ks):
+        S, tps, need = ops.flash_attention_splitkv_plan(batch, seq_q, seq_kv, heads, kv_heads, hd, ks)
+        y, lse, ws = torch.empty_like(q), torch.empty(R, device="cuda"), torch.empty(max(need, 4), device="cuda")
+
+        def fn():
+            cb._ffi.check(lib.brn_flash_attention_splitkv_forward(q.data_ptr(), k.data_ptr(), v.data_ptr(), batch, seq_q, seq_kv, heads, kv_heads, hd, 0, causal, 0.0,
+                                                                  ks, y.data_ptr(), lse.data_ptr(), ws.data_ptr(), need, 1, 0, stream))
+            return y
+        return fn, S, tps
+
+    out = []
+    ops.set_compute(mode)
+    try:
+        sides = [split_side(ks) for ks in SPLITKV_SPLITS]
+        t = _time_alternating([gqa] + [s[0] for s in sides])
+        tg, ts = t[0], t[1:]
+        assert all(bool(torch.isfinite(x[4]).all()) for x in t)
+        G = heads // kv_heads
+        rec = {"batch": batch, "seq_q": seq_q, "seq_kv": seq_kv, "heads": heads, "kv_heads": kv_heads, "head_dim": hd, "mode": mode, "causal": causal,
+               "base_workgroups": batch * kv_heads * ((G * seq_q + 63) // 64), "kv_tiles": (seq_kv + 63) // 64}
+        rec.update(_side("gqa", tg))
+        rec["splitkv"] = []
+        for ks, (_, S, tps), tt in zip(SPLITKV_SPLITS, sides, ts):
+            e = {"kv_splits": ks, "S": S, "tiles_per_split": tps, "max_abs_diff_vs_gqa": float((tt[4] - tg[4]).abs().max())}
+            e.update(_side("split", tt))
+            rec["splitkv"].append(e)
+        rec["kv_splits_1_same_bits_as_gqa"] = bool(torch.equal(ts[0][4], tg[4]))
+        explicit = rec["splitkv"][:-1]
+        best, auto = min(explicit, key=lambda e: e["split_ms_median"]), rec["splitkv"][-1]
+        rec["best_explicit_kv_splits"] = best["kv_splits"]
+        rec["auto_S"] = auto["S"]
+        rec["auto_inside_best_round_spread"] = bool(auto["split_ms_median"] <= best["split_round_medians"][1])
+        rec["auto_slower_than_gqa_beyond_spread"] = bool(auto["split_ms_median"] > tg[3])
+        rec["gqa_over_auto"] = round(tg[0] / auto["split_ms_median"], 2)
+        out.append(rec)
+        print(f"{batch:3d} x {seq_q:2d} / {seq_kv:5d} x {heads} / {kv_heads} x {hd} {mode:4s} causal {causal}: gqa {tg[0]:8.4f} ms [{tg[2]:.4f} .. {tg[3]:.4f}] | "
+              + " | ".join(f"s{e['kv_splits']}(S {e['S']}) {e['split_ms_median']:.4f} [{e['split_round_medians'][0]:.4f} .. {e['split_round_medians'][1]:.4f}]" for e in rec["splitkv"])
+              + f" | best explicit {best['kv_splits']}, rule S {auto['S']}, inside its spread {rec['auto_inside_best_round_spread']}, gqa / rule {rec['gqa_over_auto']:.2f}, "
+                f"kv_splits 1 same bits {rec['kv_splits_1_same_bits_as_gqa']}", flush=True)
+    finally:
+        ops.set_compute("f32")
+    del q, k, v
+    torch.cuda.empty_cache()
+    return out
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--bias", action="store_true", help="time brn_flash_attention_bias_forward beside the bias-free call and torch + bias")
     ap.add_argument("--gqa", action="store_true", help="time brn_flash_attention_gqa_forward beside the older entries on repeated K / V (and a -inf mask bias)")
     ap.add_argument("--varlen", action="store_true", help="time brn_flash_attention_varlen_forward: windows, a ragged pack, a uniform pack, beside the gqa entry")
+    ap.add_argument("--splitkv", action="store_true", help="time brn_flash_attention_splitkv_forward at kv_splits 1 .. 64 and 0 beside the gqa entry")
     ap.add_argument("--row", type=int, choices=range(len(BIAS_ROWS)))
     ap.add_argument("--mode", choices=MODES)
     ap.add_argument("--json", help="write the records to this file")
@@ -327,17 +407,20 @@ if __name__ == "__main__":
     if cb.device_count() < 1:
         sys.exit("no HIP device: nothing is measured")
     recs = []
-    if a.bias + a.gqa + a.varlen > 1:
-        sys.exit("--bias, --gqa and --varlen are separate tables: one at a time")
-    rows = BIAS_ROWS if a.bias else GQA_ROWS if a.gqa else VARLEN_GROUPS if a.varlen else ROWS
+    if a.bias + a.gqa + a.varlen + a.splitkv > 1:
+        sys.exit("--bias, --gqa, --varlen and --splitkv are separate tables: one at a time")
+    rows = BIAS_ROWS if a.bias else GQA_ROWS if a.gqa else VARLEN_GROUPS if a.varlen else SPLITKV_ROWS if a.splitkv else ROWS
     if a.row is not None and a.row >= len(rows):
         sys.exit(f"--row {a.row}: only {len(rows)} rows in this table")
     for row in (rows if a.row is None else [rows[a.row]]):
-        for mode in (MODES if a.mode is None else [a.mode]):
-            recs += bench_bias(row, mode) if a.bias else bench_gqa(row, mode) if a.gqa else bench_varlen(row, mode) if a.varlen else bench(row, mode)
+        for mode in ((SPLITKV_MODES if a.splitkv else MODES) if a.mode is None else [a.mode]):
+            recs += (bench_bias(row, mode) if a.bias else bench_gqa(row, mode) if a.gqa else bench_varlen(row, mode) if a.varlen else
+                     bench_splitkv(row, mode) if a.splitkv else bench(row, mode))
+    if a.splitkv and not a.json:
+        a.json = SPLITKV_JSON
     if a.json:
         with open(a.json, "w") as f:
-            alternating = a.gqa or a.varlen
-            json.dump({"tool": "tools/bench_flash_attention.py" + (" --bias" if a.bias else " --gqa" if a.gqa else " --varlen" if a.varlen else ""),
+            alternating = a.gqa or a.varlen or a.splitkv
+            json.dump({"tool": "tools/bench_flash_attention.py" + (" --bias" if a.bias else " --gqa" if a.gqa else " --varlen" if a.varlen else " --splitkv" if a.splitkv else ""),
                        "warmup": GQA_WARMUP if alternating else WARMUP, "timed": GQA_ROUNDS * GQA_TIMED if alternating else TIMED, "rows": recs}, f, indent=1)
             f.write("\n")
