@@ -6,6 +6,7 @@
 #include "../brn_kernels.h"
 #include "gemm_common.h"
 #include "gemm_split_stages.h"
+#include "gemm_conv_halo.h"
 
 namespace brn {
 
@@ -588,6 +589,8 @@ static hipError_t launch_split_tile(const GemmParams& p, int cfg, hipStream_t s)
 template <int NP>
 static hipError_t launch_split_np(const GemmParams& p, int cfg, hipStream_t s) {
     if (gemm_split_is_ws(cfg)) return launch_split_ws<NP>(p, s);
+    if constexpr (NP == 2)      // a 4-wave plan of a 3x3 conv: the halo-staged kernel (gemm_conv_halo.h), whatever the plan's tile
+        if (conv_halo_eligible(p)) return p.h2 ? launch_conv_halo<true>(p, s) : launch_conv_halo<false>(p, s);
     if (p.h2) {
         if constexpr (NP == 2) return launch_split_tile<2, true>(p, cfg, s);
         else return hipErrorInvalidValue;
