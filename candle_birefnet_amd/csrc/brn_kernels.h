@@ -218,6 +218,15 @@ struct FlashAttentionParams {
     float* o_part;                // S > 1: [S][R][head_dim] normalised partial outputs, R = batch * heads * seq_q, row r = (b * heads + h) * seq_q + i; null when S == 1
     float* lse2_part;             // S > 1: [S][R] m + log2(l) of each partial (-inf: no visible key in the split); null when S == 1
     float* lse;                   // [R] ln sum_j exp(scale q . k_j) over the row's visible keys, or null = not wanted
+    // brn_flash_attention_paged_forward; block_table == null = the kernels above, untouched.  With a table: the split form (kv_splits >= 1,
+    // seq_kv = max_kv_len sizes the grid and the split) with K / V in pages: k, v [n_pages, page_size, kv_heads, head_dim] (kv_ss = kv_heads *
+    // head_dim, kv_sh = head_dim, kv_sb = 0), each workgroup's seq_kv and causal_off its own sequence's, from kv_lens.  Both arrays hold
+    // UNVALIDATED device data: a length is used as min(max(len, 0), seq_kv), a page number as min(max(page, 0), n_pages - 1)
+    const int* block_table;       // [batch][max_pages]: key j of batch entry b is row j % page_size of page block_table[b][j / page_size]
+    const int* kv_lens;           // [batch]
+    long page_stride;             // elements between two pages: page_size * kv_heads * head_dim
+    int page_log2;                // log2(page_size), 4 .. 8
+    int n_pages, max_pages;       // max_pages * page_size >= seq_kv
 };
 hipError_t launch_flash_attention(const FlashAttentionParams& p, hipStream_t s);
 

@@ -279,7 +279,8 @@ brn_status brn_attention_forward(const float* q, const float* k, const float* v,
     });
 }
 
-// brn_flash_attention_forward, brn_flash_attention_bias_forward, brn_flash_attention_gqa_forward and brn_flash_attention_splitkv_forward:
+// brn_flash_attention_forward, brn_flash_attention_bias_forward, brn_flash_attention_gqa_forward and brn_flash_attention_splitkv_forward
+// (brn_flash_attention_paged_forward takes the size checks):
 // one set of checks, one way to fill the kernels' arguments.  who = the message prefix; with_bias = an entry with a bias, whose bias /
 // n_bias are checked (the bias-free entries pass null / 0); gqa = a grouped entry, whose kv_heads is checked (the other two pass heads)
 // and whose causal mask ends at the last key.
@@ -441,22 +442,22 @@ brn_status brn_flash_attention_varlen_forward(const float* q, const float* k, co
 // The split over keys.  brn_flash_split_plan.h decides S and tps for both entries below, from the integers alone; the checks the gqa entry
 // makes without a bias are flash_attention_check's, under this entry's prefix.
 static const char* const SPLITKV = "flash attention splitkv";
-static void splitkv_check_splits(int kv_splits) {
+static void splitkv_check_splits(const char* who, int kv_splits) {
     if (kv_splits < 0 || kv_splits > FA_SPLIT_MAX)
-        fail(BRN_ERR_INVALID_ARG, "%s: kv_splits %d unsupported (0 <= kv_splits <= %d; 0 = the library's rule)", SPLITKV, kv_splits, FA_SPLIT_MAX);
+        fail(BRN_ERR_INVALID_ARG, "%s: kv_splits %d unsupported (0 <= kv_splits <= %d; 0 = the library's rule)", who, kv_splits, FA_SPLIT_MAX);
 }
-static FaSplitPlan splitkv_plan_checked(int batch, int seq_q, int seq_kv, int heads, int kv_heads, int head_dim, int kv_splits) {
+static FaSplitPlan splitkv_plan_checked(const char* who, int batch, int seq_q, int seq_kv, int heads, int kv_heads, int head_dim, int kv_splits) {
     const FaSplitPlan pl = flash_split_plan(batch, seq_q, seq_kv, heads, kv_heads, head_dim, kv_splits);
     if (pl.base * pl.S > 0x7fffffffLL)
-        fail(BRN_ERR_INVALID_ARG, "%s: %lld workgroups x %d splits too large (batch * kv_heads * ceil(G * seq_q / 64) * S < 2^31)", SPLITKV, pl.base, pl.S);
+        fail(BRN_ERR_INVALID_ARG, "%s: %lld workgroups x %d splits too large (batch * kv_heads * ceil(G * seq_q / 64) * S < 2^31)", who, pl.base, pl.S);
     return pl;
 }
 brn_status brn_flash_attention_splitkv_plan(int batch, int seq_q, int seq_kv, int heads, int kv_heads, int head_dim, int kv_splits, int* splits_out,
                                             int* tiles_per_split_out, size_t* workspace_floats_out) {
     return guarded([&] {
         flash_attention_check_sizes(SPLITKV, true, batch, seq_q, seq_kv, heads, kv_heads, head_dim);
-        splitkv_check_splits(kv_splits);
-        const FaSplitPlan pl = splitkv_plan_checked(batch, seq_q, seq_kv, heads, kv_heads, head_dim, kv_splits);
+        splitkv_check_splits(SPLITKV, kv_splits);
+        const FaSplitPlan pl = splitkv_plan_checked(SPLITKV, batch, seq_q, seq_kv, heads, kv_heads, head_dim, kv_splits);
         if (splits_out) *splits_out = pl.S;
         if (tiles_per_split_out) *tiles_per_split_out = pl.tps;
         if (workspace_floats_out) *workspace_floats_out = pl.workspace_floats;
@@ -471,8 +472,8 @@ brn_status brn_flash_attention_splitkv_forward(const float* q, const float* k, c
         // what the plan entry checks first (a buffer size below means something only once the sizes and the splits are sound), then
         // every check of the gqa entry without a bias
         flash_attention_check_sizes(who, true, batch, seq_q, seq_kv, heads, kv_heads, head_dim);
-        splitkv_check_splits(kv_splits);
-        const FaSplitPlan pl = splitkv_plan_checked(batch, seq_q, seq_kv, heads, kv_heads, head_dim, kv_splits);
+        splitkv_check_splits(SPLITKV, kv_splits);
+        const FaSplitPlan pl = splitkv_plan_checked(SPLITKV, batch, seq_q, seq_kv, heads, kv_heads, head_dim, kv_splits);
         flash_attention_check(who, false, true, q, k, v, batch, seq_q, seq_kv, heads, kv_heads, head_dim, layout, causal, nullptr, 0, scale, y, loc);
         const size_t nq = (size_t)batch * heads * seq_q * head_dim, nkv = (size_t)batch * kv_heads * seq_kv * head_dim;
         const size_t R = (size_t)batch * heads * seq_q;
@@ -495,6 +496,84 @@ brn_status brn_flash_attention_splitkv_forward(const float* q, const float* k, c
         ensure_device(device);
         Staging st(stream, loc);
         FlashAttentionParams p = flash_attention_params(st, q, k, v, batch, seq_q, seq_kv, heads, kv_heads, head_dim, layout, causal, nullptr, 0, scale, y);
+        p.kv_splits = pl.S; p.tiles_per_split = pl.tps;
+        if (lse) p.lse = st.out(lse, R);
+        if (need) {
+            p.o_part = st.out(ws, need);
+            p.lse2_part = p.o_part + (size_t)pl.S * R * head_dim;
+        }
+        BRN_HIP(launch_flash_attention(p, (hipStream_t)stream));
+        st.finish();
+    });
+}
+
+// The split over keys with K / V in the pages of a pool and per-sequence lengths on the device.  The plan is the split entry's at
+// seq_kv = max_kv_len.  block_table and kv_lens are never read on the host for BRN_MEM_DEVICE: nothing here depends on their content, and
+// the call allocates nothing and does not synchronise (Staging has nothing to stage), so it may be captured into a graph.
+brn_status brn_flash_attention_paged_forward(const float* q, const float* k_pages, const float* v_pages, const int* block_table, const int* kv_lens, int batch,
+                                             int seq_q, int max_kv_len, int heads, int kv_heads, int head_dim, int n_pages, int page_size, int max_pages,
+                                             int layout, int causal, float scale, int kv_splits, float* y, float* lse, float* workspace,
+                                             size_t workspace_floats, brn_mem loc, int device, void* stream) {
+    return guarded([&] {
+        const char* who = "flash attention paged";
+        if (!q || !k_pages || !v_pages || !y) fail(BRN_ERR_INVALID_ARG, "%s: null q, k_pages, v_pages or y", who);
+        if (!block_table || !kv_lens) fail(BRN_ERR_INVALID_ARG, "%s: null block_table or kv_lens", who);
+        int page_log2 = 0;
+        while ((1 << page_log2) < page_size && page_log2 < 9) ++page_log2;
+        if (page_size < 16 || page_size > 256 || (1 << page_log2) != page_size)
+            fail(BRN_ERR_INVALID_ARG, "%s: page_size %d unsupported (page_size must be 16, 32, 64, 128 or 256)", who, page_size);
+        if (n_pages < 1 || max_pages < 1) fail(BRN_ERR_INVALID_ARG, "%s: n_pages %d, max_pages %d unsupported (n_pages >= 1, max_pages >= 1)", who, n_pages, max_pages);
+        if ((long long)n_pages * page_size > 0x7fffffffLL)
+            fail(BRN_ERR_INVALID_ARG, "%s: n_pages %d of page_size %d too large (n_pages * page_size < 2^31)", who, n_pages, page_size);
+        if (max_kv_len < 1 || max_kv_len > 65536 || max_kv_len > (long long)max_pages * page_size)
+            fail(BRN_ERR_INVALID_ARG, "%s: max_kv_len %d unsupported with max_pages %d of page_size %d (1 <= max_kv_len <= min(65536, max_pages * page_size))",
+                 who, max_kv_len, max_pages, page_size);
+        // every limit of the split entry with max_kv_len in the place of seq_kv, but for its causal one (a per-sequence matter the kernels define)
+        flash_attention_check_sizes(who, true, batch, seq_q, max_kv_len, heads, kv_heads, head_dim);
+        splitkv_check_splits(who, kv_splits);
+        const FaSplitPlan pl = splitkv_plan_checked(who, batch, seq_q, max_kv_len, heads, kv_heads, head_dim, kv_splits);
+        if (layout != BRN_ATTN_BSHD && layout != BRN_ATTN_BHSD) fail(BRN_ERR_INVALID_ARG, "%s: layout %d unknown (layout must be 0 = BSHD or 1 = BHSD)", who, layout);
+        if (causal != 0 && causal != 1) fail(BRN_ERR_INVALID_ARG, "%s: causal %d (causal must be 0 or 1)", who, causal);
+        if (!scale_arg_ok(scale)) fail(BRN_ERR_INVALID_ARG, "%s: scale must be finite and >= 0 (0 = head_dim^-0.5)", who);
+        const size_t nq = (size_t)batch * heads * seq_q * head_dim, npool = (size_t)n_pages * page_size * kv_heads * head_dim;
+        const size_t R = (size_t)batch * heads * seq_q, ntab = (size_t)batch * max_pages;
+        const size_t need = pl.S > 1 ? pl.workspace_floats : 0;
+        if (need && (!workspace || workspace_floats < need))
+            fail(BRN_ERR_INVALID_ARG, "%s: workspace %s for %d splits (it must hold S * batch * heads * seq_q * (head_dim + 1) = %zu floats, workspace_floats %zu)",
+                 who, workspace ? "too small" : "is NULL", pl.S, need, workspace_floats);
+        float* const ws = need ? workspace : nullptr;
+        // sizes in 4-byte elements: the table and the lengths are ints
+        const struct { const void* p; size_t n; } ins[] = {{q, nq}, {k_pages, npool}, {v_pages, npool}, {block_table, ntab}, {kv_lens, (size_t)batch}};
+        const struct { const float* p; size_t n; const char* name; } outs[] = {{y, nq, "y"}, {lse, lse ? R : 0, "lse"}, {ws, need, "workspace"}};
+        for (int a = 0; a < 3; ++a) {
+            if (!outs[a].p) continue;
+            for (const auto& in : ins)
+                if (floats_overlap(static_cast<const float*>(in.p), in.n, outs[a].p, outs[a].n)) fail(BRN_ERR_INVALID_ARG, "%s: %s must not overlap an input", who, outs[a].name);
+            for (int b = 0; b < a; ++b)
+                if (outs[b].p && floats_overlap(outs[b].p, outs[b].n, outs[a].p, outs[a].n))
+                    fail(BRN_ERR_INVALID_ARG, "%s: %s and %s must not overlap", who, outs[b].name, outs[a].name);
+        }
+        if (loc == BRN_MEM_DEVICE && !all_aligned16({q, k_pages, v_pages, y, lse, ws}))
+            fail(BRN_ERR_INVALID_ARG, "%s: device q, k_pages, v_pages, y, lse and workspace must be 16-byte aligned", who);
+        if (loc == BRN_MEM_DEVICE && ((reinterpret_cast<uintptr_t>(block_table) | reinterpret_cast<uintptr_t>(kv_lens)) & 3))
+            fail(BRN_ERR_INVALID_ARG, "%s: device block_table and kv_lens must be 4-byte aligned", who);
+        ensure_device(device);
+        Staging st(stream, loc);
+        FlashAttentionParams p{};
+        p.q = st.in(q, nq); p.k = st.in(k_pages, npool); p.v = st.in(v_pages, npool);
+        p.block_table = reinterpret_cast<const int*>(st.in(reinterpret_cast<const float*>(block_table), ntab));
+        p.kv_lens = reinterpret_cast<const int*>(st.in(reinterpret_cast<const float*>(kv_lens), (size_t)batch));
+        p.y = st.out(y, nq);
+        p.batch = batch; p.heads = heads; p.kv_heads = kv_heads; p.seq_q = seq_q; p.seq_kv = max_kv_len; p.head_dim = head_dim;
+        const long d = head_dim;
+        if (layout == BRN_ATTN_BSHD) { p.q_ss = heads * d; p.q_sh = d; p.q_sb = seq_q * p.q_ss; }
+        else { p.q_ss = d; p.q_sh = seq_q * d; p.q_sb = heads * p.q_sh; }
+        // a key's row inside a page; the page comes from the table (no batch stride)
+        p.kv_ss = kv_heads * d; p.kv_sh = d; p.kv_sb = 0;
+        p.page_stride = (long)page_size * p.kv_ss; p.page_log2 = page_log2; p.n_pages = n_pages; p.max_pages = max_pages;
+        p.causal = causal; p.causal_off = 0;       // each workgroup's own: len_b - seq_q
+        p.scale = scale_or_default(scale, head_dim);
+        p.s16 = attention_op_s16();
         p.kv_splits = pl.S; p.tiles_per_split = pl.tps;
         if (lse) p.lse = st.out(lse, R);
         if (need) {

@@ -65,6 +65,17 @@
 // heads + head) * seq_q + query, 64-bit offsets) when S > 1, straight into y (and lse = ln 2 * that) when S == 1; a row with l == 0 gets
 // 0 and -inf, selected, never computed as 0 * inf.  flash_split_combine_kernel then merges the S partials of a row in the order
 // s = 0 .. S - 1.  No atomics; a row's bits depend on its (batch entry, query head), seq_kv, the mask and tps alone.  DESIGN.md 3.2h.
+// FA_PAGED (brn_flash_attention_paged_forward): the fifth form, FA_SPLIT with K / V in the pages of a pool and a length per batch entry that
+// lives on the device.  The grid and the split are FA_SPLIT's at seq_kv = max_kv_len.  A workgroup reads its batch entry's kv_lens[b] (one
+// scalar load), clamps it to 0 .. max_kv_len, and from there on IS an FA_SPLIT workgroup at seq_kv = len (fa_params): limit, causal_off =
+// len - seq_q (it may be negative: rows with no visible key), the tile count and the empty decision all follow.  load_tile finds key t in
+// row t % page_size of page block_table[b][t / page_size]: t is clamped to len - 1 BEFORE the table is indexed, so no entry at or past
+// ceil(len / page_size) is read, the page number is clamped to 0 .. n_pages - 1 before it becomes an address, and a row at or past len is
+// replaced by zeros as the other forms replace a row past seq_kv.  The table entries of tile kt + 2 are loaded (vector loads, a thread's
+// own keys: NI entries in the f32 kernel, one per key pair in the 16-bit kernel) just before the K / V loads of tile kt + 1 are issued, so
+// a tile's entries are in registers a whole tile before its loads need them and the table's latency is paid once, in the prologue.
+// A row with no visible key at all (len 0, or causal with query + len - seq_q < 0) is empty in every split: fa_finish_split gives 0 / -inf
+// as before, and flash_split_combine_kernel<true> selects y = 0, lse = -inf for it without forming -inf - -inf.  DESIGN.md 3.2i.
 #include "../brn_kernels.h"
 #include "../brn_flash_varlen_plan.h"
 #include "attention_mfma.h"
@@ -80,8 +91,10 @@ static_assert(FA_BQ == FA_VARLEN_ROWS && FA_T == FA_VARLEN_ROWS, "the records of
 constexpr int FA_VT_LD = 72;         // 16-bit kernel: elements per LDS row of V^T (36 dwords: conflict-free 8-byte reads, 2-way 4-byte writes)
 
 // the three forms of the kernels: a workgroup per (batch entry, head, 64 queries); per (batch entry, K / V head, 64 packed rows); per
-// (record of a packed batch, K / V head), with a window; per (batch entry, K / V head, 64 packed rows, split over keys)
-enum FaForm { FA_PLAIN = 0, FA_PACKED = 1, FA_VARLEN = 2, FA_SPLIT = 3 };
+// (record of a packed batch, K / V head), with a window; per (batch entry, K / V head, 64 packed rows, split over keys); the same over pages
+enum FaForm { FA_PLAIN = 0, FA_PACKED = 1, FA_VARLEN = 2, FA_SPLIT = 3, FA_PAGED = 4 };
+// the forms whose walk is one split's range and whose finish is fa_finish_split (FA_PAGED: FA_SPLIT at the workgroup's own seq_kv, K / V in pages)
+constexpr bool fa_splits(FaForm f) { return f == FA_SPLIT || f == FA_PAGED; }
 
 // which (batch entry, head, query tile) this workgroup owns, where its operands start and how many K / V tiles it walks
 struct FaBlock {
@@ -161,7 +174,7 @@ __device__ __forceinline__ FaSplit fa_split_of(const FlashAttentionParams& p) {
 }
 template <bool BIAS, FaForm FORM>
 __device__ __forceinline__ FaBlock fa_block(const FlashAttentionParams& p) {
-    if constexpr (FORM == FA_SPLIT) return fa_block_split(p);
+    if constexpr (fa_splits(FORM)) return fa_block_split(p);
     if constexpr (FORM == FA_PACKED) return fa_block_gqa<BIAS>(p, blockIdx.x);
     const int nqt = (p.seq_q + FA_BQ - 1) / FA_BQ;
     // not causal: the query tiles of a (batch entry, head) are neighbours in the grid (they walk the same K and V).  Causal: tile qt walks
@@ -222,7 +235,7 @@ __device__ __forceinline__ FaLane fa_lane(const FlashAttentionParams& p, const F
         const int qa = (blk.q0 + min(wave * 16, blk.rem)) / blk.G, qb = (blk.q0 + min(wave * 16 + 15, blk.rem)) / blk.G;
         r.wave_row0 = wr < 0 ? p.seq_kv : min(p.seq_kv, qa + p.causal_off + wr + 1);
         r.wave_lo = wl < 0 ? 0 : max(0, qb + p.causal_off - wl);
-    } else if constexpr (FORM == FA_PACKED || FORM == FA_SPLIT) {             // (FA_SPLIT has no bias: blk.bias is null and never read)
+    } else if constexpr (FORM == FA_PACKED || fa_splits(FORM)) {              // (FA_SPLIT, FA_PAGED have no bias: blk.bias is null and never read)
         const int lr = wave * 16 + li;
         const int row = blk.q0 + min(lr, blk.rem);
         const int query = row / blk.G, head = blk.h0 + (row - query * blk.G);
@@ -322,15 +335,31 @@ __device__ __forceinline__ bool fa_tile_masks(const FlashAttentionParams& p, int
 __device__ __forceinline__ bool fa_tile_masks_window(int key0, int wave_hi, int wave_lo) { return key0 + FA_T > wave_hi || key0 < wave_lo; }
 // FA_VARLEN: the workgroup's record, and the arguments with the record's sequence in place of the call's: seq_q, seq_kv, causal_off
 // (= off of the window; it may be negative where there is no window, and is then not read)
+// FA_PAGED: the arguments with the workgroup's own sequence length in place of max_kv_len.  kv_lens[b] is unvalidated device data: it is
+// clamped to 0 .. max_kv_len here and reaches nothing unclamped.  causal_off = len - seq_q may be negative (rows with no visible key)
 template <FaForm FORM>
 __device__ __forceinline__ FlashAttentionParams fa_params(const FlashAttentionParams& pa, FaVarlenRecord& rec) {
-    if constexpr (FORM != FA_VARLEN) return pa;
-    else {
+    if constexpr (FORM == FA_VARLEN) {
         rec = pa.plan[blockIdx.x / (unsigned)pa.kv_heads];           // wave-uniform
         FlashAttentionParams p = pa;
         p.seq_q = rec.len_q; p.seq_kv = rec.len_kv; p.causal_off = rec.len_kv - rec.len_q;
         return p;
-    }
+    } else if constexpr (FORM == FA_PAGED) {
+        FlashAttentionParams p = pa;
+        p.seq_kv = min(max(pa.kv_lens[fa_split_of(pa).b], 0), pa.seq_kv);       // workgroup-uniform: one scalar load
+        p.causal_off = pa.causal ? p.seq_kv - pa.seq_q : 0;
+        return p;
+    } else return pa;
+}
+// FA_PAGED: where key t (already clamped below the sequence's length) of the workgroup's batch entry lives: its table entry, and the
+// offset of its row from the K / V head's base in the pool (64-bit), the page number clamped into the pool
+struct FaPages { const int* table; long stride; int lg, mask, last; };
+__device__ __forceinline__ FaPages fa_pages_of(const FlashAttentionParams& p) {
+    return FaPages{p.block_table + (long)fa_split_of(p).b * p.max_pages, p.page_stride, p.page_log2, (1 << p.page_log2) - 1, p.n_pages - 1};
+}
+__device__ __forceinline__ int fa_page_entry(const FaPages& pg, int t) { return pg.table[t >> pg.lg]; }
+__device__ __forceinline__ long fa_page_row(const FaPages& pg, int entry, int t, long kv_ss) {
+    return (long)min(max(entry, 0), pg.last) * pg.stride + (long)(t & pg.mask) * kv_ss;
 }
 template <bool BIAS, FaForm FORM>
 __device__ __forceinline__ FaBlock fa_block_of(const FlashAttentionParams& p, const FaVarlenRecord& rec) {
@@ -393,7 +422,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
     const FlashAttentionParams p = fa_params<FORM>(pa, rec);
     const FaBlock blk = fa_block_of<BIAS, FORM>(p, rec);
     const FaLane ln = fa_lane<FORM>(p, blk, wave, li);
-    if constexpr (FORM == FA_SPLIT) {
+    if constexpr (fa_splits(FORM)) {
         // nothing to walk (workgroup-uniform, before the first barrier): the empty markers of the real rows
         if (blk.kt0 >= blk.nkt) {
             f32x4 z[D / 16];
@@ -415,11 +444,24 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
     }
     f32x4 kr[NI], vr[NI];
     f32x4 bn[FA_T / 16];                                   // BIAS: the bias of the tile in kr / vr, loaded with it
+    // FA_PAGED: the table entries of the thread's NI keys of a tile: pn as fetch_pages loads them, a tile ahead; pe those load_tile uses
+    FaPages pgs{};
+    int pe[NI], pn[NI];
+    auto fetch_pages = [&](int key0) {
+#pragma unroll
+        for (int i = 0; i < NI; ++i) pn[i] = fa_page_entry(pgs, min(key0 + (tid + i * FA_THREADS) / (D / 4), p.seq_kv - 1));
+    };
+    auto use_pages = [&]() {
+#pragma unroll
+        for (int i = 0; i < NI; ++i) pe[i] = pn[i];
+    };
     auto load_tile = [&](int key0) {
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
             const int idx = tid + i * FA_THREADS, t = key0 + idx / (D / 4), c4 = (idx % (D / 4)) * 4;
-            const long src = min(t, p.seq_kv - 1) * p.kv_ss + c4;
+            long src;
+            if constexpr (FORM == FA_PAGED) src = fa_page_row(pgs, pe[i], min(t, p.seq_kv - 1), p.kv_ss) + c4;
+            else src = min(t, p.seq_kv - 1) * p.kv_ss + c4;
             kr[i] = *reinterpret_cast<const f32x4*>(blk.k + src);
             vr[i] = *reinterpret_cast<const f32x4*>(blk.v + src);
             if (t >= p.seq_kv) { kr[i] = f32x4{0.f, 0.f, 0.f, 0.f}; vr[i] = kr[i]; }
@@ -432,8 +474,10 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
     float m = ATT_NEG, l = 0.f;
     const float sc2 = p.scale * ATT_LOG2E;
 
-    const int kt_first = (FORM == FA_VARLEN || FORM == FA_SPLIT) ? blk.kt0 : 0;
+    const int kt_first = (FORM == FA_VARLEN || fa_splits(FORM)) ? blk.kt0 : 0;
+    if constexpr (FORM == FA_PAGED) { pgs = fa_pages_of(p); fetch_pages(kt_first * FA_T); use_pages(); }
     load_tile(kt_first * FA_T);
+    if constexpr (FORM == FA_PAGED) fetch_pages((kt_first + 1) * FA_T);      // (a key past the sequence is clamped into it: a valid entry, not used)
     for (int kt = kt_first; kt < blk.nkt; ++kt) {
         __syncthreads();                                   // every wave is done reading the previous tile
 #pragma unroll
@@ -449,7 +493,10 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
 #pragma unroll
             for (int s = 0; s < FA_T / 16; ++s) st[s] = bn[s];
         }
-        if (kt + 1 < blk.nkt) load_tile((kt + 1) * FA_T);
+        if (kt + 1 < blk.nkt) {
+            if constexpr (FORM == FA_PAGED) { use_pages(); fetch_pages((kt + 2) * FA_T); }   // tile kt + 2's entries go out ahead of tile kt + 1's K / V
+            load_tile((kt + 1) * FA_T);
+        }
 #pragma unroll
         for (int s = 0; s < FA_T / 16; ++s) {
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -460,7 +507,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
         }
         float alpha;
         if constexpr (FORM == FA_VARLEN) alpha = fa_softmax_tile<true>(st, sc2, fa_tile_masks_window(kt * FA_T, ln.wave_row0, ln.wave_lo), kt * FA_T, g, ln.limit, m, l, ln.lo);
-        else if constexpr (FORM == FA_SPLIT) alpha = fa_softmax_tile<true>(st, sc2, fa_tile_masks(p, kt * FA_T, ln.wave_row0), kt * FA_T, g, ln.limit, m, l, 0);
+        else if constexpr (fa_splits(FORM)) alpha = fa_softmax_tile<true>(st, sc2, fa_tile_masks(p, kt * FA_T, ln.wave_row0), kt * FA_T, g, ln.limit, m, l, 0);
         else alpha = fa_softmax_tile(st, sc2, fa_tile_masks(p, kt * FA_T, ln.wave_row0), kt * FA_T, g, ln.limit, m, l);
 #pragma unroll
         for (int dt = 0; dt < ND; ++dt) o[dt] *= alpha;
@@ -475,7 +522,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
             }
         }
     }
-    if constexpr (FORM == FA_SPLIT) fa_finish_split<D>(p, blk, ln, g, o, l, m);
+    if constexpr (fa_splits(FORM)) fa_finish_split<D>(p, blk, ln, g, o, l, m);
     else fa_finish<ND, BIAS>(fa_lane_y<FORM>(p, blk, ln), g, o, l, m);
 }
 
@@ -498,7 +545,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
     const FlashAttentionParams p = fa_params<FORM>(pa, rec);
     const FaBlock blk = fa_block_of<BIAS, FORM>(p, rec);
     const FaLane ln = fa_lane<FORM>(p, blk, wave, li);
-    if constexpr (FORM == FA_SPLIT) {
+    if constexpr (fa_splits(FORM)) {
         // nothing to walk (workgroup-uniform, before the first barrier): the empty markers of the real rows
         if (blk.kt0 >= blk.nkt) {
             f32x4 z[D / 16];
@@ -519,6 +566,12 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
     const int s_lo = tid & 3, s_tp = (tid >> 2) & 31, s_hi = tid >> 7;
     f32x4 kr[NP][2], vr[NP][2];
     f32x4 bn[FA_T / 16];                                   // BIAS: the bias of the tile in kr / vr, loaded with it
+    // FA_PAGED: the table entry of the thread's key pair of a tile: pn as fetch_pages loads it, a tile ahead; pe the one load_tile uses.
+    // A page holds an even number of keys from an even key on, so the pair (and what a key past the sequence is clamped to) shares a page
+    FaPages pgs{};
+    int pe = 0, pn = 0;
+    auto fetch_pages = [&](int key0) { pn = fa_page_entry(pgs, min(key0 + s_tp * 2, p.seq_kv - 1)); };
+    auto use_pages = [&]() { pe = pn; };
     auto load_tile = [&](int key0) {
 #pragma unroll
         for (int ps = 0; ps < NP; ++ps) {
@@ -526,7 +579,9 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const int t = key0 + s_tp * 2 + u;
-                const long src = min(t, p.seq_kv - 1) * p.kv_ss + c4;
+                long src;
+                if constexpr (FORM == FA_PAGED) src = fa_page_row(pgs, pe, min(t, p.seq_kv - 1), p.kv_ss) + c4;
+                else src = min(t, p.seq_kv - 1) * p.kv_ss + c4;
                 kr[ps][u] = *reinterpret_cast<const f32x4*>(blk.k + src);
                 vr[ps][u] = *reinterpret_cast<const f32x4*>(blk.v + src);
                 if (t >= p.seq_kv) { kr[ps][u] = f32x4{0.f, 0.f, 0.f, 0.f}; vr[ps][u] = kr[ps][u]; }
@@ -540,8 +595,10 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
     float m = ATT_NEG, l = 0.f;
     const float sc2 = p.scale * ATT_LOG2E;
 
-    const int kt_first = (FORM == FA_VARLEN || FORM == FA_SPLIT) ? blk.kt0 : 0;
+    const int kt_first = (FORM == FA_VARLEN || fa_splits(FORM)) ? blk.kt0 : 0;
+    if constexpr (FORM == FA_PAGED) { pgs = fa_pages_of(p); fetch_pages(kt_first * FA_T); use_pages(); }
     load_tile(kt_first * FA_T);
+    if constexpr (FORM == FA_PAGED) fetch_pages((kt_first + 1) * FA_T);      // (a key past the sequence is clamped into it: a valid entry, not used)
     for (int kt = kt_first; kt < blk.nkt; ++kt) {
         __syncthreads();                                   // every wave is done reading the previous tile
 #pragma unroll
@@ -565,7 +622,10 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
 #pragma unroll
             for (int s = 0; s < FA_T / 16; ++s) st[s] = bn[s];
         }
-        if (kt + 1 < blk.nkt) load_tile((kt + 1) * FA_T);
+        if (kt + 1 < blk.nkt) {
+            if constexpr (FORM == FA_PAGED) { use_pages(); fetch_pages((kt + 2) * FA_T); }   // tile kt + 2's entries go out ahead of tile kt + 1's K / V
+            load_tile((kt + 1) * FA_T);
+        }
 #pragma unroll
         for (int s = 0; s < FA_T / 16; ++s) {
             const int key = s * 16 + li;
@@ -577,7 +637,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
         }
         float alpha;
         if constexpr (FORM == FA_VARLEN) alpha = fa_softmax_tile<true>(st, sc2, fa_tile_masks_window(kt * FA_T, ln.wave_row0, ln.wave_lo), kt * FA_T, g, ln.limit, m, l, ln.lo);
-        else if constexpr (FORM == FA_SPLIT) alpha = fa_softmax_tile<true>(st, sc2, fa_tile_masks(p, kt * FA_T, ln.wave_row0), kt * FA_T, g, ln.limit, m, l, 0);
+        else if constexpr (fa_splits(FORM)) alpha = fa_softmax_tile<true>(st, sc2, fa_tile_masks(p, kt * FA_T, ln.wave_row0), kt * FA_T, g, ln.limit, m, l, 0);
         else alpha = fa_softmax_tile(st, sc2, fa_tile_masks(p, kt * FA_T, ln.wave_row0), kt * FA_T, g, ln.limit, m, l);
 #pragma unroll
         for (int dt = 0; dt < ND; ++dt) o[dt] *= alpha;
@@ -589,7 +649,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
             for (int dt = 0; dt < ND; ++dt) o[dt] = att_mfma<F16>(att_vt_frag(Vt + (dt * 16 + li) * FA_VT_LD + g * 4, t), pf, o[dt]);
         }
     }
-    if constexpr (FORM == FA_SPLIT) fa_finish_split<D>(p, blk, ln, g, o, l, m);
+    if constexpr (fa_splits(FORM)) fa_finish_split<D>(p, blk, ln, g, o, l, m);
     else fa_finish<ND, BIAS>(fa_lane_y<FORM>(p, blk, ln), g, o, l, m);
 }
 
@@ -599,9 +659,14 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
 // (-inf) has w = exp2(-inf) = 0 exactly and its O_part is 0.  y has q's strides; every offset into the workspace is 64-bit.
 // A decode call has few rows and many splits, so the kernel is a chain of S load latencies unless the loads are issued together: the
 // partials are fetched FA_COMBINE_CHUNK splits at a time (the index clamped to S - 1, the value of a clamped slot not used), and only
-// the arithmetic runs one split after the other. ----
+// the arithmetic runs one split after the other.
+// PAGED = true (brn_flash_attention_paged_forward): a row may have no visible key in ANY split (its sequence is empty, or causal with
+// query + len - seq_q < 0), so M may be -inf.  The weights are then taken against 0 instead of M (exp2(-inf - 0) = 0: -inf - -inf is never
+// formed), and y = 0, lse = -inf are SELECTED for the row.  A row with a visible key has a finite M and goes through the operations of
+// PAGED = false, which is the kernel of the split entry as it was. ----
 constexpr int FA_COMBINE_THREADS = 256;
 constexpr int FA_COMBINE_CHUNK = 8;
+template <bool PAGED>
 __global__ void __launch_bounds__(FA_COMBINE_THREADS) flash_split_combine_kernel(const FlashAttentionParams p) {
     const int D4 = p.head_dim / 4;
     const long R = (long)p.batch * p.heads * p.seq_q;
@@ -618,6 +683,8 @@ __global__ void __launch_bounds__(FA_COMBINE_THREADS) flash_split_combine_kernel
 #pragma unroll
         for (int j = 0; j < FA_COMBINE_CHUNK; ++j) M = fmaxf(M, l2[j]);          // (a clamped slot repeats split S - 1)
     }
+    const bool none = PAGED && !(M > -__builtin_inff());
+    if constexpr (PAGED) M = none ? 0.f : M;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     float wsum = 0.f;
     for (int s0 = 0; s0 < S; s0 += FA_COMBINE_CHUNK) {
@@ -640,8 +707,13 @@ __global__ void __launch_bounds__(FA_COMBINE_THREADS) flash_split_combine_kernel
     }
     const long bh = r / p.seq_q;
     const int query = (int)(r - bh * p.seq_q), b = (int)(bh / p.heads), head = (int)(bh - (long)b * p.heads);
-    *reinterpret_cast<f32x4*>(p.y + (b * p.q_sb + head * p.q_sh + query * p.q_ss + d)) = acc / wsum;
-    if (d == 0 && p.lse) p.lse[r] = (M + __builtin_amdgcn_logf(wsum)) * 0.6931471805599453f;
+    f32x4 yv = acc / wsum;
+    float lv = (M + __builtin_amdgcn_logf(wsum)) * 0.6931471805599453f;
+    if constexpr (PAGED) {
+        if (none) { yv = f32x4{0.f, 0.f, 0.f, 0.f}; lv = -__builtin_inff(); }
+    }
+    *reinterpret_cast<f32x4*>(p.y + (b * p.q_sb + head * p.q_sh + query * p.q_ss + d)) = yv;
+    if (d == 0 && p.lse) p.lse[r] = lv;
 }
 
 template <int D, bool BIAS, FaForm FORM>
@@ -654,6 +726,7 @@ void fa_launch(const FlashAttentionParams& p, dim3 grid, hipStream_t s) {
 template <int D>
 void fa_launch(const FlashAttentionParams& p, FaForm form, dim3 grid, hipStream_t s) {
     if (form == FA_VARLEN) fa_launch<D, false, FA_VARLEN>(p, grid, s);
+    else if (form == FA_PAGED) fa_launch<D, false, FA_PAGED>(p, grid, s);
     else if (form == FA_SPLIT) fa_launch<D, false, FA_SPLIT>(p, grid, s);
     else if (form == FA_PACKED) {
         if (p.bias) fa_launch<D, true, FA_PACKED>(p, grid, s);
@@ -682,12 +755,19 @@ hipError_t launch_flash_attention(const FlashAttentionParams& p, hipStream_t s) 
     }
     if (!(p.head_dim == 32 || p.head_dim == 64 || p.head_dim == 128) || p.seq_q < 1 || p.seq_kv < 1 || p.seq_q > 65536 || p.seq_kv > 65536 ||
         p.batch < 1 || p.heads < 1 || p.kv_heads < 1 || p.kv_heads > p.heads || p.heads % p.kv_heads ||
-        p.causal_off != (p.causal ? p.seq_kv - p.seq_q : 0) || p.causal_off < 0 || p.s16 < 0 || p.s16 > 2 || !(p.scale > 0.f) ||
+        p.causal_off != (p.causal && !p.block_table ? p.seq_kv - p.seq_q : 0) || p.causal_off < 0 || (p.block_table && !p.kv_splits) || p.s16 < 0 || p.s16 > 2 || !(p.scale > 0.f) ||
         p.n_bias < 0 || (p.bias == nullptr) != (p.n_bias == 0) || (p.n_bias > 0 && p.batch % p.n_bias))
         return hipErrorInvalidValue;
     if (p.kv_splits) {
         // the split over keys: S = kv_splits and tps = tiles_per_split as brn_flash_split_plan.h normalises them (no empty trailing split),
-        // the partials in the workspace exactly when S > 1; no bias
+        // the partials in the workspace exactly when S > 1; no bias.  With a block table (the paged entry) seq_kv is max_kv_len, k and v are
+        // the pool with a page's strides, and the per-sequence causal_off is the kernels' own (0 here)
+        const bool paged = p.block_table != nullptr;
+        if (paged && (!p.kv_lens || p.page_log2 < 4 || p.page_log2 > 8 || p.n_pages < 1 || p.max_pages < 1 || ((long)p.n_pages << p.page_log2) > 0x7fffffffL ||
+                      ((long)p.max_pages << p.page_log2) < p.seq_kv || p.kv_sb != 0 || p.kv_sh != p.head_dim || p.kv_ss != (long)p.kv_heads * p.head_dim ||
+                      p.page_stride != (p.kv_ss << p.page_log2)))
+            return hipErrorInvalidValue;
+        if (!paged && (p.kv_lens || p.page_stride || p.page_log2 || p.n_pages || p.max_pages)) return hipErrorInvalidValue;
         const int nkt = (p.seq_kv + FA_T - 1) / FA_T, S = p.kv_splits, tps = p.tiles_per_split;
         const long rows = (long)(p.heads / p.kv_heads) * p.seq_q;
         const long nwg = (long)p.batch * p.kv_heads * ((rows + FA_BQ - 1) / FA_BQ) * S;
@@ -696,10 +776,13 @@ hipError_t launch_flash_attention(const FlashAttentionParams& p, hipStream_t s) 
             (S > 1) != (p.o_part != nullptr) || (S > 1) != (p.lse2_part != nullptr) || (quads + FA_COMBINE_THREADS - 1) / FA_COMBINE_THREADS > 0x7fffffffL)
             return hipErrorInvalidValue;
         const dim3 grid((unsigned)nwg);
-        if (p.head_dim == 32) fa_launch<32>(p, FA_SPLIT, grid, s);
-        else if (p.head_dim == 64) fa_launch<64>(p, FA_SPLIT, grid, s);
-        else fa_launch<128>(p, FA_SPLIT, grid, s);
-        if (S > 1) hipLaunchKernelGGL(flash_split_combine_kernel, dim3((unsigned)((quads + FA_COMBINE_THREADS - 1) / FA_COMBINE_THREADS)), dim3(FA_COMBINE_THREADS), 0, s, p);
+        const FaForm form = paged ? FA_PAGED : FA_SPLIT;
+        if (p.head_dim == 32) fa_launch<32>(p, form, grid, s);
+        else if (p.head_dim == 64) fa_launch<64>(p, form, grid, s);
+        else fa_launch<128>(p, form, grid, s);
+        const dim3 cgrid((unsigned)((quads + FA_COMBINE_THREADS - 1) / FA_COMBINE_THREADS));
+        if (S > 1 && paged) hipLaunchKernelGGL(flash_split_combine_kernel<true>, cgrid, dim3(FA_COMBINE_THREADS), 0, s, p);
+        else if (S > 1) hipLaunchKernelGGL(flash_split_combine_kernel<false>, cgrid, dim3(FA_COMBINE_THREADS), 0, s, p);
         return hipGetLastError();
     }
     // one K / V head per query head and the diagonal at key = query: the kernels of the two older entries, a workgroup per (batch entry,

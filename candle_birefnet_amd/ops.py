@@ -267,6 +267,80 @@ def flash_attention_splitkv(q, k, v, kv_heads=None, causal=False, scale=None, la
     return out[0] if len(out) == 1 else out
 
 
+def _int32_arg(a, shape, what):
+    """an int32 contiguous array / tensor of `shape` -> (pointer, loc, keepalive, host copy or None): a numpy input (or a CPU tensor) is
+    converted and handed back for the range checks; a device tensor is never read back"""
+    if T._is_torch(a):
+        import torch
+        if a.dtype != torch.int32:
+            raise TypeError(f"{what} must be an int32 tensor")
+        t = a.contiguous()
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{what}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+        if t.is_cuda:
+            return t.data_ptr(), _ffi.BRN_MEM_DEVICE, t, None
+        return t.data_ptr(), _ffi.BRN_MEM_HOST, t, t.numpy()
+    h = np.asarray(a)
+    if h.dtype.kind not in "iu" or (h.size and (int(h.min()) < -2 ** 31 or int(h.max()) >= 2 ** 31)):
+        raise ValueError(f"{what} must be integers that fit int32")
+    h = np.ascontiguousarray(h, dtype=np.int32)
+    if tuple(h.shape) != tuple(shape):
+        raise ValueError(f"{what}: expected shape {tuple(shape)}, got {tuple(h.shape)}")
+    return h.ctypes.data, _ffi.BRN_MEM_HOST, h, h
+
+
+def flash_attention_paged(q, k_pages, v_pages, block_table, kv_lens, max_kv_len=None, causal=False, scale=None, layout="bshd", kv_splits=0,
+                          return_lse=False, return_partials=False, device=0):
+    """brn_flash_attention_paged_forward: flash_attention_splitkv over a paged K / V cache.  q as in flash_attention_splitkv (layout
+    "bshd" [batch, seq_q, heads, head_dim] or "bhsd"); k_pages, v_pages [n_pages, page_size, kv_heads, head_dim] fp32; block_table
+    [batch, max_pages] int32 (key j of batch entry b is row j % page_size of page block_table[b][j // page_size]); kv_lens [batch] int32;
+    both on q's side.  max_kv_len sizes the grid and the split: None = max_pages * page_size capped at 65536.  The workspace is sized by
+    flash_attention_splitkv_plan(batch, seq_q, max_kv_len, ...) and allocated beside q.  Returns as flash_attention_splitkv: y, with
+    return_lse (y, lse), with return_partials additionally (O_part, lse2_part) or (None, None) when S == 1.  A row with no visible key
+    comes back as zeros with lse -inf.
+    For host (numpy / CPU tensor) inputs only, the wrapper refuses what only it can know cheaply: a length outside 0 .. max_kv_len and a
+    USED table entry (one below ceil(len / page_size) of its sequence) outside 0 .. n_pages - 1.  Device tensors are not read back: the
+    library clamps their values (include/birefnet_hip.h).  Every other limit is the library's."""
+    lay = _ATTN_LAYOUT[layout]
+    seq_axis, head_axis = (1, 2) if lay == _ffi.BRN_ATTN_BSHD else (2, 1)
+    batch, hd = int(q.shape[0]), int(q.shape[3])
+    seq_q, heads = int(q.shape[seq_axis]), int(q.shape[head_axis])
+    n_pages, page_size, kv_heads = (int(s) for s in k_pages.shape[:3])
+    if len(block_table.shape) != 2:
+        raise ValueError("block_table must be [batch, max_pages]")
+    max_pages = int(block_table.shape[1])
+    if max_kv_len is None:
+        max_kv_len = min(max_pages * page_size, 65536)
+    max_kv_len = int(max_kv_len)
+    pool_shape = (n_pages, page_size, kv_heads, hd)
+    pq, loc, keep, _ = T.as_arg(q)
+    pk, kloc, kkeep, _ = T.as_arg(k_pages, pool_shape)
+    pv, vloc, vkeep, _ = T.as_arg(v_pages, pool_shape)
+    pt, tloc, tkeep, th = _int32_arg(block_table, (batch, max_pages), "block_table")
+    pl, lloc, lkeep, lh = _int32_arg(kv_lens, (batch,), "kv_lens")
+    if not (kloc == vloc == tloc == lloc == loc):
+        raise ValueError("q, k_pages, v_pages, block_table and kv_lens must live on the same side")
+    if lh is not None and th is not None:
+        if lh.size and (int(lh.min()) < 0 or int(lh.max()) > max_kv_len):
+            raise ValueError(f"kv_lens must lie in 0 .. max_kv_len = {max_kv_len}")
+        used = np.arange(max_pages)[None, :] * page_size < lh[:, None]
+        if used.any() and (int(th[used].min()) < 0 or int(th[used].max()) >= n_pages):
+            raise ValueError(f"block_table entries in use must lie in 0 .. n_pages - 1 = {n_pages - 1}")
+    S, _tps, nws = flash_attention_splitkv_plan(batch, seq_q, max_kv_len, heads, kv_heads, hd, kv_splits)
+    R = batch * heads * seq_q
+    y = T.alloc_like(keep, tuple(int(s) for s in q.shape))
+    lse = T.alloc_like(keep, (batch, heads, seq_q)) if return_lse else None
+    ws = T.alloc_like(keep, (nws,)) if S > 1 else None
+    _ffi.check(_ffi.lib.brn_flash_attention_paged_forward(pq, pk, pv, pt, pl, batch, seq_q, max_kv_len, heads, kv_heads, hd, n_pages, page_size, max_pages, lay,
+                                                          int(bool(causal)), float(scale) if scale is not None else 0.0, int(kv_splits), T.ptr_of(y),
+                                                          T.ptr_of(lse) if lse is not None else None, T.ptr_of(ws) if ws is not None else None,
+                                                          nws if ws is not None else 0, loc, T.device_of(keep, device), T.stream_of(keep)))
+    out = (y,) + ((lse,) if return_lse else ())
+    if return_partials:
+        out += ((ws[:S * R * hd].reshape(S, R, hd), ws[S * R * hd:].reshape(S, R)) if ws is not None else (None, None),)
+    return out[0] if len(out) == 1 else out
+
+
 def patch_merging(x, H, W, norm_g, norm_b, reduction_w, device=0):
     """PatchMerging::forward (swin.rs:491-527): x [B,H*W,C] -> [B, ceil(H/2)*ceil(W/2), 2C]."""
     B, L, Cc = (int(v) for v in x.shape)

@@ -437,7 +437,8 @@ brn_status brn_flash_attention_varlen_forward(const float* q, const float* k, co
  * the device): every limit of brn_flash_attention_gqa_forward without a bias; 0 <= kv_splits <= 1024; workspace not NULL and
  * workspace_floats large enough when S > 1 (the message names the float count needed); batch * kv_heads * ceil(G * seq_q / 64) * S < 2^31;
  * y, lse and workspace overlap neither each other nor an input; BRN_MEM_DEVICE pointers 16-byte aligned.
- * Not provided: a bias; packed or paged K / V; 16-bit tensors at the boundary; a split for the four older entries. */
+ * Not provided: a bias; packed or paged K / V; 16-bit tensors at the boundary; a split for the four older entries.  (Paged K / V with
+ * per-sequence lengths on the device is brn_flash_attention_paged_forward below.) */
 brn_status brn_flash_attention_splitkv_plan(int batch, int seq_q, int seq_kv, int heads, int kv_heads, int head_dim,
                                             int kv_splits, int* splits_out, int* tiles_per_split_out,
                                             size_t* workspace_floats_out);
@@ -446,6 +447,53 @@ brn_status brn_flash_attention_splitkv_forward(const float* q, const float* k, c
                                                int layout, int causal, float scale, int kv_splits,
                                                float* y, float* lse, float* workspace, size_t workspace_floats,
                                                brn_mem loc, int device_ordinal, void* stream);
+/* brn_flash_attention_splitkv_forward over a PAGED K / V cache with per-sequence lengths that live on the device: the decode entry of a
+ * serving batch, whose sequences have different lengths and keep their keys in fixed-size pages of a shared pool.
+ *   y[b,h] = softmax over the visible keys j < len_b of batch entry b( scale * q[b,h] k_b[j, h / G]^T ) v_b[j, h / G],   lse as in the split entry
+ * q, y, layout, G = heads / kv_heads, scale, lse ([batch, heads, seq_q], or NULL), workspace and kv_splits are exactly those of
+ * brn_flash_attention_splitkv_forward.
+ * k_pages, v_pages: [n_pages, page_size, kv_heads, head_dim] fp32, contiguous, where `loc` says; page_size 16, 32, 64, 128 or 256.  Offsets
+ * into the pool are 64-bit: a pool may hold more than 2^31 floats.
+ * block_table: [batch, max_pages] int32 where `loc` says.  Key j of batch entry b is row j % page_size of page block_table[b][j / page_size].
+ * kv_lens: [batch] int32 where `loc` says; len_b = kv_lens[b] keys of batch entry b take part.  The kernels read both arrays as device
+ * data: the host never reads them for BRN_MEM_DEVICE (for BRN_MEM_HOST they are staged like the float operands), so their values cannot
+ * be validated before the launch and are made harmless instead:
+ *   kv_lens[b] is used as min(max(kv_lens[b], 0), max_kv_len); a page number is used as min(max(page, 0), n_pages - 1);
+ * no address in a kernel depends on either value other than through these clamps.  An out-of-range length therefore means max_kv_len (or
+ * 0), an out-of-range page number means the last (or the first) page of the pool: a wrong result for that sequence, never an access
+ * outside the pool or the table.  A table entry at or past ceil(len_b / page_size) of its sequence is never used to form an address, and
+ * rows of a page at or past len_b are never read into the arithmetic: they, and every page no used entry names, may hold anything (NaN
+ * included).
+ * The mask: causal 0, the keys 0 .. len_b - 1; causal 1, key j takes part in query i's row exactly when j <= i + len_b - seq_q: the gqa
+ * entry's mask, ending at the sequence's own last key.  len_b >= seq_q cannot be required of device data, so a row with no visible key
+ * is defined: y = 0 (exact zeros) and lse = -inf, no NaN anywhere.  That covers len_b == 0 and causal rows with i + len_b - seq_q < 0.
+ * The split and the workspace are brn_flash_attention_splitkv_plan(batch, seq_q, max_kv_len, heads, kv_heads, head_dim, kv_splits):
+ * nkt = ceil(max_kv_len / 64), split s owns tiles s * tps .. min((s + 1) * tps, nkt) - 1 of every sequence; the grid and the split are
+ * sized by max_kv_len, an upper bound the host knows, and a split that starts at or past a sequence's (causal) end writes the empty
+ * markers O_part = 0 and lse2_part = -inf.  O_part / lse2_part keep the layout and meaning of the split entry; S == 1 writes y and lse
+ * directly and touches no workspace.
+ * The promise: no atomics; the partials of a row are combined in the fixed order s = 0 .. S - 1; a row's bits depend only on its own q
+ * row, the keys and values of its sequence in logical order, len_b, the mask and tps: not on which physical pages hold the keys, not
+ * on page_size, n_pages, max_pages, `batch`, the other sequences' lengths, the launch grid or which rows share its workgroup; a repeated
+ * call repeats its bits.  With BRN_MEM_DEVICE the call allocates nothing, does not synchronise the stream and may be captured into a
+ * graph; changing kv_lens, block_table and the pool contents between replays is the intended use.  For a sequence the split entry accepts
+ * (len_b >= 1; causal: len_b >= seq_q) the row carries the bits of brn_flash_attention_splitkv_forward on that sequence's keys gathered
+ * into a dense tensor with seq_kv = len_b, whenever both calls walk the same tile ranges (the same tps, or one split holding all of it).
+ * Limits (each violation is BRN_ERR_INVALID_ARG with the prefix "flash attention paged:" and a message naming the limit, checked before
+ * the device): every limit of brn_flash_attention_splitkv_forward with max_kv_len in the place of seq_kv, except that causal does not
+ * require max_kv_len >= seq_q (a per-sequence matter, defined above); block_table and kv_lens not NULL; page_size 16, 32, 64, 128 or
+ * 256; n_pages >= 1, max_pages >= 1, n_pages * page_size < 2^31; 1 <= max_kv_len <= min(65536, max_pages * page_size); y, lse and
+ * workspace overlap neither each other nor any of the five inputs (sizes in bytes: the table and the lengths are ints); BRN_MEM_DEVICE
+ * pointers 16-byte aligned, the two int arrays 4-byte aligned.
+ * Not provided: a bias; a window; 16-bit or quantised pages; a K-transposed page layout; appending to the cache (the caller writes new
+ * keys into the pool). */
+brn_status brn_flash_attention_paged_forward(const float* q, const float* k_pages, const float* v_pages,
+                                             const int* block_table, const int* kv_lens,
+                                             int batch, int seq_q, int max_kv_len, int heads, int kv_heads, int head_dim,
+                                             int n_pages, int page_size, int max_pages,
+                                             int layout, int causal, float scale, int kv_splits,
+                                             float* y, float* lse, float* workspace, size_t workspace_floats,
+                                             brn_mem loc, int device_ordinal, void* stream);
 /* PatchMerging::forward (swin.rs:491-527): x [B,H*W,C] -> [B, ceil(H/2)*ceil(W/2), 2C]. */
 brn_status brn_patch_merging_forward(const float* x, int B, int H, int W, int C, const float* norm_g,
                                      const float* norm_b, const float* reduction_w, float* y, brn_mem loc,

@@ -42,7 +42,16 @@ the timed calls), so an event pair sees the library call and nothing of a wrappe
 explicit side, whether the rule's median lies inside that side's round spread, and whether the rule is slower than the gqa call beyond
 the gqa call's round spread.  Without --json the records go to profiles/flash_attention_splitkv_bench.json.
 
-  python tools/bench_flash_attention.py [--bias | --gqa | --varlen | --splitkv] [--row N] [--mode f32|bf16|f16] [--json PATH]"""
+--paged times brn_flash_attention_paged_forward beside brn_flash_attention_splitkv_forward on the same logical data, in the same
+alternating style, modes bf16 and f32, at 32 / 8 heads of 128, kv_splits 0 on every side: 16 x 1 / 4096, 1 x 1 / 32768, 64 x 1 / 4096, the
+causal 1 x 8 / 16384, and a ragged batch of 16 sequences whose lengths are spread evenly over 512 .. 4096 (max_kv_len 4096; its dense side
+is the padded call at 4096, which computes more).  Sides: the split entry on the dense K / V, then the paged entry with pages of 16, 64
+and 256 keys, each with an identity table (the pool IS the dense tensor's memory) and a shuffled one (a permuted copy).  The table and the
+lengths are device tensors; raw library calls on preallocated outputs.  Per paged side: its time over the dense side's, whether its median
+lies inside the dense side's round spread, and (equal lengths) whether it returned the dense call's bits.  Without --json the records go
+to profiles/flash_attention_paged_bench.json.
+
+  python tools/bench_flash_attention.py [--bias | --gqa | --varlen | --splitkv | --paged] [--row N] [--mode f32|bf16|f16] [--json PATH]"""
 import argparse
 import json
 import os
@@ -66,6 +75,11 @@ SPLITKV_ROWS = [(16, 1, 4096, 32, 8, 128, 0), (1, 1, 4096, 32, 8, 128, 0), (1, 1
 SPLITKV_SPLITS = [1, 2, 4, 8, 16, 32, 64, 0]
 SPLITKV_MODES = ["bf16", "f32"]
 SPLITKV_JSON = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "flash_attention_splitkv_bench.json")
+# (batch, seq_q, max_kv_len, heads, kv_heads, head_dim, causal, ragged): ragged = lengths spread evenly over 512 .. max_kv_len
+PAGED_ROWS = [(16, 1, 4096, 32, 8, 128, 0, 0), (1, 1, 32768, 32, 8, 128, 0, 0), (64, 1, 4096, 32, 8, 128, 0, 0), (1, 8, 16384, 32, 8, 128, 1, 0),
+              (16, 1, 4096, 32, 8, 128, 0, 1)]
+PAGED_PAGES = [16, 64, 256]
+PAGED_JSON = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "flash_attention_paged_bench.json")
 HBM_BYTES_PER_S = 8.0e12
 MODES = ["f32", "bf16", "f16"]
 WARMUP, TIMED = 5, 20
@@ -393,12 +407,89 @@ def bench_splitkv(row, mode):
     return out
 
 
+def bench_paged(row, mode):
+    import torch
+    import candle_birefnet_amd as cb
+    from candle_birefnet_amd import ops
+    lib = cb._ffi.lib
+    batch, seq_q, seq_kv, heads, kv_heads, hd, causal, ragged = row
+    g = torch.Generator(device="cuda").manual_seed(1)
+    q = torch.randn(batch, seq_q, heads, hd, device="cuda", generator=g)
+    k, v = (torch.randn(batch, seq_kv, kv_heads, hd, device="cuda", generator=g) for _ in range(2))
+    lens_h = [512 + (seq_kv - 512) * b // (batch - 1) for b in range(batch)] if ragged else [seq_kv] * batch
+    lens = torch.tensor(lens_h, dtype=torch.int32, device="cuda")
+    stream = torch.cuda.current_stream().cuda_stream
+    R = batch * heads * seq_q
+    S, tps, need = ops.flash_attention_splitkv_plan(batch, seq_q, seq_kv, heads, kv_heads, hd, 0)
+
+    def outputs():
+        return torch.empty_like(q), torch.empty(R, device="cuda"), torch.empty(max(need, 4), device="cuda")
+
+    yd, lsed, wsd = outputs()
+
+    def dense():
+        cb._ffi.check(lib.brn_flash_attention_splitkv_forward(q.data_ptr(), k.data_ptr(), v.data_ptr(), batch, seq_q, seq_kv, heads, kv_heads, hd, 0, causal, 0.0,
+                                                              0, yd.data_ptr(), lsed.data_ptr(), wsd.data_ptr(), need, 1, 0, stream))
+        return yd
+
+    def paged_side(page, shuffle):
+        n_pages, max_pages = batch * seq_kv // page, seq_kv // page
+        ident = torch.arange(n_pages, dtype=torch.int64, device="cuda")
+        if shuffle:
+            # physical page perm[j] holds logical page j
+            perm = torch.randperm(n_pages, device="cuda", generator=g)
+            kp, vp = (torch.empty_like(a).view(n_pages, page, kv_heads, hd).index_copy_(0, perm, a.view(n_pages, page, kv_heads, hd)) for a in (k, v))
+            table = perm.to(torch.int32).view(batch, max_pages).contiguous()
+        else:
+            kp, vp, table = k, v, ident.to(torch.int32).view(batch, max_pages).contiguous()
+        y, lse, ws = outputs()
+
+        def fn():
+            cb._ffi.check(lib.brn_flash_attention_paged_forward(q.data_ptr(), kp.data_ptr(), vp.data_ptr(), table.data_ptr(), lens.data_ptr(), batch, seq_q, seq_kv,
+                                                                heads, kv_heads, hd, n_pages, page, max_pages, 0, causal, 0.0, 0, y.data_ptr(), lse.data_ptr(),
+                                                                ws.data_ptr(), need, 1, 0, stream))
+            return y
+        return fn, (kp, vp, table)
+
+    out = []
+    ops.set_compute(mode)
+    try:
+        names = [(page, shuffle) for page in PAGED_PAGES for shuffle in (False, True)]
+        sides = [paged_side(*n) for n in names]
+        t = _time_alternating([dense] + [s[0] for s in sides])
+        td, tp = t[0], t[1:]
+        assert all(bool(torch.isfinite(x[4]).all()) for x in t)
+        rec = {"batch": batch, "seq_q": seq_q, "max_kv_len": seq_kv, "kv_lens": "all max_kv_len" if not ragged else lens_h, "heads": heads, "kv_heads": kv_heads,
+               "head_dim": hd, "mode": mode, "causal": causal, "S": S, "tiles_per_split": tps,
+               "kv_bytes_read": 2 * 4 * sum(lens_h) * kv_heads * hd, "table_bytes": 4 * batch * (seq_kv // 16)}
+        rec.update(_side("dense_split", td))
+        rec["paged"] = []
+        for (page, shuffle), tt in zip(names, tp):
+            e = {"page_size": page, "table": "shuffled" if shuffle else "identity", "over_dense": round(tt[0] / td[0], 4),
+                 "inside_dense_round_spread": bool(td[2] <= tt[0] <= td[3]), "faster_than_dense_spread": bool(tt[0] < td[2])}
+            if not ragged:
+                e["same_bits_as_dense"] = bool(torch.equal(tt[4], td[4]))
+            e.update(_side("paged", tt))
+            rec["paged"].append(e)
+        out.append(rec)
+        print(f"{batch:3d} x {seq_q:2d} / {seq_kv:5d}{' ragged' if ragged else ''} x {heads} / {kv_heads} x {hd} {mode:4s} causal {causal} S {S}: "
+              f"dense split {td[0]:8.4f} ms [{td[2]:.4f} .. {td[3]:.4f}] | "
+              + " | ".join(f"p{e['page_size']} {e['table'][:5]} {e['paged_ms_median']:.4f} [{e['paged_round_medians'][0]:.4f} .. {e['paged_round_medians'][1]:.4f}] x{e['over_dense']:.3f}"
+                           + ("" if ragged else f" bits {e['same_bits_as_dense']}") for e in rec["paged"]), flush=True)
+    finally:
+        ops.set_compute("f32")
+    del q, k, v, sides
+    torch.cuda.empty_cache()
+    return out
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--bias", action="store_true", help="time brn_flash_attention_bias_forward beside the bias-free call and torch + bias")
     ap.add_argument("--gqa", action="store_true", help="time brn_flash_attention_gqa_forward beside the older entries on repeated K / V (and a -inf mask bias)")
     ap.add_argument("--varlen", action="store_true", help="time brn_flash_attention_varlen_forward: windows, a ragged pack, a uniform pack, beside the gqa entry")
     ap.add_argument("--splitkv", action="store_true", help="time brn_flash_attention_splitkv_forward at kv_splits 1 .. 64 and 0 beside the gqa entry")
+    ap.add_argument("--paged", action="store_true", help="time brn_flash_attention_paged_forward (pages of 16 / 64 / 256, identity and shuffled tables) beside the split entry")
     ap.add_argument("--row", type=int, choices=range(len(BIAS_ROWS)))
     ap.add_argument("--mode", choices=MODES)
     ap.add_argument("--json", help="write the records to this file")
@@ -407,20 +498,23 @@ if __name__ == "__main__":
     if cb.device_count() < 1:
         sys.exit("no HIP device: nothing is measured")
     recs = []
-    if a.bias + a.gqa + a.varlen + a.splitkv > 1:
-        sys.exit("--bias, --gqa, --varlen and --splitkv are separate tables: one at a time")
-    rows = BIAS_ROWS if a.bias else GQA_ROWS if a.gqa else VARLEN_GROUPS if a.varlen else SPLITKV_ROWS if a.splitkv else ROWS
+    if a.bias + a.gqa + a.varlen + a.splitkv + a.paged > 1:
+        sys.exit("--bias, --gqa, --varlen, --splitkv and --paged are separate tables: one at a time")
+    rows = BIAS_ROWS if a.bias else GQA_ROWS if a.gqa else VARLEN_GROUPS if a.varlen else SPLITKV_ROWS if a.splitkv else PAGED_ROWS if a.paged else ROWS
     if a.row is not None and a.row >= len(rows):
         sys.exit(f"--row {a.row}: only {len(rows)} rows in this table")
     for row in (rows if a.row is None else [rows[a.row]]):
-        for mode in ((SPLITKV_MODES if a.splitkv else MODES) if a.mode is None else [a.mode]):
+        for mode in ((SPLITKV_MODES if a.splitkv or a.paged else MODES) if a.mode is None else [a.mode]):
             recs += (bench_bias(row, mode) if a.bias else bench_gqa(row, mode) if a.gqa else bench_varlen(row, mode) if a.varlen else
-                     bench_splitkv(row, mode) if a.splitkv else bench(row, mode))
+                     bench_splitkv(row, mode) if a.splitkv else bench_paged(row, mode) if a.paged else bench(row, mode))
     if a.splitkv and not a.json:
         a.json = SPLITKV_JSON
+    if a.paged and not a.json:
+        a.json = PAGED_JSON
     if a.json:
         with open(a.json, "w") as f:
-            alternating = a.gqa or a.varlen or a.splitkv
-            json.dump({"tool": "tools/bench_flash_attention.py" + (" --bias" if a.bias else " --gqa" if a.gqa else " --varlen" if a.varlen else " --splitkv" if a.splitkv else ""),
+            alternating = a.gqa or a.varlen or a.splitkv or a.paged
+            json.dump({"tool": "tools/bench_flash_attention.py" + (" --bias" if a.bias else " --gqa" if a.gqa else " --varlen" if a.varlen else " --splitkv" if a.splitkv else
+                                                                     " --paged" if a.paged else ""),
                        "warmup": GQA_WARMUP if alternating else WARMUP, "timed": GQA_ROUNDS * GQA_TIMED if alternating else TIMED, "rows": recs}, f, indent=1)
             f.write("\n")
