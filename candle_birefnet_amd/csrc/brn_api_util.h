@@ -70,6 +70,11 @@ inline bool floats_overlap(const float* a, size_t na, const float* y, size_t ny)
     const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), y0 = reinterpret_cast<uintptr_t>(y);
     return a && a0 < y0 + ny * sizeof(float) && y0 < a0 + na * sizeof(float);
 }
+// the same in bytes, for buffers whose element size varies (a K / V pool of brn_kv_type)
+inline bool bytes_overlap(const void* a, size_t na, const void* y, size_t ny) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), y0 = reinterpret_cast<uintptr_t>(y);
+    return a && y && a0 < y0 + ny && y0 < a0 + na;
+}
 // device buffers are read and written with 16-byte accesses (host buffers are staged into allocations of the library's own)
 inline bool all_aligned16(std::initializer_list<const void*> ptrs) {
     for (const void* p : ptrs)

@@ -227,8 +227,30 @@ struct FlashAttentionParams {
     long page_stride;             // elements between two pages: page_size * kv_heads * head_dim
     int page_log2;                // log2(page_size), 4 .. 8
     int n_pages, max_pages;       // max_pages * page_size >= seq_kv
+    // brn_flash_attention_paged_kv_forward; 0 = the kernels above, untouched.  1 / 2 (with a table only): k and v point at a pool of bf16 /
+    // fp16 elements (16-bit patterns; every stride and page_stride still counts ELEMENTS), read as stored by the 16-bit kernel of the same
+    // type (s16 == kv_type) or widened exactly by the fp32 kernel (s16 == 0); any other pairing is refused.  Read by the launcher alone
+    int kv_type;
 };
 hipError_t launch_flash_attention(const FlashAttentionParams& p, hipStream_t s);
+
+// brn_kv_cache_append (kernels/kv_cache.hip): token t of batch entry b becomes key min(max(kv_lens[b], 0), cap) + t of sequence b in the
+// pool of the paged attention entries; keys at or past cap are dropped; kv_lens_out[b] = min(that length + seq_new, cap), written by a
+// second launch (kv_lens_out may be kv_lens).  block_table and kv_lens hold UNVALIDATED device data, clamped as in FlashAttentionParams
+struct KvAppendParams {
+    const float* k_new; const float* v_new;   // fp32, 16-byte aligned, head_dim contiguous
+    long new_sb, new_ss, new_sh;              // their element strides: batch entry, token, K / V head
+    void* k_pages; void* v_pages;             // [n_pages, page_size, kv_heads, head_dim] of kv_type, 16-byte aligned
+    int kv_type;                              // 0 fp32, 1 bf16, 2 fp16: the cast (E)x of the attention kernels, round to nearest even
+    const int* block_table;                   // [batch][max_pages]
+    const int* kv_lens;                       // [batch]
+    int* kv_lens_out;                         // [batch], null = not wanted, or kv_lens itself
+    int batch, seq_new, kv_heads, head_dim;
+    long kv_ss, page_stride;                  // elements between two rows of a page (kv_heads * head_dim) and between two pages
+    int page_log2, n_pages, max_pages;
+    int cap;                                  // max_pages * page_size < 2^31
+};
+hipError_t launch_kv_cache_append(const KvAppendParams& p, hipStream_t s);
 
 // the index kernels of the generic window route (kernels/window_generic.hip; geometry: kernels/window_generic_geometry.h), window sides
 // 2 .. 32 other than the fused kernels' 12 and 7.  One struct for the three; each launcher reads the fields its kernel needs

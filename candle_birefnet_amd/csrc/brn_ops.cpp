@@ -510,77 +510,187 @@ brn_status brn_flash_attention_splitkv_forward(const float* q, const float* k, c
 // The split over keys with K / V in the pages of a pool and per-sequence lengths on the device.  The plan is the split entry's at
 // seq_kv = max_kv_len.  block_table and kv_lens are never read on the host for BRN_MEM_DEVICE: nothing here depends on their content, and
 // the call allocates nothing and does not synchronise (Staging has nothing to stage), so it may be captured into a graph.
+// One body for brn_flash_attention_paged_forward (kv_type BRN_KV_F32) and brn_flash_attention_paged_kv_forward: the pool's element size is
+// the only thing that differs on the host, so the overlap checks count bytes.
+static const char* const KV_TYPE_NAME[3] = {"f32", "bf16", "f16"};
+static size_t kv_type_bytes(int kv_type) { return kv_type == BRN_KV_F32 ? 4 : 2; }
+static void kv_type_check(const char* who, int kv_type) {
+    if (kv_type != BRN_KV_F32 && kv_type != BRN_KV_BF16 && kv_type != BRN_KV_F16)
+        fail(BRN_ERR_INVALID_ARG, "%s: kv_type %d unknown (kv_type must be 0 = f32, 1 = bf16 or 2 = f16)", who, kv_type);
+}
+// page_size 16 .. 256, a power of two; n_pages, max_pages >= 1; n_pages * page_size < 2^31 -> log2(page_size)
+static int paged_pool_check(const char* who, int n_pages, int page_size, int max_pages) {
+    int page_log2 = 0;
+    while ((1 << page_log2) < page_size && page_log2 < 9) ++page_log2;
+    if (page_size < 16 || page_size > 256 || (1 << page_log2) != page_size)
+        fail(BRN_ERR_INVALID_ARG, "%s: page_size %d unsupported (page_size must be 16, 32, 64, 128 or 256)", who, page_size);
+    if (n_pages < 1 || max_pages < 1) fail(BRN_ERR_INVALID_ARG, "%s: n_pages %d, max_pages %d unsupported (n_pages >= 1, max_pages >= 1)", who, n_pages, max_pages);
+    if ((long long)n_pages * page_size > 0x7fffffffLL)
+        fail(BRN_ERR_INVALID_ARG, "%s: n_pages %d of page_size %d too large (n_pages * page_size < 2^31)", who, n_pages, page_size);
+    return page_log2;
+}
+static void flash_attention_paged_body(const char* who, const float* q, const void* k_pages, const void* v_pages, int kv_type, const int* block_table,
+                                       const int* kv_lens, int batch, int seq_q, int max_kv_len, int heads, int kv_heads, int head_dim, int n_pages,
+                                       int page_size, int max_pages, int layout, int causal, float scale, int kv_splits, float* y, float* lse,
+                                       float* workspace, size_t workspace_floats, brn_mem loc, int device, void* stream) {
+    if (!q || !k_pages || !v_pages || !y) fail(BRN_ERR_INVALID_ARG, "%s: null q, k_pages, v_pages or y", who);
+    if (!block_table || !kv_lens) fail(BRN_ERR_INVALID_ARG, "%s: null block_table or kv_lens", who);
+    kv_type_check(who, kv_type);
+    const int s16 = attention_op_s16();
+    if (kv_type != BRN_KV_F32 && s16 && s16 != kv_type)
+        fail(BRN_ERR_INVALID_ARG, "%s: kv_type %s cannot be read in compute mode %s (a 16-bit compute mode reads a pool of its own type; the fp32-class modes read bf16 and f16 pools alike)",
+             who, KV_TYPE_NAME[kv_type], KV_TYPE_NAME[s16]);
+    const int page_log2 = paged_pool_check(who, n_pages, page_size, max_pages);
+    if (max_kv_len < 1 || max_kv_len > 65536 || max_kv_len > (long long)max_pages * page_size)
+        fail(BRN_ERR_INVALID_ARG, "%s: max_kv_len %d unsupported with max_pages %d of page_size %d (1 <= max_kv_len <= min(65536, max_pages * page_size))",
+             who, max_kv_len, max_pages, page_size);
+    // every limit of the split entry with max_kv_len in the place of seq_kv, but for its causal one (a per-sequence matter the kernels define)
+    flash_attention_check_sizes(who, true, batch, seq_q, max_kv_len, heads, kv_heads, head_dim);
+    splitkv_check_splits(who, kv_splits);
+    const FaSplitPlan pl = splitkv_plan_checked(who, batch, seq_q, max_kv_len, heads, kv_heads, head_dim, kv_splits);
+    if (layout != BRN_ATTN_BSHD && layout != BRN_ATTN_BHSD) fail(BRN_ERR_INVALID_ARG, "%s: layout %d unknown (layout must be 0 = BSHD or 1 = BHSD)", who, layout);
+    if (causal != 0 && causal != 1) fail(BRN_ERR_INVALID_ARG, "%s: causal %d (causal must be 0 or 1)", who, causal);
+    if (!scale_arg_ok(scale)) fail(BRN_ERR_INVALID_ARG, "%s: scale must be finite and >= 0 (0 = head_dim^-0.5)", who);
+    const size_t nq = (size_t)batch * heads * seq_q * head_dim, npool = (size_t)n_pages * page_size * kv_heads * head_dim;
+    const size_t pool_floats = npool * kv_type_bytes(kv_type) / 4;        // (npool is a multiple of 16 * 32)
+    const size_t R = (size_t)batch * heads * seq_q, ntab = (size_t)batch * max_pages;
+    const size_t need = pl.S > 1 ? pl.workspace_floats : 0;
+    if (need && (!workspace || workspace_floats < need))
+        fail(BRN_ERR_INVALID_ARG, "%s: workspace %s for %d splits (it must hold S * batch * heads * seq_q * (head_dim + 1) = %zu floats, workspace_floats %zu)",
+             who, workspace ? "too small" : "is NULL", pl.S, need, workspace_floats);
+    float* const ws = need ? workspace : nullptr;
+    // sizes in bytes: the table and the lengths are ints, the pool's elements 4 or 2 bytes
+    const struct { const void* p; size_t n; } ins[] = {{q, nq * 4}, {k_pages, pool_floats * 4}, {v_pages, pool_floats * 4}, {block_table, ntab * 4}, {kv_lens, (size_t)batch * 4}};
+    const struct { const float* p; size_t n; const char* name; } outs[] = {{y, nq * 4, "y"}, {lse, lse ? R * 4 : 0, "lse"}, {ws, need * 4, "workspace"}};
+    for (int a = 0; a < 3; ++a) {
+        if (!outs[a].p) continue;
+        for (const auto& in : ins)
+            if (bytes_overlap(in.p, in.n, outs[a].p, outs[a].n)) fail(BRN_ERR_INVALID_ARG, "%s: %s must not overlap an input", who, outs[a].name);
+        for (int b = 0; b < a; ++b)
+            if (outs[b].p && bytes_overlap(outs[b].p, outs[b].n, outs[a].p, outs[a].n))
+                fail(BRN_ERR_INVALID_ARG, "%s: %s and %s must not overlap", who, outs[b].name, outs[a].name);
+    }
+    if (loc == BRN_MEM_DEVICE && !all_aligned16({q, k_pages, v_pages, y, lse, ws}))
+        fail(BRN_ERR_INVALID_ARG, "%s: device q, k_pages, v_pages, y, lse and workspace must be 16-byte aligned", who);
+    if (loc == BRN_MEM_DEVICE && ((reinterpret_cast<uintptr_t>(block_table) | reinterpret_cast<uintptr_t>(kv_lens)) & 3))
+        fail(BRN_ERR_INVALID_ARG, "%s: device block_table and kv_lens must be 4-byte aligned", who);
+    ensure_device(device);
+    Staging st(stream, loc);
+    FlashAttentionParams p{};
+    p.q = st.in(q, nq); p.k = st.in(static_cast<const float*>(k_pages), pool_floats); p.v = st.in(static_cast<const float*>(v_pages), pool_floats);
+    p.block_table = reinterpret_cast<const int*>(st.in(reinterpret_cast<const float*>(block_table), ntab));
+    p.kv_lens = reinterpret_cast<const int*>(st.in(reinterpret_cast<const float*>(kv_lens), (size_t)batch));
+    p.y = st.out(y, nq);
+    p.batch = batch; p.heads = heads; p.kv_heads = kv_heads; p.seq_q = seq_q; p.seq_kv = max_kv_len; p.head_dim = head_dim;
+    const long d = head_dim;
+    if (layout == BRN_ATTN_BSHD) { p.q_ss = heads * d; p.q_sh = d; p.q_sb = seq_q * p.q_ss; }
+    else { p.q_ss = d; p.q_sh = seq_q * d; p.q_sb = heads * p.q_sh; }
+    // a key's row inside a page; the page comes from the table (no batch stride).  Strides count elements of the pool's type
+    p.kv_ss = kv_heads * d; p.kv_sh = d; p.kv_sb = 0;
+    p.page_stride = (long)page_size * p.kv_ss; p.page_log2 = page_log2; p.n_pages = n_pages; p.max_pages = max_pages;
+    p.kv_type = kv_type;
+    p.causal = causal; p.causal_off = 0;       // each workgroup's own: len_b - seq_q
+    p.scale = scale_or_default(scale, head_dim);
+    p.s16 = s16;
+    p.kv_splits = pl.S; p.tiles_per_split = pl.tps;
+    if (lse) p.lse = st.out(lse, R);
+    if (need) {
+        p.o_part = st.out(ws, need);
+        p.lse2_part = p.o_part + (size_t)pl.S * R * head_dim;
+    }
+    BRN_HIP(launch_flash_attention(p, (hipStream_t)stream));
+    st.finish();
+}
+
 brn_status brn_flash_attention_paged_forward(const float* q, const float* k_pages, const float* v_pages, const int* block_table, const int* kv_lens, int batch,
                                              int seq_q, int max_kv_len, int heads, int kv_heads, int head_dim, int n_pages, int page_size, int max_pages,
                                              int layout, int causal, float scale, int kv_splits, float* y, float* lse, float* workspace,
                                              size_t workspace_floats, brn_mem loc, int device, void* stream) {
     return guarded([&] {
-        const char* who = "flash attention paged";
-        if (!q || !k_pages || !v_pages || !y) fail(BRN_ERR_INVALID_ARG, "%s: null q, k_pages, v_pages or y", who);
+        flash_attention_paged_body("flash attention paged", q, k_pages, v_pages, BRN_KV_F32, block_table, kv_lens, batch, seq_q, max_kv_len, heads, kv_heads, head_dim,
+                                   n_pages, page_size, max_pages, layout, causal, scale, kv_splits, y, lse, workspace, workspace_floats, loc, device, stream);
+    });
+}
+
+brn_status brn_flash_attention_paged_kv_forward(const float* q, const void* k_pages, const void* v_pages, int kv_type, const int* block_table,
+                                                const int* kv_lens, int batch, int seq_q, int max_kv_len, int heads, int kv_heads, int head_dim,
+                                                int n_pages, int page_size, int max_pages, int layout, int causal, float scale, int kv_splits, float* y,
+                                                float* lse, float* workspace, size_t workspace_floats, brn_mem loc, int device, void* stream) {
+    return guarded([&] {
+        flash_attention_paged_body("flash attention paged kv", q, k_pages, v_pages, kv_type, block_table, kv_lens, batch, seq_q, max_kv_len, heads, kv_heads, head_dim,
+                                   n_pages, page_size, max_pages, layout, causal, scale, kv_splits, y, lse, workspace, workspace_floats, loc, device, stream);
+    });
+}
+
+// seq_new tokens per sequence into the pool, behind the keys each sequence has (kernels/kv_cache.hip).  Like the paged attention entries it
+// reads neither block_table nor kv_lens on the host for BRN_MEM_DEVICE, allocates nothing and does not synchronise.  BRN_MEM_HOST (a test
+// convenience) stages the whole pool up and copies it back whole.
+brn_status brn_kv_cache_append(const float* k_new, const float* v_new, int batch, int seq_new, int kv_heads, int head_dim, int layout, void* k_pages,
+                               void* v_pages, int kv_type, const int* block_table, const int* kv_lens, int* kv_lens_out, int n_pages, int page_size,
+                               int max_pages, brn_mem loc, int device, void* stream) {
+    return guarded([&] {
+        const char* who = "kv cache append";
+        if (!k_new || !v_new || !k_pages || !v_pages) fail(BRN_ERR_INVALID_ARG, "%s: null k_new, v_new, k_pages or v_pages", who);
         if (!block_table || !kv_lens) fail(BRN_ERR_INVALID_ARG, "%s: null block_table or kv_lens", who);
-        int page_log2 = 0;
-        while ((1 << page_log2) < page_size && page_log2 < 9) ++page_log2;
-        if (page_size < 16 || page_size > 256 || (1 << page_log2) != page_size)
-            fail(BRN_ERR_INVALID_ARG, "%s: page_size %d unsupported (page_size must be 16, 32, 64, 128 or 256)", who, page_size);
-        if (n_pages < 1 || max_pages < 1) fail(BRN_ERR_INVALID_ARG, "%s: n_pages %d, max_pages %d unsupported (n_pages >= 1, max_pages >= 1)", who, n_pages, max_pages);
-        if ((long long)n_pages * page_size > 0x7fffffffLL)
-            fail(BRN_ERR_INVALID_ARG, "%s: n_pages %d of page_size %d too large (n_pages * page_size < 2^31)", who, n_pages, page_size);
-        if (max_kv_len < 1 || max_kv_len > 65536 || max_kv_len > (long long)max_pages * page_size)
-            fail(BRN_ERR_INVALID_ARG, "%s: max_kv_len %d unsupported with max_pages %d of page_size %d (1 <= max_kv_len <= min(65536, max_pages * page_size))",
-                 who, max_kv_len, max_pages, page_size);
-        // every limit of the split entry with max_kv_len in the place of seq_kv, but for its causal one (a per-sequence matter the kernels define)
-        flash_attention_check_sizes(who, true, batch, seq_q, max_kv_len, heads, kv_heads, head_dim);
-        splitkv_check_splits(who, kv_splits);
-        const FaSplitPlan pl = splitkv_plan_checked(who, batch, seq_q, max_kv_len, heads, kv_heads, head_dim, kv_splits);
+        kv_type_check(who, kv_type);
+        if (!(head_dim == 32 || head_dim == 64 || head_dim == 128))
+            fail(BRN_ERR_INVALID_ARG, "%s: head_dim %d unsupported (head_dim must be 32, 64 or 128)", who, head_dim);
+        if (batch < 1 || kv_heads < 1) fail(BRN_ERR_INVALID_ARG, "%s: batch %d, kv_heads %d unsupported (batch >= 1, kv_heads >= 1)", who, batch, kv_heads);
+        if (seq_new < 1 || seq_new > 65536) fail(BRN_ERR_INVALID_ARG, "%s: seq_new %d unsupported (1 <= seq_new <= 65536)", who, seq_new);
         if (layout != BRN_ATTN_BSHD && layout != BRN_ATTN_BHSD) fail(BRN_ERR_INVALID_ARG, "%s: layout %d unknown (layout must be 0 = BSHD or 1 = BHSD)", who, layout);
-        if (causal != 0 && causal != 1) fail(BRN_ERR_INVALID_ARG, "%s: causal %d (causal must be 0 or 1)", who, causal);
-        if (!scale_arg_ok(scale)) fail(BRN_ERR_INVALID_ARG, "%s: scale must be finite and >= 0 (0 = head_dim^-0.5)", who);
-        const size_t nq = (size_t)batch * heads * seq_q * head_dim, npool = (size_t)n_pages * page_size * kv_heads * head_dim;
-        const size_t R = (size_t)batch * heads * seq_q, ntab = (size_t)batch * max_pages;
-        const size_t need = pl.S > 1 ? pl.workspace_floats : 0;
-        if (need && (!workspace || workspace_floats < need))
-            fail(BRN_ERR_INVALID_ARG, "%s: workspace %s for %d splits (it must hold S * batch * heads * seq_q * (head_dim + 1) = %zu floats, workspace_floats %zu)",
-                 who, workspace ? "too small" : "is NULL", pl.S, need, workspace_floats);
-        float* const ws = need ? workspace : nullptr;
-        // sizes in 4-byte elements: the table and the lengths are ints
-        const struct { const void* p; size_t n; } ins[] = {{q, nq}, {k_pages, npool}, {v_pages, npool}, {block_table, ntab}, {kv_lens, (size_t)batch}};
-        const struct { const float* p; size_t n; const char* name; } outs[] = {{y, nq, "y"}, {lse, lse ? R : 0, "lse"}, {ws, need, "workspace"}};
-        for (int a = 0; a < 3; ++a) {
-            if (!outs[a].p) continue;
+        const int page_log2 = paged_pool_check(who, n_pages, page_size, max_pages);
+        if ((long long)max_pages * page_size > 0x7fffffffLL)
+            fail(BRN_ERR_INVALID_ARG, "%s: max_pages %d of page_size %d too large (max_pages * page_size < 2^31)", who, max_pages, page_size);
+        // the grid: a thread per 8 elements of a new row of K and of V
+        const long long per_b = (long long)seq_new * kv_heads * (head_dim / 8);
+        if (per_b > 0x7fffffffLL || (per_b * batch + 255) / 256 > 0x7fffffffLL)
+            fail(BRN_ERR_INVALID_ARG, "%s: batch %d, seq_new %d, kv_heads %d too large (seq_new * kv_heads * head_dim / 8 < 2^31, batch * that / 256 < 2^31)", who, batch, seq_new, kv_heads);
+        const size_t nnew = (size_t)batch * seq_new * kv_heads * head_dim, npool = (size_t)n_pages * page_size * kv_heads * head_dim;
+        const size_t pool_floats = npool * kv_type_bytes(kv_type) / 4, ntab = (size_t)batch * max_pages;
+        const struct { const void* p; size_t n; const char* name; } ins[] = {{k_new, nnew * 4, "k_new"}, {v_new, nnew * 4, "v_new"}, {block_table, ntab * 4, "block_table"},
+                                                                             {kv_lens, (size_t)batch * 4, "kv_lens"}};
+        for (const auto& in : ins)
+            if (bytes_overlap(in.p, in.n, k_pages, pool_floats * 4) || bytes_overlap(in.p, in.n, v_pages, pool_floats * 4))
+                fail(BRN_ERR_INVALID_ARG, "%s: %s must not overlap the pool", who, in.name);
+        if (bytes_overlap(k_pages, pool_floats * 4, v_pages, pool_floats * 4)) fail(BRN_ERR_INVALID_ARG, "%s: k_pages and v_pages must not overlap", who);
+        if (kv_lens_out && kv_lens_out != kv_lens) {
+            // kv_lens itself is the in-place form; any other overlap with an array the rows kernel reads or writes is refused
             for (const auto& in : ins)
-                if (floats_overlap(static_cast<const float*>(in.p), in.n, outs[a].p, outs[a].n)) fail(BRN_ERR_INVALID_ARG, "%s: %s must not overlap an input", who, outs[a].name);
-            for (int b = 0; b < a; ++b)
-                if (outs[b].p && floats_overlap(outs[b].p, outs[b].n, outs[a].p, outs[a].n))
-                    fail(BRN_ERR_INVALID_ARG, "%s: %s and %s must not overlap", who, outs[b].name, outs[a].name);
+                if (bytes_overlap(in.p, in.n, kv_lens_out, (size_t)batch * 4)) fail(BRN_ERR_INVALID_ARG, "%s: kv_lens_out must not overlap %s (kv_lens itself, the in-place form, excepted)", who, in.name);
+            if (bytes_overlap(k_pages, pool_floats * 4, kv_lens_out, (size_t)batch * 4) || bytes_overlap(v_pages, pool_floats * 4, kv_lens_out, (size_t)batch * 4))
+                fail(BRN_ERR_INVALID_ARG, "%s: kv_lens_out must not overlap the pool", who);
         }
-        if (loc == BRN_MEM_DEVICE && !all_aligned16({q, k_pages, v_pages, y, lse, ws}))
-            fail(BRN_ERR_INVALID_ARG, "%s: device q, k_pages, v_pages, y, lse and workspace must be 16-byte aligned", who);
-        if (loc == BRN_MEM_DEVICE && ((reinterpret_cast<uintptr_t>(block_table) | reinterpret_cast<uintptr_t>(kv_lens)) & 3))
-            fail(BRN_ERR_INVALID_ARG, "%s: device block_table and kv_lens must be 4-byte aligned", who);
+        if (loc == BRN_MEM_DEVICE && !all_aligned16({k_new, v_new, k_pages, v_pages}))
+            fail(BRN_ERR_INVALID_ARG, "%s: device k_new, v_new, k_pages and v_pages must be 16-byte aligned", who);
+        if (loc == BRN_MEM_DEVICE && ((reinterpret_cast<uintptr_t>(block_table) | reinterpret_cast<uintptr_t>(kv_lens) | reinterpret_cast<uintptr_t>(kv_lens_out)) & 3))
+            fail(BRN_ERR_INVALID_ARG, "%s: device block_table, kv_lens and kv_lens_out must be 4-byte aligned", who);
         ensure_device(device);
         Staging st(stream, loc);
-        FlashAttentionParams p{};
-        p.q = st.in(q, nq); p.k = st.in(k_pages, npool); p.v = st.in(v_pages, npool);
+        KvAppendParams p{};
+        p.k_new = st.in(k_new, nnew); p.v_new = st.in(v_new, nnew);
+        if (loc == BRN_MEM_DEVICE) { p.k_pages = k_pages; p.v_pages = v_pages; }
+        else {
+            // the pool goes up whole and comes back whole
+            float* pools[2] = {static_cast<float*>(k_pages), static_cast<float*>(v_pages)};
+            void** dst[2] = {&p.k_pages, &p.v_pages};
+            for (int a = 0; a < 2; ++a) {
+                float* dpool = st.dalloc(pool_floats);
+                BRN_HIP(hipMemcpyAsync(dpool, pools[a], pool_floats * 4, hipMemcpyHostToDevice, (hipStream_t)stream));
+                st.outs.push_back({pools[a], dpool, pool_floats});
+                *dst[a] = dpool;
+            }
+        }
         p.block_table = reinterpret_cast<const int*>(st.in(reinterpret_cast<const float*>(block_table), ntab));
         p.kv_lens = reinterpret_cast<const int*>(st.in(reinterpret_cast<const float*>(kv_lens), (size_t)batch));
-        p.y = st.out(y, nq);
-        p.batch = batch; p.heads = heads; p.kv_heads = kv_heads; p.seq_q = seq_q; p.seq_kv = max_kv_len; p.head_dim = head_dim;
+        if (kv_lens_out) p.kv_lens_out = reinterpret_cast<int*>(st.out(reinterpret_cast<float*>(kv_lens_out), (size_t)batch));
+        p.kv_type = kv_type;
+        p.batch = batch; p.seq_new = seq_new; p.kv_heads = kv_heads; p.head_dim = head_dim;
         const long d = head_dim;
-        if (layout == BRN_ATTN_BSHD) { p.q_ss = heads * d; p.q_sh = d; p.q_sb = seq_q * p.q_ss; }
-        else { p.q_ss = d; p.q_sh = seq_q * d; p.q_sb = heads * p.q_sh; }
-        // a key's row inside a page; the page comes from the table (no batch stride)
-        p.kv_ss = kv_heads * d; p.kv_sh = d; p.kv_sb = 0;
-        p.page_stride = (long)page_size * p.kv_ss; p.page_log2 = page_log2; p.n_pages = n_pages; p.max_pages = max_pages;
-        p.causal = causal; p.causal_off = 0;       // each workgroup's own: len_b - seq_q
-        p.scale = scale_or_default(scale, head_dim);
-        p.s16 = attention_op_s16();
-        p.kv_splits = pl.S; p.tiles_per_split = pl.tps;
-        if (lse) p.lse = st.out(lse, R);
-        if (need) {
-            p.o_part = st.out(ws, need);
-            p.lse2_part = p.o_part + (size_t)pl.S * R * head_dim;
-        }
-        BRN_HIP(launch_flash_attention(p, (hipStream_t)stream));
+        if (layout == BRN_ATTN_BSHD) { p.new_ss = kv_heads * d; p.new_sh = d; p.new_sb = seq_new * p.new_ss; }
+        else { p.new_ss = d; p.new_sh = seq_new * d; p.new_sb = kv_heads * p.new_sh; }
+        p.kv_ss = kv_heads * d; p.page_stride = (long)page_size * p.kv_ss;
+        p.page_log2 = page_log2; p.n_pages = n_pages; p.max_pages = max_pages; p.cap = max_pages * page_size;
+        BRN_HIP(launch_kv_cache_append(p, (hipStream_t)stream));
         st.finish();
     });
 }

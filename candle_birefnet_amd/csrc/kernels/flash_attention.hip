@@ -76,6 +76,12 @@
 // a tile's entries are in registers a whole tile before its loads need them and the table's latency is paid once, in the prologue.
 // A row with no visible key at all (len 0, or causal with query + len - seq_q < 0) is empty in every split: fa_finish_split gives 0 / -inf
 // as before, and flash_split_combine_kernel<true> selects y = 0, lse = -inf for it without forming -inf - -inf.  DESIGN.md 3.2i.
+// KV (brn_flash_attention_paged_kv_forward): the type the pool is STORED in, a last template parameter of both kernels; float everywhere
+// but in 12 FA_PAGED instantiations, where the pool holds __bf16 or _Float16.  The 16-bit kernel reads a pool of its own type with one
+// 16-byte load per (key, 8 d) and carries the bits to LDS unconverted; the fp32 kernel reads either type and widens exactly as it writes
+// LDS.  What reaches LDS is what KV = float puts there from the pool widened to fp32 ((E)(float)e == e), so a row carries those bits.
+// The table-entry schedule, the clamps and the zero-select are FA_PAGED's; every instantiation with KV = float is the kernel it was,
+// instruction for instruction.  DESIGN.md 3.2j.
 #include "../brn_kernels.h"
 #include "../brn_flash_varlen_plan.h"
 #include "attention_mfma.h"
@@ -409,11 +415,28 @@ __device__ __forceinline__ void fa_finish_split(const FlashAttentionParams& p, c
     if (g == 0 && ldst) *ldst = lv;
 }
 
+// ---- KV (brn_flash_attention_paged_kv_forward): the type the pool is stored in, float in every older form.  A 16-bit pool is read with
+// 16-byte loads of 8 consecutive d of one key; offsets stay 64-bit and count elements.  fa_kv_base: the workgroup's K / V head in such a
+// pool (FaBlock keeps float pointers: blk.k - p.k is the head's offset in elements, whatever an element is).  fa_widen is exact. ----
+template <typename KV>
+__device__ __forceinline__ const KV* fa_kv_base(const float* pool, const float* head) { return reinterpret_cast<const KV*>(pool) + (head - pool); }
+template <typename KV>
+__device__ __forceinline__ float fa_widen(KV e) {
+    if constexpr (std::is_same<KV, __bf16>::value) return __builtin_bit_cast(float, (unsigned)__builtin_bit_cast(unsigned short, e) << 16);
+    else return (float)e;
+}
+
 // ---- fp32: v_mfma_f32_16x16x4_f32, an exact fmaf chain per score and per output ----
 // LDS: Ks, Vs [64][D + 4] floats (D 128: 66 KB).  Staging item = (key, 4-wide d chunk), D / 16 items of K and of V per thread.
-template <int D, bool BIAS, FaForm FORM>
+// KV = __bf16 / _Float16 (FA_PAGED only): staging item = (key, 8-wide d chunk), D / 32 items per thread, each ONE 16-byte load of K and of
+// V; the elements stay 16-bit in registers under the MFMAs and are widened (exactly) as they are written to LDS, so Ks / Vs hold what
+// the float pool widened on the host would have put there.  A thread's items are whole keys: one table entry per item, as for KV = float.
+template <int D, bool BIAS, FaForm FORM, typename KV = float>
 __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const FlashAttentionParams pa) {
+    constexpr bool KV16 = !std::is_same<KV, float>::value;
+    static_assert(!KV16 || (FORM == FA_PAGED && !BIAS), "16-bit K / V storage exists for the paged form alone");
     constexpr int LD = D + 4, NI = D / 16, ND = D / 16, NC = D / 32;
+    constexpr int NI16 = D / 32;                           // KV16: items per thread
     __shared__ __attribute__((aligned(16))) float Ks[FA_T * LD];
     __shared__ __attribute__((aligned(16))) float Vs[FA_T * LD];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -443,19 +466,42 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
         }
     }
     f32x4 kr[NI], vr[NI];
+    vec8<KV> kr16[NI16], vr16[NI16];                       // KV16: the tile in flight, as stored
     f32x4 bn[FA_T / 16];                                   // BIAS: the bias of the tile in kr / vr, loaded with it
     // FA_PAGED: the table entries of the thread's NI keys of a tile: pn as fetch_pages loads them, a tile ahead; pe those load_tile uses
+    // (KV16: the thread's NI16 keys)
     FaPages pgs{};
     int pe[NI], pn[NI];
     auto fetch_pages = [&](int key0) {
+        if constexpr (KV16) {
 #pragma unroll
-        for (int i = 0; i < NI; ++i) pn[i] = fa_page_entry(pgs, min(key0 + (tid + i * FA_THREADS) / (D / 4), p.seq_kv - 1));
+            for (int i = 0; i < NI16; ++i) pn[i] = fa_page_entry(pgs, min(key0 + (tid + i * FA_THREADS) / (D / 8), p.seq_kv - 1));
+        } else {
+#pragma unroll
+            for (int i = 0; i < NI; ++i) pn[i] = fa_page_entry(pgs, min(key0 + (tid + i * FA_THREADS) / (D / 4), p.seq_kv - 1));
+        }
     };
     auto use_pages = [&]() {
 #pragma unroll
-        for (int i = 0; i < NI; ++i) pe[i] = pn[i];
+        for (int i = 0; i < (KV16 ? NI16 : NI); ++i) pe[i] = pn[i];
     };
     auto load_tile = [&](int key0) {
+        if constexpr (KV16) {
+            const KV* kb = fa_kv_base<KV>(p.k, blk.k);
+            const KV* vb = fa_kv_base<KV>(p.v, blk.v);
+#pragma unroll
+            for (int i = 0; i < NI16; ++i) {
+                const int idx = tid + i * FA_THREADS, t = key0 + idx / (D / 8), c8 = (idx % (D / 8)) * 8;
+                const long src = fa_page_row(pgs, pe[i], min(t, p.seq_kv - 1), p.kv_ss) + c8;
+                kr16[i] = *reinterpret_cast<const vec8<KV>*>(kb + src);
+                vr16[i] = *reinterpret_cast<const vec8<KV>*>(vb + src);
+                if (t >= p.seq_kv) {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) { kr16[i][e] = (KV)0.f; vr16[i][e] = (KV)0.f; }
+                }
+            }
+            return;
+        }
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
             const int idx = tid + i * FA_THREADS, t = key0 + idx / (D / 4), c4 = (idx % (D / 4)) * 4;
@@ -480,11 +526,26 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
     if constexpr (FORM == FA_PAGED) fetch_pages((kt_first + 1) * FA_T);      // (a key past the sequence is clamped into it: a valid entry, not used)
     for (int kt = kt_first; kt < blk.nkt; ++kt) {
         __syncthreads();                                   // every wave is done reading the previous tile
+        if constexpr (KV16) {
 #pragma unroll
-        for (int i = 0; i < NI; ++i) {
-            const int idx = tid + i * FA_THREADS, t = idx / (D / 4), c4 = (idx % (D / 4)) * 4;
-            *reinterpret_cast<f32x4*>(Ks + t * LD + c4) = kr[i];
-            *reinterpret_cast<f32x4*>(Vs + t * LD + c4) = vr[i];
+            for (int i = 0; i < NI16; ++i) {
+                const int idx = tid + i * FA_THREADS, t = idx / (D / 8), c8 = (idx % (D / 8)) * 8;
+#pragma unroll
+                for (int hh = 0; hh < 2; ++hh) {
+                    f32x4 kw, vw;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) { kw[e] = fa_widen<KV>(kr16[i][hh * 4 + e]); vw[e] = fa_widen<KV>(vr16[i][hh * 4 + e]); }
+                    *reinterpret_cast<f32x4*>(Ks + t * LD + c8 + hh * 4) = kw;
+                    *reinterpret_cast<f32x4*>(Vs + t * LD + c8 + hh * 4) = vw;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < NI; ++i) {
+                const int idx = tid + i * FA_THREADS, t = idx / (D / 4), c4 = (idx % (D / 4)) * 4;
+                *reinterpret_cast<f32x4*>(Ks + t * LD + c4) = kr[i];
+                *reinterpret_cast<f32x4*>(Vs + t * LD + c4) = vr[i];
+            }
         }
         __syncthreads();
         // S^T = K . Q^T (BIAS: + bias, as the initial accumulator: it joins the unscaled scores, and an all-zero bias gives the bias-free bits)
@@ -530,10 +591,19 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
 // Scores, m, l (of the UNROUNDED numerators) and O are fp32; the numerators are rounded to E for P . V.
 // LDS: Kp[key][D] and Vt[d][72 keys] (kernels/attention_mfma.h): D 128 = 16 + 18 KB.
 // Staging item = (key pair, 4-wide d chunk): thread -> (d chunk low 2 bits, key pair, d chunk high bits), so a quad of lanes reads 64
-// contiguous bytes of a row and the 4-byte transposed V writes of a wave fall 2-way on the 32 banks. ----
-template <typename E, int D, bool BIAS, FaForm FORM>
+// contiguous bytes of a row and the 4-byte transposed V writes of a wave fall 2-way on the 32 banks.
+// KV = E (FA_PAGED only; brn_flash_attention_paged_kv_forward): the pool already holds E.  Staging item = (key pair, 8-wide d chunk), the
+// same thread map with 8 d where the float map has 4: ONE 16-byte load per key of K and of V, a quad of lanes still reads 64 contiguous
+// bytes of a row, the K side goes to LDS as one 16-byte store of a whole att_k_chunk and the V side as 8 att_vt_store of the thread's
+// key pair, no conversion anywhere.  Passes: D / 64; with D = 32 the 128 items fill half a pass, and waves 2 and 3 stage nothing
+// (a wave-uniform branch; the tile is 4 KB of K and of V, and a map of single keys would turn the V^T stores into twice as many 2-byte
+// ones).  What reaches LDS is what the float pool's cast puts there, since (E)(float)e == e: the bits of KV = float on the widened pool. ----
+template <typename E, int D, bool BIAS, FaForm FORM, typename KV = float>
 __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const FlashAttentionParams pa) {
     constexpr bool F16 = std::is_same<E, _Float16>::value;
+    constexpr bool KV16 = !std::is_same<KV, float>::value;
+    static_assert(!KV16 || (FORM == FA_PAGED && !BIAS && std::is_same<KV, E>::value), "16-bit K / V storage: the paged form, in the kernel's own type");
+    constexpr int NP16 = D == 128 ? 2 : 1;        // KV16: staging passes
     constexpr int NP = D / 32, ND = D / 16;       // staging passes = MFMA k steps of a score tile; d tiles of O^T
     typedef vec8<E> ex8;
     typedef vec4<E> ex4;
@@ -565,14 +635,41 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
     // staging: keys (2 tp, 2 tp + 1) of the tile, d = c4 .. c4 + 3 with c4 = 16 (hi + 2 pass) + 4 lo
     const int s_lo = tid & 3, s_tp = (tid >> 2) & 31, s_hi = tid >> 7;
     f32x4 kr[NP][2], vr[NP][2];
+    ex8 kr16[NP16][2], vr16[NP16][2];                      // KV16: the tile in flight, as stored
+    const bool stages = D >= 64 || s_hi == 0;              // KV16, D = 32: the waves that hold items (wave-uniform)
     f32x4 bn[FA_T / 16];                                   // BIAS: the bias of the tile in kr / vr, loaded with it
     // FA_PAGED: the table entry of the thread's key pair of a tile: pn as fetch_pages loads it, a tile ahead; pe the one load_tile uses.
     // A page holds an even number of keys from an even key on, so the pair (and what a key past the sequence is clamped to) shares a page
+    // (KV16: the thread still owns ONE key pair (2 tp, 2 tp + 1), now with 8 d of it.  A page holds at least 16 keys and starts at a
+    // multiple of 16, 2 tp is even, so 2 tp and 2 tp + 1 lie on one page; a key at or past len is clamped to len - 1, which is 2 tp itself
+    // when only 2 tp + 1 is past the end and the one key the entry was fetched for when both are: one entry per thread and tile serves)
     FaPages pgs{};
     int pe = 0, pn = 0;
     auto fetch_pages = [&](int key0) { pn = fa_page_entry(pgs, min(key0 + s_tp * 2, p.seq_kv - 1)); };
     auto use_pages = [&]() { pe = pn; };
     auto load_tile = [&](int key0) {
+        if constexpr (KV16) {
+            if (stages) {
+                const KV* kb = fa_kv_base<KV>(p.k, blk.k);
+                const KV* vb = fa_kv_base<KV>(p.v, blk.v);
+#pragma unroll
+                for (int ps = 0; ps < NP16; ++ps) {
+                    const int c8 = (s_hi + 2 * ps) * 32 + s_lo * 8;
+#pragma unroll
+                    for (int u = 0; u < 2; ++u) {
+                        const int t = key0 + s_tp * 2 + u;
+                        const long src = fa_page_row(pgs, pe, min(t, p.seq_kv - 1), p.kv_ss) + c8;
+                        kr16[ps][u] = *reinterpret_cast<const ex8*>(kb + src);
+                        vr16[ps][u] = *reinterpret_cast<const ex8*>(vb + src);
+                        if (t >= p.seq_kv) {
+#pragma unroll
+                            for (int e = 0; e < 8; ++e) { kr16[ps][u][e] = (E)0.f; vr16[ps][u][e] = (E)0.f; }
+                        }
+                    }
+                }
+            }
+            return;
+        }
 #pragma unroll
         for (int ps = 0; ps < NP; ++ps) {
             const int c4 = (s_hi + 2 * ps) * 16 + s_lo * 4;
@@ -601,19 +698,35 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
     if constexpr (FORM == FA_PAGED) fetch_pages((kt_first + 1) * FA_T);      // (a key past the sequence is clamped into it: a valid entry, not used)
     for (int kt = kt_first; kt < blk.nkt; ++kt) {
         __syncthreads();                                   // every wave is done reading the previous tile
+        if constexpr (KV16) {
+            if (stages) {
 #pragma unroll
-        for (int ps = 0; ps < NP; ++ps) {
-            const int c4 = (s_hi + 2 * ps) * 16 + s_lo * 4;
+                for (int ps = 0; ps < NP16; ++ps) {
+                    const int c8 = (s_hi + 2 * ps) * 32 + s_lo * 8;
 #pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int t = s_tp * 2 + u;
-                ex4 h;
+                    for (int u = 0; u < 2; ++u) {
+                        const int t = s_tp * 2 + u;
+                        *reinterpret_cast<ex8*>(att_k_chunk<D>(Kp + t * D, t, c8 >> 3)) = kr16[ps][u];
+                    }
 #pragma unroll
-                for (int e = 0; e < 4; ++e) h[e] = (E)kr[ps][u][e];
-                *reinterpret_cast<ex4*>(att_k_chunk<D>(Kp + t * D, t, c4 >> 3) + (c4 & 4)) = h;
+                    for (int e = 0; e < 8; ++e) att_vt_store(Vt + (c8 + e) * FA_VT_LD, s_tp, vr16[ps][0][e], vr16[ps][1][e]);
+                }
             }
+        } else {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) att_vt_store(Vt + (c4 + e) * FA_VT_LD, s_tp, (E)vr[ps][0][e], (E)vr[ps][1][e]);
+            for (int ps = 0; ps < NP; ++ps) {
+                const int c4 = (s_hi + 2 * ps) * 16 + s_lo * 4;
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const int t = s_tp * 2 + u;
+                    ex4 h;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) h[e] = (E)kr[ps][u][e];
+                    *reinterpret_cast<ex4*>(att_k_chunk<D>(Kp + t * D, t, c4 >> 3) + (c4 & 4)) = h;
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) att_vt_store(Vt + (c4 + e) * FA_VT_LD, s_tp, (E)vr[ps][0][e], (E)vr[ps][1][e]);
+            }
         }
         __syncthreads();
         // S^T = K . Q^T (BIAS: + bias, as the initial accumulator: it joins the unscaled scores, and an all-zero bias gives the bias-free bits)
@@ -723,9 +836,20 @@ void fa_launch(const FlashAttentionParams& p, dim3 grid, hipStream_t s) {
     else if (p.s16 == 1) hipLaunchKernelGGL((flash_attention_s16_kernel<__bf16, D, BIAS, FORM>), grid, block, 0, s, p);
     else hipLaunchKernelGGL((flash_attention_s16_kernel<_Float16, D, BIAS, FORM>), grid, block, 0, s, p);
 }
+// FA_PAGED over a 16-bit pool (p.kv_type 1 bf16 / 2 fp16; launch_flash_attention has refused every pairing but these): the fp32 kernel
+// widening either type, or the 16-bit kernel of the pool's own type
+template <int D>
+void fa_launch_kv16(const FlashAttentionParams& p, dim3 grid, hipStream_t s) {
+    const dim3 block(FA_THREADS);
+    if (p.s16 == 0 && p.kv_type == 1) hipLaunchKernelGGL((flash_attention_f32_kernel<D, false, FA_PAGED, __bf16>), grid, block, 0, s, p);
+    else if (p.s16 == 0) hipLaunchKernelGGL((flash_attention_f32_kernel<D, false, FA_PAGED, _Float16>), grid, block, 0, s, p);
+    else if (p.s16 == 1) hipLaunchKernelGGL((flash_attention_s16_kernel<__bf16, D, false, FA_PAGED, __bf16>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((flash_attention_s16_kernel<_Float16, D, false, FA_PAGED, _Float16>), grid, block, 0, s, p);
+}
 template <int D>
 void fa_launch(const FlashAttentionParams& p, FaForm form, dim3 grid, hipStream_t s) {
     if (form == FA_VARLEN) fa_launch<D, false, FA_VARLEN>(p, grid, s);
+    else if (form == FA_PAGED && p.kv_type) fa_launch_kv16<D>(p, grid, s);
     else if (form == FA_PAGED) fa_launch<D, false, FA_PAGED>(p, grid, s);
     else if (form == FA_SPLIT) fa_launch<D, false, FA_SPLIT>(p, grid, s);
     else if (form == FA_PACKED) {
@@ -740,6 +864,8 @@ void fa_launch(const FlashAttentionParams& p, FaForm form, dim3 grid, hipStream_
 }  // namespace
 
 hipError_t launch_flash_attention(const FlashAttentionParams& p, hipStream_t s) {
+    // a 16-bit pool exists for the paged form alone, and a 16-bit kernel reads only a pool of its own type
+    if (p.kv_type && (p.kv_type < 0 || p.kv_type > 2 || !p.block_table || p.plan || (p.s16 && p.s16 != p.kv_type))) return hipErrorInvalidValue;
     if (p.plan) {
         // the packed batch: the record table was built and every value in it checked by the entry (brn_flash_varlen_plan.h); what is
         // checked here is what the kernels assume of the other arguments

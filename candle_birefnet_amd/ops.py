@@ -289,8 +289,35 @@ def _int32_arg(a, shape, what):
     return h.ctypes.data, _ffi.BRN_MEM_HOST, h, h
 
 
+_KV_TYPE = {None: _ffi.BRN_KV_F32, "f32": _ffi.BRN_KV_F32, "bf16": _ffi.BRN_KV_BF16, "f16": _ffi.BRN_KV_F16}
+
+
+def _pool_arg(a, shape, kv_dtype, what):
+    """a K / V pool of `kv_dtype` ("f32", "bf16", "f16") AS IT IS, never converted or copied (the append writes it in place) ->
+    (pointer, loc, keepalive).  f32: float32 tensors / arrays.  bf16 / f16: torch.bfloat16 / torch.float16 tensors (host or device),
+    np.float16 arrays for f16, np.uint16 arrays of bit patterns for either (numpy has no bf16).  Anything else raises."""
+    if tuple(int(s) for s in a.shape) != tuple(shape):
+        raise ValueError(f"{what}: expected shape {tuple(shape)}, got {tuple(a.shape)}")
+    if T._is_torch(a):
+        import torch
+        want = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}[kv_dtype]
+        if a.dtype != want:
+            raise TypeError(f"{what}: kv_dtype {kv_dtype!r} needs a {want} tensor, got {a.dtype}")
+        if not a.is_contiguous():
+            raise ValueError(f"{what} must be contiguous")
+        return a.data_ptr(), (_ffi.BRN_MEM_DEVICE if a.is_cuda else _ffi.BRN_MEM_HOST), a
+    if not isinstance(a, np.ndarray):
+        raise TypeError(f"{what} must be a torch tensor or a numpy array")
+    ok = {"f32": (np.float32,), "bf16": (np.uint16,), "f16": (np.float16, np.uint16)}[kv_dtype]
+    if a.dtype not in [np.dtype(t) for t in ok]:
+        raise TypeError(f"{what}: kv_dtype {kv_dtype!r} needs a numpy array of {' or '.join(np.dtype(t).name for t in ok)}, got {a.dtype}")
+    if not a.flags.c_contiguous:
+        raise ValueError(f"{what} must be contiguous")
+    return a.ctypes.data, _ffi.BRN_MEM_HOST, a
+
+
 def flash_attention_paged(q, k_pages, v_pages, block_table, kv_lens, max_kv_len=None, causal=False, scale=None, layout="bshd", kv_splits=0,
-                          return_lse=False, return_partials=False, device=0):
+                          return_lse=False, return_partials=False, device=0, kv_dtype=None):
     """brn_flash_attention_paged_forward: flash_attention_splitkv over a paged K / V cache.  q as in flash_attention_splitkv (layout
     "bshd" [batch, seq_q, heads, head_dim] or "bhsd"); k_pages, v_pages [n_pages, page_size, kv_heads, head_dim] fp32; block_table
     [batch, max_pages] int32 (key j of batch entry b is row j % page_size of page block_table[b][j // page_size]); kv_lens [batch] int32;
@@ -300,7 +327,12 @@ def flash_attention_paged(q, k_pages, v_pages, block_table, kv_lens, max_kv_len=
     comes back as zeros with lse -inf.
     For host (numpy / CPU tensor) inputs only, the wrapper refuses what only it can know cheaply: a length outside 0 .. max_kv_len and a
     USED table entry (one below ceil(len / page_size) of its sequence) outside 0 .. n_pages - 1.  Device tensors are not read back: the
-    library clamps their values (include/birefnet_hip.h).  Every other limit is the library's."""
+    library clamps their values (include/birefnet_hip.h).  Every other limit is the library's.
+    kv_dtype None: the above, exactly (whatever the pool is given as is converted to fp32).  "bf16" / "f16": brn_flash_attention_paged_kv_forward
+    on a pool STORED in that type: torch.bfloat16 / torch.float16 tensors (host or device), np.float16 arrays for "f16", np.uint16 arrays
+    of bit patterns for either; a pool of another dtype raises.  ("f32" is the new entry on an fp32 pool: the bits of None.)"""
+    if kv_dtype not in _KV_TYPE:
+        raise ValueError(f"kv_dtype {kv_dtype!r} unknown (None, 'f32', 'bf16' or 'f16')")
     lay = _ATTN_LAYOUT[layout]
     seq_axis, head_axis = (1, 2) if lay == _ffi.BRN_ATTN_BSHD else (2, 1)
     batch, hd = int(q.shape[0]), int(q.shape[3])
@@ -314,8 +346,12 @@ def flash_attention_paged(q, k_pages, v_pages, block_table, kv_lens, max_kv_len=
     max_kv_len = int(max_kv_len)
     pool_shape = (n_pages, page_size, kv_heads, hd)
     pq, loc, keep, _ = T.as_arg(q)
-    pk, kloc, kkeep, _ = T.as_arg(k_pages, pool_shape)
-    pv, vloc, vkeep, _ = T.as_arg(v_pages, pool_shape)
+    if kv_dtype is None:
+        pk, kloc, kkeep, _ = T.as_arg(k_pages, pool_shape)
+        pv, vloc, vkeep, _ = T.as_arg(v_pages, pool_shape)
+    else:
+        pk, kloc, kkeep = _pool_arg(k_pages, pool_shape, kv_dtype, "k_pages")
+        pv, vloc, vkeep = _pool_arg(v_pages, pool_shape, kv_dtype, "v_pages")
     pt, tloc, tkeep, th = _int32_arg(block_table, (batch, max_pages), "block_table")
     pl, lloc, lkeep, lh = _int32_arg(kv_lens, (batch,), "kv_lens")
     if not (kloc == vloc == tloc == lloc == loc):
@@ -331,14 +367,74 @@ def flash_attention_paged(q, k_pages, v_pages, block_table, kv_lens, max_kv_len=
     y = T.alloc_like(keep, tuple(int(s) for s in q.shape))
     lse = T.alloc_like(keep, (batch, heads, seq_q)) if return_lse else None
     ws = T.alloc_like(keep, (nws,)) if S > 1 else None
-    _ffi.check(_ffi.lib.brn_flash_attention_paged_forward(pq, pk, pv, pt, pl, batch, seq_q, max_kv_len, heads, kv_heads, hd, n_pages, page_size, max_pages, lay,
-                                                          int(bool(causal)), float(scale) if scale is not None else 0.0, int(kv_splits), T.ptr_of(y),
-                                                          T.ptr_of(lse) if lse is not None else None, T.ptr_of(ws) if ws is not None else None,
-                                                          nws if ws is not None else 0, loc, T.device_of(keep, device), T.stream_of(keep)))
+    tail = (batch, seq_q, max_kv_len, heads, kv_heads, hd, n_pages, page_size, max_pages, lay, int(bool(causal)), float(scale) if scale is not None else 0.0,
+            int(kv_splits), T.ptr_of(y), T.ptr_of(lse) if lse is not None else None, T.ptr_of(ws) if ws is not None else None,
+            nws if ws is not None else 0, loc, T.device_of(keep, device), T.stream_of(keep))
+    if kv_dtype is None:
+        _ffi.check(_ffi.lib.brn_flash_attention_paged_forward(pq, pk, pv, pt, pl, *tail))
+    else:
+        _ffi.check(_ffi.lib.brn_flash_attention_paged_kv_forward(pq, pk, pv, _KV_TYPE[kv_dtype], pt, pl, *tail))
     out = (y,) + ((lse,) if return_lse else ())
     if return_partials:
         out += ((ws[:S * R * hd].reshape(S, R, hd), ws[S * R * hd:].reshape(S, R)) if ws is not None else (None, None),)
     return out[0] if len(out) == 1 else out
+
+
+def kv_cache_append(k_new, v_new, k_pages, v_pages, block_table, kv_lens, kv_dtype=None, layout="bshd", update_lens=True, device=0):
+    """brn_kv_cache_append: the seq_new tokens of k_new, v_new (fp32; layout "bshd" [batch, seq_new, kv_heads, head_dim] or "bhsd") go
+    into the pool behind the keys each sequence has: token t of batch entry b becomes key L_b + t, L_b = kv_lens[b] clamped to
+    0 .. max_pages * page_size; positions at or past that cap are dropped.  k_pages, v_pages [n_pages, page_size, kv_heads, head_dim]
+    are written IN PLACE and therefore taken as they are: float32 for kv_dtype None / "f32"; for "bf16" / "f16" the dtypes
+    flash_attention_paged(kv_dtype=...) accepts (the cast is the attention kernels', round to nearest even).  block_table
+    [batch, max_pages] int32 and kv_lens [batch] int32, all on k_new's side.
+    update_lens True: kv_lens (an int32 tensor / array, not a list) is updated in place and returned; False: the new lengths come back
+    in a new array and kv_lens is left alone; None: no lengths are written and None is returned.
+    For host inputs only, the wrapper refuses what flash_attention_paged refuses there: a length outside 0 .. max_pages * page_size and a
+    table entry at a written position outside 0 .. n_pages - 1.  Device tensors are not read back: the library clamps their values."""
+    if kv_dtype not in _KV_TYPE:
+        raise ValueError(f"kv_dtype {kv_dtype!r} unknown (None, 'f32', 'bf16' or 'f16')")
+    lay = _ATTN_LAYOUT[layout]
+    seq_axis, head_axis = (1, 2) if lay == _ffi.BRN_ATTN_BSHD else (2, 1)
+    batch, hd = int(k_new.shape[0]), int(k_new.shape[3])
+    seq_new, kv_heads = int(k_new.shape[seq_axis]), int(k_new.shape[head_axis])
+    n_pages, page_size = int(k_pages.shape[0]), int(k_pages.shape[1])
+    if len(block_table.shape) != 2:
+        raise ValueError("block_table must be [batch, max_pages]")
+    max_pages = int(block_table.shape[1])
+    pool_shape = (n_pages, page_size, kv_heads, hd)
+    pk, loc, keep, _ = T.as_arg(k_new)
+    pv, vloc, vkeep, _ = T.as_arg(v_new, tuple(int(s) for s in k_new.shape))
+    ppk, kloc, kkeep = _pool_arg(k_pages, pool_shape, kv_dtype or "f32", "k_pages")
+    ppv, pvloc, pvkeep = _pool_arg(v_pages, pool_shape, kv_dtype or "f32", "v_pages")
+    pt, tloc, tkeep, th = _int32_arg(block_table, (batch, max_pages), "block_table")
+    pl, lloc, lkeep, lh = _int32_arg(kv_lens, (batch,), "kv_lens")
+    if not (vloc == kloc == pvloc == tloc == lloc == loc):
+        raise ValueError("k_new, v_new, k_pages, v_pages, block_table and kv_lens must live on the same side")
+    cap = max_pages * page_size
+    if lh is not None and th is not None:
+        if lh.size and (int(lh.min()) < 0 or int(lh.max()) > cap):
+            raise ValueError(f"kv_lens must lie in 0 .. max_pages * page_size = {cap}")
+        slots = np.arange(max_pages)[None, :]
+        written = (slots >= lh[:, None] // page_size) & (slots * page_size < np.minimum(lh[:, None] + seq_new, cap))
+        if written.any() and (int(th[written].min()) < 0 or int(th[written].max()) >= n_pages):
+            raise ValueError(f"block_table entries at written positions must lie in 0 .. n_pages - 1 = {n_pages - 1}")
+    if update_lens is None:
+        out, po = None, None
+    elif update_lens:
+        if lkeep is not kv_lens and not (T._is_torch(kv_lens) and lkeep.data_ptr() == kv_lens.data_ptr()):
+            raise TypeError("update_lens=True needs kv_lens as a contiguous int32 tensor or array (it is written in place)")
+        out, po = kv_lens, pl
+    else:
+        if T._is_torch(lkeep):
+            import torch
+            out = torch.empty_like(lkeep)
+            po = out.data_ptr()
+        else:
+            out = np.empty(batch, np.int32)
+            po = out.ctypes.data
+    _ffi.check(_ffi.lib.brn_kv_cache_append(pk, pv, batch, seq_new, kv_heads, hd, lay, ppk, ppv, _KV_TYPE[kv_dtype], pt, pl, po, n_pages, page_size, max_pages,
+                                            loc, T.device_of(keep, device), T.stream_of(keep)))
+    return out
 
 
 def patch_merging(x, H, W, norm_g, norm_b, reduction_w, device=0):

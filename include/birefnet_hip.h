@@ -438,7 +438,8 @@ brn_status brn_flash_attention_varlen_forward(const float* q, const float* k, co
  * workspace_floats large enough when S > 1 (the message names the float count needed); batch * kv_heads * ceil(G * seq_q / 64) * S < 2^31;
  * y, lse and workspace overlap neither each other nor an input; BRN_MEM_DEVICE pointers 16-byte aligned.
  * Not provided: a bias; packed or paged K / V; 16-bit tensors at the boundary; a split for the four older entries.  (Paged K / V with
- * per-sequence lengths on the device is brn_flash_attention_paged_forward below.) */
+ * per-sequence lengths on the device is brn_flash_attention_paged_forward below; a bf16 / fp16 K / V pool is
+ * brn_flash_attention_paged_kv_forward, and writing new keys into a pool brn_kv_cache_append.) */
 brn_status brn_flash_attention_splitkv_plan(int batch, int seq_q, int seq_kv, int heads, int kv_heads, int head_dim,
                                             int kv_splits, int* splits_out, int* tiles_per_split_out,
                                             size_t* workspace_floats_out);
@@ -485,8 +486,8 @@ brn_status brn_flash_attention_splitkv_forward(const float* q, const float* k, c
  * 256; n_pages >= 1, max_pages >= 1, n_pages * page_size < 2^31; 1 <= max_kv_len <= min(65536, max_pages * page_size); y, lse and
  * workspace overlap neither each other nor any of the five inputs (sizes in bytes: the table and the lengths are ints); BRN_MEM_DEVICE
  * pointers 16-byte aligned, the two int arrays 4-byte aligned.
- * Not provided: a bias; a window; 16-bit or quantised pages; a K-transposed page layout; appending to the cache (the caller writes new
- * keys into the pool). */
+ * Not provided: a bias; a window; 16-bit or quantised pages (bf16 / fp16 pages are brn_flash_attention_paged_kv_forward below; quantised
+ * ones nowhere); a K-transposed page layout; appending to the cache (brn_kv_cache_append below writes new keys into the pool). */
 brn_status brn_flash_attention_paged_forward(const float* q, const float* k_pages, const float* v_pages,
                                              const int* block_table, const int* kv_lens,
                                              int batch, int seq_q, int max_kv_len, int heads, int kv_heads, int head_dim,
@@ -494,6 +495,63 @@ brn_status brn_flash_attention_paged_forward(const float* q, const float* k_page
                                              int layout, int causal, float scale, int kv_splits,
                                              float* y, float* lse, float* workspace, size_t workspace_floats,
                                              brn_mem loc, int device_ordinal, void* stream);
+/* The element type of a K / V pool.  bf16 and fp16 pools hold the 16-bit patterns of their elements. */
+typedef enum { BRN_KV_F32 = 0, BRN_KV_BF16 = 1, BRN_KV_F16 = 2 } brn_kv_type;
+/* brn_flash_attention_paged_forward over a pool stored in fp32, bf16 or fp16: a decode call's cost is the K / V bytes it reads, and a
+ * 16-bit pool holds twice the tokens and moves half the bytes.  Semantics, mask, clamps, plan, workspace layout, the defined empty row
+ * (y = 0, lse = -inf), the promise (allocates nothing, does not synchronise, may be captured) and every limit are those of
+ * brn_flash_attention_paged_forward; the arguments after kv_type are its arguments after v_pages, in its order.  What differs:
+ * k_pages, v_pages: [n_pages, page_size, kv_heads, head_dim] of the type kv_type (a brn_kv_type) names, where `loc` says.  q, y, lse and
+ * the workspace stay fp32.  BRN_KV_F32 runs brn_flash_attention_paged_forward's path and returns its bits.
+ * Which arithmetic (brn_set_op_compute, as in every attention entry) reads which pool: BRN_BF16 reads a bf16 pool and BRN_F16 an f16 pool,
+ * on the 16-bit kernels, and the elements go to the matrix instructions as stored, with no conversion; BRN_F32 and the three plane modes
+ * read either 16-bit pool on the exact fp32 kernel, widening each element exactly.  A bf16 pool in mode BRN_F16, or the reverse, is
+ * refused with a message that names both types: nothing is re-rounded silently.
+ * The promise added: a row carries the bits of brn_flash_attention_paged_forward in the same compute mode on the pool widened to fp32
+ * (y, lse and the partials in the workspace), because the 16-bit kernels round an fp32 pool to the type the 16-bit pool already holds.
+ * Limits (each violation is BRN_ERR_INVALID_ARG with the prefix "flash attention paged kv:" and a message naming the limit, checked
+ * before the device): every limit of brn_flash_attention_paged_forward; kv_type one of the three; the pairing of pool and compute mode
+ * above; BRN_MEM_DEVICE k_pages / v_pages 16-byte aligned whatever the type; the overlap rules count bytes.
+ * Not provided: fp8 / int8 or otherwise scaled pages; a K-transposed page layout; 16-bit q / y; 16-bit tensors for the dense, split and
+ * varlen entries; a window or a bias. */
+brn_status brn_flash_attention_paged_kv_forward(const float* q, const void* k_pages, const void* v_pages, int kv_type,
+                                                const int* block_table, const int* kv_lens,
+                                                int batch, int seq_q, int max_kv_len, int heads, int kv_heads, int head_dim,
+                                                int n_pages, int page_size, int max_pages,
+                                                int layout, int causal, float scale, int kv_splits,
+                                                float* y, float* lse, float* workspace, size_t workspace_floats,
+                                                brn_mem loc, int device_ordinal, void* stream);
+/* Appends seq_new new tokens to every sequence of a paged K / V cache (the pool, block table and lengths of the two paged attention
+ * entries) and moves the lengths on, all on the device: an append with kv_lens_out = kv_lens followed by a paged attention call is one
+ * whole decode step, and one captured graph.
+ * k_new, v_new: fp32, [batch, seq_new, kv_heads, head_dim] (layout BRN_ATTN_BSHD) or [batch, kv_heads, seq_new, head_dim] (BRN_ATTN_BHSD).
+ * k_pages, v_pages: the pool, [n_pages, page_size, kv_heads, head_dim] of kv_type (any brn_kv_type; BRN_KV_F32 is a plain scatter),
+ * written in place.  block_table [batch, max_pages] and kv_lens [batch]: int32, read as device data and clamped, never trusted.
+ * The rule: with cap = max_pages * page_size and L_b = min(max(kv_lens[b], 0), cap), token t of batch entry b becomes key L_b + t of
+ * sequence b: row (L_b + t) % page_size of page min(max(block_table[b][(L_b + t) / page_size], 0), n_pages - 1).  A token whose position
+ * is >= cap is dropped: nothing is written for it and no table entry is read for it.  No other row of the pool is written.
+ * kv_lens_out: [batch] int32 or NULL; it receives min(L_b + seq_new, cap).  It may be kv_lens itself: the lengths are written by a launch
+ * of their own after the rows, so the in-place form is well defined.  With NULL, kv_lens is left as it is.
+ * Two sequences whose tables name the same page at a written position are the caller's error: the content of that page is then
+ * unspecified, and nothing outside the pool is touched.
+ * Conversion: the cast the attention kernels apply to an fp32 pool, round to nearest even.  An element appended to a 16-bit pool is bit for
+ * bit what the fp32-pool kernel of that compute mode would have fed the matrix instructions, so append + attention over the 16-bit pool
+ * gives the bits of brn_flash_attention_paged_forward in that mode on an fp32 pool of the unrounded keys.  A value beyond the fp16 range
+ * becomes +-inf in an f16 pool, a NaN stays a NaN: documented, not trapped.
+ * With BRN_MEM_DEVICE the call allocates nothing, does not synchronise the stream and may be captured.  BRN_MEM_HOST is a test
+ * convenience: the WHOLE pool is staged to the device and copied back whole.
+ * Limits (BRN_ERR_INVALID_ARG, prefix "kv cache append:", checked before the device): no NULL but kv_lens_out; kv_type one of the three;
+ * head_dim 32, 64 or 128; batch >= 1, kv_heads >= 1; 1 <= seq_new <= 65536; layout 0 or 1; page_size 16, 32, 64, 128 or 256; n_pages >= 1,
+ * max_pages >= 1, n_pages * page_size < 2^31, max_pages * page_size < 2^31; seq_new * kv_heads * head_dim / 8 < 2^31; k_new, v_new,
+ * block_table and kv_lens do not overlap the pool, k_pages and v_pages not each other, kv_lens_out nothing but (wholly) kv_lens, sizes in
+ * bytes; BRN_MEM_DEVICE k_new, v_new, k_pages, v_pages 16-byte aligned, the int arrays 4-byte aligned.
+ * Not provided: a per-sequence number of new tokens (seq_new is one integer); copy-on-write or reference counting of shared pages;
+ * scaled (fp8 / int8) pages. */
+brn_status brn_kv_cache_append(const float* k_new, const float* v_new, int batch, int seq_new, int kv_heads, int head_dim, int layout,
+                               void* k_pages, void* v_pages, int kv_type,
+                               const int* block_table, const int* kv_lens, int* kv_lens_out,
+                               int n_pages, int page_size, int max_pages,
+                               brn_mem loc, int device_ordinal, void* stream);
 /* PatchMerging::forward (swin.rs:491-527): x [B,H*W,C] -> [B, ceil(H/2)*ceil(W/2), 2C]. */
 brn_status brn_patch_merging_forward(const float* x, int B, int H, int W, int C, const float* norm_g,
                                      const float* norm_b, const float* reduction_w, float* y, brn_mem loc,

@@ -50,8 +50,13 @@ and 256 keys, each with an identity table (the pool IS the dense tensor's memory
 lengths are device tensors; raw library calls on preallocated outputs.  Per paged side: its time over the dense side's, whether its median
 lies inside the dense side's round spread, and (equal lengths) whether it returned the dense call's bits.  Without --json the records go
 to profiles/flash_attention_paged_bench.json.
+--paged-kv16 times brn_flash_attention_paged_kv_forward on a bf16 / fp16 pool beside brn_flash_attention_paged_forward on the fp32 pool of
+the same values (the yardstick: the older entry's kernels, never the code under test), in the same compute mode, on the rows of --paged at
+page 64 with a shuffled table, for the pairs bf16 on bf16, f16 on f16 and f32 on bf16; then brn_kv_cache_append (64 x 1 and 16 x 512 new
+tokens, lengths in place) beside a device-to-device copy of the bytes it writes.  Same protocol; --row picks an attention row, --mode a
+pair by its compute mode.  Written to profiles/flash_attention_paged_kv16_bench.json.
 
-  python tools/bench_flash_attention.py [--bias | --gqa | --varlen | --splitkv | --paged] [--row N] [--mode f32|bf16|f16] [--json PATH]"""
+  python tools/bench_flash_attention.py [--bias | --gqa | --varlen | --splitkv | --paged | --paged-kv16] [--row N] [--mode f32|bf16|f16] [--json PATH]"""
 import argparse
 import json
 import os
@@ -79,6 +84,13 @@ SPLITKV_JSON = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__fi
 PAGED_ROWS = [(16, 1, 4096, 32, 8, 128, 0, 0), (1, 1, 32768, 32, 8, 128, 0, 0), (64, 1, 4096, 32, 8, 128, 0, 0), (1, 8, 16384, 32, 8, 128, 1, 0),
               (16, 1, 4096, 32, 8, 128, 0, 1)]
 PAGED_PAGES = [16, 64, 256]
+# --paged-kv16: the rows above at page 64 with a shuffled table, per (compute mode, pool type) pair; then the append:
+# (batch, seq_new, kv_heads, head_dim, page_size, pages per sequence): a decode step and a prefill chunk
+PAGED_KV16_PAGE = 64
+PAGED_KV16_PAIRS = [("bf16", "bf16"), ("f16", "f16"), ("f32", "bf16")]
+KV_APPEND_ROWS = [(64, 1, 8, 128, 64, 64), (16, 512, 8, 128, 64, 64)]
+KV_APPEND_TYPES = ["bf16", "f16", "f32"]
+PAGED_KV16_JSON = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "flash_attention_paged_kv16_bench.json")
 PAGED_JSON = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "flash_attention_paged_bench.json")
 HBM_BYTES_PER_S = 8.0e12
 MODES = ["f32", "bf16", "f16"]
@@ -483,6 +495,105 @@ def bench_paged(row, mode):
     return out
 
 
+def bench_paged_kv16(row, pair):
+    """brn_flash_attention_paged_kv_forward on a 16-bit pool beside brn_flash_attention_paged_forward (the yardstick, the parent's kernels)
+    on the fp32 pool of the same logical data, in the same compute mode; page 64, shuffled table"""
+    import torch
+    import candle_birefnet_amd as cb
+    from candle_birefnet_amd import ops
+    lib = cb._ffi.lib
+    mode, kv = pair
+    batch, seq_q, seq_kv, heads, kv_heads, hd, causal, ragged = row
+    page = PAGED_KV16_PAGE
+    tdt = torch.bfloat16 if kv == "bf16" else torch.float16
+    g = torch.Generator(device="cuda").manual_seed(1)
+    q = torch.randn(batch, seq_q, heads, hd, device="cuda", generator=g)
+    lens_h = [512 + (seq_kv - 512) * b // (batch - 1) for b in range(batch)] if ragged else [seq_kv] * batch
+    lens = torch.tensor(lens_h, dtype=torch.int32, device="cuda")
+    n_pages, max_pages = batch * seq_kv // page, seq_kv // page
+    perm = torch.randperm(n_pages, device="cuda", generator=g)
+    table = perm.to(torch.int32).view(batch, max_pages).contiguous()
+    # the 16-bit pool, and the fp32 pool holding the same values: one logical cache, two storage types
+    pools16 = [torch.randn(n_pages, page, kv_heads, hd, device="cuda", generator=g).to(tdt) for _ in range(2)]
+    pools32 = [a.float() for a in pools16]
+    stream = torch.cuda.current_stream().cuda_stream
+    R = batch * heads * seq_q
+    S, tps, need = ops.flash_attention_splitkv_plan(batch, seq_q, seq_kv, heads, kv_heads, hd, 0)
+    outs = [(torch.empty_like(q), torch.empty(R, device="cuda"), torch.empty(max(need, 4), device="cuda")) for _ in range(2)]
+    tail = (table.data_ptr(), lens.data_ptr(), batch, seq_q, seq_kv, heads, kv_heads, hd, n_pages, page, max_pages, 0, causal, 0.0, 0)
+
+    def fp32_pool():
+        y, lse, ws = outs[0]
+        cb._ffi.check(lib.brn_flash_attention_paged_forward(q.data_ptr(), pools32[0].data_ptr(), pools32[1].data_ptr(), *tail, y.data_ptr(), lse.data_ptr(), ws.data_ptr(), need, 1, 0, stream))
+        return y
+
+    def kv16_pool():
+        y, lse, ws = outs[1]
+        cb._ffi.check(lib.brn_flash_attention_paged_kv_forward(q.data_ptr(), pools16[0].data_ptr(), pools16[1].data_ptr(), cb._ffi.BRN_KV_BF16 if kv == "bf16" else cb._ffi.BRN_KV_F16,
+                                                               *tail, y.data_ptr(), lse.data_ptr(), ws.data_ptr(), need, 1, 0, stream))
+        return y
+
+    ops.set_compute(mode)
+    try:
+        t32, t16 = _time_alternating([fp32_pool, kv16_pool])
+        assert bool(torch.isfinite(t32[4]).all()) and bool(torch.isfinite(t16[4]).all())
+        keys = sum(lens_h) * kv_heads * hd
+        rec = {"batch": batch, "seq_q": seq_q, "max_kv_len": seq_kv, "kv_lens": "all max_kv_len" if not ragged else lens_h, "heads": heads, "kv_heads": kv_heads,
+               "head_dim": hd, "mode": mode, "kv_type": kv, "page_size": page, "table": "shuffled", "causal": causal, "S": S, "tiles_per_split": tps,
+               "fp32_pool_kv_bytes": 2 * 4 * keys, "kv16_pool_kv_bytes": 2 * 2 * keys,
+               "kv16_over_fp32": round(t16[0] / t32[0], 4), "kv16_below_lowest_fp32_round_median": bool(t16[0] < t32[2]),
+               "same_bits": bool(torch.equal(t16[4], t32[4])),
+               "fp32_pool_tb_per_s": round(2 * 4 * keys / (t32[0] * 1e-3) / 1e12, 3), "kv16_pool_tb_per_s": round(2 * 2 * keys / (t16[0] * 1e-3) / 1e12, 3)}
+        rec.update(_side("fp32_pool", t32))
+        rec.update(_side("kv16_pool", t16))
+        print(f"{batch:3d} x {seq_q:2d} / {seq_kv:5d}{' ragged' if ragged else ''} x {heads} / {kv_heads} x {hd} {mode:4s} on {kv:4s} causal {causal} S {S}: "
+              f"fp32 pool {t32[0]:8.4f} ms [{t32[2]:.4f} .. {t32[3]:.4f}] {rec['fp32_pool_tb_per_s']:.2f} TB/s | {kv} pool {t16[0]:8.4f} ms [{t16[2]:.4f} .. {t16[3]:.4f}] "
+              f"{rec['kv16_pool_tb_per_s']:.2f} TB/s x{rec['kv16_over_fp32']:.3f} below the fp32 side's lowest round {rec['kv16_below_lowest_fp32_round_median']} bits {rec['same_bits']}", flush=True)
+    finally:
+        ops.set_compute("f32")
+    del q, pools16, pools32, outs
+    torch.cuda.empty_cache()
+    return [rec]
+
+
+def bench_kv_append(row, kv):
+    """brn_kv_cache_append (rows + lengths, in place) beside a device-to-device copy of the bytes it writes, the bandwidth floor"""
+    import torch
+    import candle_birefnet_amd as cb
+    lib = cb._ffi.lib
+    batch, seq_new, kv_heads, hd, page, pages_per_seq = row
+    tdt = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}[kv]
+    g = torch.Generator(device="cuda").manual_seed(2)
+    k_new, v_new = (torch.randn(batch, seq_new, kv_heads, hd, device="cuda", generator=g) for _ in range(2))
+    n_pages = batch * pages_per_seq
+    kp, vp = (torch.zeros(n_pages, page, kv_heads, hd, device="cuda", dtype=tdt) for _ in range(2))
+    table = torch.randperm(n_pages, device="cuda", generator=g).to(torch.int32).view(batch, pages_per_seq).contiguous()
+    start = torch.full((batch,), page * pages_per_seq // 2 - 1, dtype=torch.int32, device="cuda")       # the first token lands on a page's last row
+    lens = start.clone()
+    stream = torch.cuda.current_stream().cuda_stream
+    src, dst = (torch.empty(2 * batch * seq_new * kv_heads * hd, device="cuda", dtype=tdt) for _ in range(2))
+
+    def append():
+        lens.copy_(start)
+        cb._ffi.check(lib.brn_kv_cache_append(k_new.data_ptr(), v_new.data_ptr(), batch, seq_new, kv_heads, hd, 0, kp.data_ptr(), vp.data_ptr(),
+                                              {"f32": 0, "bf16": 1, "f16": 2}[kv], table.data_ptr(), lens.data_ptr(), lens.data_ptr(), n_pages, page, pages_per_seq, 1, 0, stream))
+        return kp
+
+    def copy():
+        lens.copy_(start)
+        dst.copy_(src)
+        return dst
+
+    ta, tc = _time_alternating([append, copy])
+    rec = {"batch": batch, "seq_new": seq_new, "kv_heads": kv_heads, "head_dim": hd, "page_size": page, "kv_type": kv, "bytes_written": src.numel() * src.element_size(),
+           "bytes_read": 2 * 4 * batch * seq_new * kv_heads * hd, "append_over_copy": round(ta[0] / tc[0], 3), "note": "both sides include one copy of the lengths (batch ints)"}
+    rec.update(_side("append", ta))
+    rec.update(_side("copy", tc))
+    print(f"append {batch:3d} x {seq_new:3d} x {kv_heads} x {hd} -> {kv:4s}: {ta[0]:.4f} ms [{ta[2]:.4f} .. {ta[3]:.4f}] | copy of {rec['bytes_written']} bytes {tc[0]:.4f} ms "
+          f"[{tc[2]:.4f} .. {tc[3]:.4f}] x{rec['append_over_copy']:.2f}", flush=True)
+    return [rec]
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--bias", action="store_true", help="time brn_flash_attention_bias_forward beside the bias-free call and torch + bias")
@@ -490,6 +601,7 @@ if __name__ == "__main__":
     ap.add_argument("--varlen", action="store_true", help="time brn_flash_attention_varlen_forward: windows, a ragged pack, a uniform pack, beside the gqa entry")
     ap.add_argument("--splitkv", action="store_true", help="time brn_flash_attention_splitkv_forward at kv_splits 1 .. 64 and 0 beside the gqa entry")
     ap.add_argument("--paged", action="store_true", help="time brn_flash_attention_paged_forward (pages of 16 / 64 / 256, identity and shuffled tables) beside the split entry")
+    ap.add_argument("--paged-kv16", action="store_true", help="time brn_flash_attention_paged_kv_forward on 16-bit pools beside the fp32-pool entry, and brn_kv_cache_append beside a copy")
     ap.add_argument("--row", type=int, choices=range(len(BIAS_ROWS)))
     ap.add_argument("--mode", choices=MODES)
     ap.add_argument("--json", help="write the records to this file")
@@ -498,8 +610,22 @@ if __name__ == "__main__":
     if cb.device_count() < 1:
         sys.exit("no HIP device: nothing is measured")
     recs = []
-    if a.bias + a.gqa + a.varlen + a.splitkv + a.paged > 1:
-        sys.exit("--bias, --gqa, --varlen, --splitkv and --paged are separate tables: one at a time")
+    if a.bias + a.gqa + a.varlen + a.splitkv + a.paged + a.paged_kv16 > 1:
+        sys.exit("--bias, --gqa, --varlen, --splitkv, --paged and --paged-kv16 are separate tables: one at a time")
+    if a.paged_kv16:
+        for row in (PAGED_ROWS if a.row is None else [PAGED_ROWS[a.row]] if a.row < len(PAGED_ROWS) else sys.exit(f"--row {a.row}: only {len(PAGED_ROWS)} rows in this table")):
+            for pair in PAGED_KV16_PAIRS:
+                if a.mode is None or pair[0] == a.mode:
+                    recs += bench_paged_kv16(row, pair)
+        appends = []
+        if a.row is None:
+            for row in KV_APPEND_ROWS:
+                for kv in KV_APPEND_TYPES:
+                    appends += bench_kv_append(row, kv)
+        with open(a.json or PAGED_KV16_JSON, "w") as f:
+            json.dump({"tool": "tools/bench_flash_attention.py --paged-kv16", "warmup": GQA_WARMUP, "timed": GQA_ROUNDS * GQA_TIMED, "rows": recs, "append": appends}, f, indent=1)
+            f.write("\n")
+        sys.exit(0)
     rows = BIAS_ROWS if a.bias else GQA_ROWS if a.gqa else VARLEN_GROUPS if a.varlen else SPLITKV_ROWS if a.splitkv else PAGED_ROWS if a.paged else ROWS
     if a.row is not None and a.row >= len(rows):
         sys.exit(f"--row {a.row}: only {len(rows)} rows in this table")
