@@ -119,6 +119,9 @@ _sig("brn_flash_attention_paged_forward", C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_
 _sig("brn_flash_attention_paged_kv_forward", C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
      C.c_int, C.c_float, C.c_int, _vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp)
 _sig("brn_kv_cache_append", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp)
+_sig("brn_flash_attention_paged_fp8_forward", C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+     C.c_int, C.c_float, C.c_int, _vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp)
+_sig("brn_kv_cache_append_fp8", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp)
 _sig("brn_patch_merging_forward", C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp)
 _sig("brn_deform_conv2d_forward", C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int,
      C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp)
@@ -144,7 +147,7 @@ DECLARED = [
     "brn_forward", "brn_model_backbone_forward", "brn_model_squeeze_forward", "brn_model_decoder_forward",
     "brn_model_set_streams", "brn_model_set_profiling", "brn_model_last_timings", "brn_model_last_kernel_stats", "brn_kernel_family_name",
     "brn_swin_create", "brn_swin_destroy", "brn_swin_forward", "brn_linear_forward", "brn_linear_residual_layer_norm_forward", "brn_layer_norm_forward",
-    "brn_conv2d_forward", "brn_upsample_bilinear2d", "brn_window_attention_forward", "brn_attention_forward", "brn_flash_attention_forward", "brn_flash_attention_bias_forward", "brn_flash_attention_gqa_forward", "brn_flash_attention_varlen_forward", "brn_flash_attention_splitkv_plan", "brn_flash_attention_splitkv_forward", "brn_flash_attention_paged_forward", "brn_flash_attention_paged_kv_forward", "brn_kv_cache_append", "brn_patch_merging_forward",
+    "brn_conv2d_forward", "brn_upsample_bilinear2d", "brn_window_attention_forward", "brn_attention_forward", "brn_flash_attention_forward", "brn_flash_attention_bias_forward", "brn_flash_attention_gqa_forward", "brn_flash_attention_varlen_forward", "brn_flash_attention_splitkv_plan", "brn_flash_attention_splitkv_forward", "brn_flash_attention_paged_forward", "brn_flash_attention_paged_kv_forward", "brn_kv_cache_append", "brn_flash_attention_paged_fp8_forward", "brn_kv_cache_append_fp8", "brn_patch_merging_forward",
     "brn_deform_conv2d_forward", "brn_deform_conv2d_offsets_forward", "brn_aspp_deformable_forward", "brn_decblk_forward", "brn_set_op_compute", "brn_preprocess_image", "brn_postprocess_mask", "brn_infer_images_u8",
 ]
 

@@ -231,7 +231,13 @@ struct FlashAttentionParams {
     // fp16 elements (16-bit patterns; every stride and page_stride still counts ELEMENTS), read as stored by the 16-bit kernel of the same
     // type (s16 == kv_type) or widened exactly by the fp32 kernel (s16 == 0); any other pairing is refused.  Read by the launcher alone
     int kv_type;
+    // brn_flash_attention_paged_fp8_forward: kv_type 3 (with a table only; any s16).  k and v point at a pool of OCP e4m3fn BYTES (strides
+    // and page_stride still count elements), widened exactly to the kernel's own type as they are staged.  k_scale, v_scale: [kv_heads]
+    // fp32 on the device, or null = all ones; device data like the table: read by the kernels alone, no address depends on them.  K / V
+    // head g's workgroups run with scale * k_scale[g] in the place of scale, and a row's final y is multiplied by v_scale[g] once
+    const float* k_scale; const float* v_scale;
 };
+constexpr int FA_KV_FP8 = 3;      // FlashAttentionParams::kv_type / KvAppendParams::kv_type of an e4m3fn pool (not a brn_kv_type: the public enum keeps its three values)
 hipError_t launch_flash_attention(const FlashAttentionParams& p, hipStream_t s);
 
 // brn_kv_cache_append (kernels/kv_cache.hip): token t of batch entry b becomes key min(max(kv_lens[b], 0), cap) + t of sequence b in the
@@ -249,6 +255,9 @@ struct KvAppendParams {
     long kv_ss, page_stride;                  // elements between two rows of a page (kv_heads * head_dim) and between two pages
     int page_log2, n_pages, max_pages;
     int cap;                                  // max_pages * page_size < 2^31
+    // brn_kv_cache_append_fp8: kv_type FA_KV_FP8, an e4m3fn pool of bytes.  An element x of K head h is stored as the byte of
+    // clamp(x / k_scale[h], +-448) rounded to nearest even (v_scale for V); [kv_heads] fp32 on the device, or null = all ones
+    const float* k_scale; const float* v_scale;
 };
 hipError_t launch_kv_cache_append(const KvAppendParams& p, hipStream_t s);
 

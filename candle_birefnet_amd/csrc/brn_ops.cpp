@@ -511,9 +511,10 @@ brn_status brn_flash_attention_splitkv_forward(const float* q, const float* k, c
 // seq_kv = max_kv_len.  block_table and kv_lens are never read on the host for BRN_MEM_DEVICE: nothing here depends on their content, and
 // the call allocates nothing and does not synchronise (Staging has nothing to stage), so it may be captured into a graph.
 // One body for brn_flash_attention_paged_forward (kv_type BRN_KV_F32) and brn_flash_attention_paged_kv_forward: the pool's element size is
-// the only thing that differs on the host, so the overlap checks count bytes.
+// the only thing that differs on the host, so the overlap checks count bytes.  brn_flash_attention_paged_fp8_forward (fp8 = true: an
+// e4m3fn pool of bytes, FA_KV_FP8 to the launcher, never a brn_kv_type) adds the two scale arrays, which are inputs like the table.
 static const char* const KV_TYPE_NAME[3] = {"f32", "bf16", "f16"};
-static size_t kv_type_bytes(int kv_type) { return kv_type == BRN_KV_F32 ? 4 : 2; }
+static size_t kv_type_bytes(int kv_type) { return kv_type == BRN_KV_F32 ? 4 : kv_type == FA_KV_FP8 ? 1 : 2; }
 static void kv_type_check(const char* who, int kv_type) {
     if (kv_type != BRN_KV_F32 && kv_type != BRN_KV_BF16 && kv_type != BRN_KV_F16)
         fail(BRN_ERR_INVALID_ARG, "%s: kv_type %d unknown (kv_type must be 0 = f32, 1 = bf16 or 2 = f16)", who, kv_type);
@@ -529,15 +530,17 @@ static int paged_pool_check(const char* who, int n_pages, int page_size, int max
         fail(BRN_ERR_INVALID_ARG, "%s: n_pages %d of page_size %d too large (n_pages * page_size < 2^31)", who, n_pages, page_size);
     return page_log2;
 }
-static void flash_attention_paged_body(const char* who, const float* q, const void* k_pages, const void* v_pages, int kv_type, const int* block_table,
+static void flash_attention_paged_body(const char* who, const float* q, const void* k_pages, const void* v_pages, int kv_type, bool fp8, const float* k_scale,
+                                       const float* v_scale, const int* block_table,
                                        const int* kv_lens, int batch, int seq_q, int max_kv_len, int heads, int kv_heads, int head_dim, int n_pages,
                                        int page_size, int max_pages, int layout, int causal, float scale, int kv_splits, float* y, float* lse,
                                        float* workspace, size_t workspace_floats, brn_mem loc, int device, void* stream) {
     if (!q || !k_pages || !v_pages || !y) fail(BRN_ERR_INVALID_ARG, "%s: null q, k_pages, v_pages or y", who);
     if (!block_table || !kv_lens) fail(BRN_ERR_INVALID_ARG, "%s: null block_table or kv_lens", who);
-    kv_type_check(who, kv_type);
+    if (fp8) kv_type = FA_KV_FP8;
+    else kv_type_check(who, kv_type);
     const int s16 = attention_op_s16();
-    if (kv_type != BRN_KV_F32 && s16 && s16 != kv_type)
+    if (!fp8 && kv_type != BRN_KV_F32 && s16 && s16 != kv_type)
         fail(BRN_ERR_INVALID_ARG, "%s: kv_type %s cannot be read in compute mode %s (a 16-bit compute mode reads a pool of its own type; the fp32-class modes read bf16 and f16 pools alike)",
              who, KV_TYPE_NAME[kv_type], KV_TYPE_NAME[s16]);
     const int page_log2 = paged_pool_check(who, n_pages, page_size, max_pages);
@@ -559,8 +562,9 @@ static void flash_attention_paged_body(const char* who, const float* q, const vo
         fail(BRN_ERR_INVALID_ARG, "%s: workspace %s for %d splits (it must hold S * batch * heads * seq_q * (head_dim + 1) = %zu floats, workspace_floats %zu)",
              who, workspace ? "too small" : "is NULL", pl.S, need, workspace_floats);
     float* const ws = need ? workspace : nullptr;
-    // sizes in bytes: the table and the lengths are ints, the pool's elements 4 or 2 bytes
-    const struct { const void* p; size_t n; } ins[] = {{q, nq * 4}, {k_pages, pool_floats * 4}, {v_pages, pool_floats * 4}, {block_table, ntab * 4}, {kv_lens, (size_t)batch * 4}};
+    // sizes in bytes: the table and the lengths are ints, the pool's elements 4, 2 or 1 bytes (a null scale array overlaps nothing)
+    const struct { const void* p; size_t n; } ins[] = {{q, nq * 4}, {k_pages, pool_floats * 4}, {v_pages, pool_floats * 4}, {block_table, ntab * 4}, {kv_lens, (size_t)batch * 4},
+                                                       {k_scale, (size_t)kv_heads * 4}, {v_scale, (size_t)kv_heads * 4}};
     const struct { const float* p; size_t n; const char* name; } outs[] = {{y, nq * 4, "y"}, {lse, lse ? R * 4 : 0, "lse"}, {ws, need * 4, "workspace"}};
     for (int a = 0; a < 3; ++a) {
         if (!outs[a].p) continue;
@@ -574,9 +578,13 @@ static void flash_attention_paged_body(const char* who, const float* q, const vo
         fail(BRN_ERR_INVALID_ARG, "%s: device q, k_pages, v_pages, y, lse and workspace must be 16-byte aligned", who);
     if (loc == BRN_MEM_DEVICE && ((reinterpret_cast<uintptr_t>(block_table) | reinterpret_cast<uintptr_t>(kv_lens)) & 3))
         fail(BRN_ERR_INVALID_ARG, "%s: device block_table and kv_lens must be 4-byte aligned", who);
+    if (loc == BRN_MEM_DEVICE && ((reinterpret_cast<uintptr_t>(k_scale) | reinterpret_cast<uintptr_t>(v_scale)) & 3))
+        fail(BRN_ERR_INVALID_ARG, "%s: device k_scale and v_scale must be 4-byte aligned", who);
     ensure_device(device);
     Staging st(stream, loc);
     FlashAttentionParams p{};
+    if (k_scale) p.k_scale = st.in(k_scale, (size_t)kv_heads);
+    if (v_scale) p.v_scale = st.in(v_scale, (size_t)kv_heads);
     p.q = st.in(q, nq); p.k = st.in(static_cast<const float*>(k_pages), pool_floats); p.v = st.in(static_cast<const float*>(v_pages), pool_floats);
     p.block_table = reinterpret_cast<const int*>(st.in(reinterpret_cast<const float*>(block_table), ntab));
     p.kv_lens = reinterpret_cast<const int*>(st.in(reinterpret_cast<const float*>(kv_lens), (size_t)batch));
@@ -607,7 +615,7 @@ brn_status brn_flash_attention_paged_forward(const float* q, const float* k_page
                                              int layout, int causal, float scale, int kv_splits, float* y, float* lse, float* workspace,
                                              size_t workspace_floats, brn_mem loc, int device, void* stream) {
     return guarded([&] {
-        flash_attention_paged_body("flash attention paged", q, k_pages, v_pages, BRN_KV_F32, block_table, kv_lens, batch, seq_q, max_kv_len, heads, kv_heads, head_dim,
+        flash_attention_paged_body("flash attention paged", q, k_pages, v_pages, BRN_KV_F32, false, nullptr, nullptr, block_table, kv_lens, batch, seq_q, max_kv_len, heads, kv_heads, head_dim,
                                    n_pages, page_size, max_pages, layout, causal, scale, kv_splits, y, lse, workspace, workspace_floats, loc, device, stream);
     });
 }
@@ -617,22 +625,33 @@ brn_status brn_flash_attention_paged_kv_forward(const float* q, const void* k_pa
                                                 int n_pages, int page_size, int max_pages, int layout, int causal, float scale, int kv_splits, float* y,
                                                 float* lse, float* workspace, size_t workspace_floats, brn_mem loc, int device, void* stream) {
     return guarded([&] {
-        flash_attention_paged_body("flash attention paged kv", q, k_pages, v_pages, kv_type, block_table, kv_lens, batch, seq_q, max_kv_len, heads, kv_heads, head_dim,
-                                   n_pages, page_size, max_pages, layout, causal, scale, kv_splits, y, lse, workspace, workspace_floats, loc, device, stream);
+        flash_attention_paged_body("flash attention paged kv", q, k_pages, v_pages, kv_type, false, nullptr, nullptr, block_table, kv_lens, batch, seq_q, max_kv_len, heads,
+                                   kv_heads, head_dim, n_pages, page_size, max_pages, layout, causal, scale, kv_splits, y, lse, workspace, workspace_floats, loc, device, stream);
+    });
+}
+
+brn_status brn_flash_attention_paged_fp8_forward(const float* q, const void* k_pages, const void* v_pages, const float* k_scale, const float* v_scale,
+                                                 const int* block_table, const int* kv_lens, int batch, int seq_q, int max_kv_len, int heads, int kv_heads,
+                                                 int head_dim, int n_pages, int page_size, int max_pages, int layout, int causal, float scale, int kv_splits,
+                                                 float* y, float* lse, float* workspace, size_t workspace_floats, brn_mem loc, int device, void* stream) {
+    return guarded([&] {
+        flash_attention_paged_body("flash attention paged fp8", q, k_pages, v_pages, FA_KV_FP8, true, k_scale, v_scale, block_table, kv_lens, batch, seq_q, max_kv_len, heads,
+                                   kv_heads, head_dim, n_pages, page_size, max_pages, layout, causal, scale, kv_splits, y, lse, workspace, workspace_floats, loc, device, stream);
     });
 }
 
 // seq_new tokens per sequence into the pool, behind the keys each sequence has (kernels/kv_cache.hip).  Like the paged attention entries it
 // reads neither block_table nor kv_lens on the host for BRN_MEM_DEVICE, allocates nothing and does not synchronise.  BRN_MEM_HOST (a test
 // convenience) stages the whole pool up and copies it back whole.
-brn_status brn_kv_cache_append(const float* k_new, const float* v_new, int batch, int seq_new, int kv_heads, int head_dim, int layout, void* k_pages,
-                               void* v_pages, int kv_type, const int* block_table, const int* kv_lens, int* kv_lens_out, int n_pages, int page_size,
-                               int max_pages, brn_mem loc, int device, void* stream) {
-    return guarded([&] {
-        const char* who = "kv cache append";
+// One body for brn_kv_cache_append and brn_kv_cache_append_fp8 (fp8 = true: an e4m3fn pool of bytes and the two scale arrays).
+static void kv_cache_append_body(const char* who, const float* k_new, const float* v_new, int batch, int seq_new, int kv_heads, int head_dim, int layout, void* k_pages,
+                                 void* v_pages, int kv_type, bool fp8, const float* k_scale, const float* v_scale, const int* block_table, const int* kv_lens,
+                                 int* kv_lens_out, int n_pages, int page_size, int max_pages, brn_mem loc, int device, void* stream) {
+    {
         if (!k_new || !v_new || !k_pages || !v_pages) fail(BRN_ERR_INVALID_ARG, "%s: null k_new, v_new, k_pages or v_pages", who);
         if (!block_table || !kv_lens) fail(BRN_ERR_INVALID_ARG, "%s: null block_table or kv_lens", who);
-        kv_type_check(who, kv_type);
+        if (fp8) kv_type = FA_KV_FP8;
+        else kv_type_check(who, kv_type);
         if (!(head_dim == 32 || head_dim == 64 || head_dim == 128))
             fail(BRN_ERR_INVALID_ARG, "%s: head_dim %d unsupported (head_dim must be 32, 64 or 128)", who, head_dim);
         if (batch < 1 || kv_heads < 1) fail(BRN_ERR_INVALID_ARG, "%s: batch %d, kv_heads %d unsupported (batch >= 1, kv_heads >= 1)", who, batch, kv_heads);
@@ -648,7 +667,8 @@ brn_status brn_kv_cache_append(const float* k_new, const float* v_new, int batch
         const size_t nnew = (size_t)batch * seq_new * kv_heads * head_dim, npool = (size_t)n_pages * page_size * kv_heads * head_dim;
         const size_t pool_floats = npool * kv_type_bytes(kv_type) / 4, ntab = (size_t)batch * max_pages;
         const struct { const void* p; size_t n; const char* name; } ins[] = {{k_new, nnew * 4, "k_new"}, {v_new, nnew * 4, "v_new"}, {block_table, ntab * 4, "block_table"},
-                                                                             {kv_lens, (size_t)batch * 4, "kv_lens"}};
+                                                                             {kv_lens, (size_t)batch * 4, "kv_lens"}, {k_scale, (size_t)kv_heads * 4, "k_scale"},
+                                                                             {v_scale, (size_t)kv_heads * 4, "v_scale"}};
         for (const auto& in : ins)
             if (bytes_overlap(in.p, in.n, k_pages, pool_floats * 4) || bytes_overlap(in.p, in.n, v_pages, pool_floats * 4))
                 fail(BRN_ERR_INVALID_ARG, "%s: %s must not overlap the pool", who, in.name);
@@ -664,9 +684,13 @@ brn_status brn_kv_cache_append(const float* k_new, const float* v_new, int batch
             fail(BRN_ERR_INVALID_ARG, "%s: device k_new, v_new, k_pages and v_pages must be 16-byte aligned", who);
         if (loc == BRN_MEM_DEVICE && ((reinterpret_cast<uintptr_t>(block_table) | reinterpret_cast<uintptr_t>(kv_lens) | reinterpret_cast<uintptr_t>(kv_lens_out)) & 3))
             fail(BRN_ERR_INVALID_ARG, "%s: device block_table, kv_lens and kv_lens_out must be 4-byte aligned", who);
+        if (loc == BRN_MEM_DEVICE && ((reinterpret_cast<uintptr_t>(k_scale) | reinterpret_cast<uintptr_t>(v_scale)) & 3))
+            fail(BRN_ERR_INVALID_ARG, "%s: device k_scale and v_scale must be 4-byte aligned", who);
         ensure_device(device);
         Staging st(stream, loc);
         KvAppendParams p{};
+        if (k_scale) p.k_scale = st.in(k_scale, (size_t)kv_heads);
+        if (v_scale) p.v_scale = st.in(v_scale, (size_t)kv_heads);
         p.k_new = st.in(k_new, nnew); p.v_new = st.in(v_new, nnew);
         if (loc == BRN_MEM_DEVICE) { p.k_pages = k_pages; p.v_pages = v_pages; }
         else {
@@ -692,6 +716,24 @@ brn_status brn_kv_cache_append(const float* k_new, const float* v_new, int batch
         p.page_log2 = page_log2; p.n_pages = n_pages; p.max_pages = max_pages; p.cap = max_pages * page_size;
         BRN_HIP(launch_kv_cache_append(p, (hipStream_t)stream));
         st.finish();
+    }
+}
+
+brn_status brn_kv_cache_append(const float* k_new, const float* v_new, int batch, int seq_new, int kv_heads, int head_dim, int layout, void* k_pages,
+                               void* v_pages, int kv_type, const int* block_table, const int* kv_lens, int* kv_lens_out, int n_pages, int page_size,
+                               int max_pages, brn_mem loc, int device, void* stream) {
+    return guarded([&] {
+        kv_cache_append_body("kv cache append", k_new, v_new, batch, seq_new, kv_heads, head_dim, layout, k_pages, v_pages, kv_type, false, nullptr, nullptr, block_table,
+                             kv_lens, kv_lens_out, n_pages, page_size, max_pages, loc, device, stream);
+    });
+}
+
+brn_status brn_kv_cache_append_fp8(const float* k_new, const float* v_new, int batch, int seq_new, int kv_heads, int head_dim, int layout, void* k_pages,
+                                   void* v_pages, const float* k_scale, const float* v_scale, const int* block_table, const int* kv_lens, int* kv_lens_out,
+                                   int n_pages, int page_size, int max_pages, brn_mem loc, int device, void* stream) {
+    return guarded([&] {
+        kv_cache_append_body("kv cache append fp8", k_new, v_new, batch, seq_new, kv_heads, head_dim, layout, k_pages, v_pages, FA_KV_FP8, true, k_scale, v_scale, block_table,
+                             kv_lens, kv_lens_out, n_pages, page_size, max_pages, loc, device, stream);
     });
 }
 

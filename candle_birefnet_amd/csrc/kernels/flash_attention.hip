@@ -82,6 +82,12 @@
 // LDS.  What reaches LDS is what KV = float puts there from the pool widened to fp32 ((E)(float)e == e), so a row carries those bits.
 // The table-entry schedule, the clamps and the zero-select are FA_PAGED's; every instantiation with KV = float is the kernel it was,
 // instruction for instruction.  DESIGN.md 3.2j.
+// KV = fa_e4m3 (brn_flash_attention_paged_fp8_forward): the pool holds OCP e4m3fn BYTES with one fp32 scale per K / V head.  Both kernels
+// read 8 bytes per (key, 8 d) with the 16-bit pools' staging maps and widen them in registers, exactly, to the type their LDS image
+// holds (v_cvt_pk_f32_fp8, then the kernel's own cast: every e4m3 value is a bf16, an fp16 and an fp32 value), so LDS and everything
+// after it see the fp32 pool of the widened bytes.  k_scale[g] joins the score scale once per workgroup (fl32(scale * k_scale[g]) where
+// the other forms have scale), v_scale[g] multiplies a row's final y once: in fa_finish_split when S == 1, in
+// flash_split_combine_kernel<true, true> when S > 1; partials and lse never see v_scale.  DESIGN.md 3.2k.
 #include "../brn_kernels.h"
 #include "../brn_flash_varlen_plan.h"
 #include "attention_mfma.h"
@@ -390,8 +396,9 @@ __device__ __forceinline__ void fa_finish(float* yrow, int g, const f32x4 (&o)[N
 // under the causal mask, or a workgroup with nothing to walk) stores 0 and -inf: inv is SELECTED to 0, 0 * inf is never computed.
 // S > 1 (p.o_part): row r = (batch entry * heads + head) * seq_q + query of the workspace's O_part[split] and lse2_part[split], 64-bit
 // offsets.  S == 1: the row of y, and lse[r] = ln 2 * (m + log2 l) where lse is wanted.
-template <int D>
-__device__ __forceinline__ void fa_finish_split(const FlashAttentionParams& p, const FaBlock& blk, const FaLane& ln, int g, const f32x4 (&o)[D / 16], float l, float m) {
+// VS (the fp8 pool): the S == 1 row of y is fl32(vs * fl32(o * inv)), vs = v_scale of the workgroup's K / V head; a partial is not scaled.
+template <int D, bool VS = false>
+__device__ __forceinline__ void fa_finish_split(const FlashAttentionParams& p, const FaBlock& blk, const FaLane& ln, int g, const f32x4 (&o)[D / 16], float l, float m, float vs = 1.f) {
     const float lsum = att_group_sum(l);
     const bool empty = !(lsum > 0.f);
     const float inv = empty ? 0.f : 1.0f / lsum;
@@ -410,6 +417,14 @@ __device__ __forceinline__ void fa_finish_split(const FlashAttentionParams& p, c
         ldst = p.lse ? p.lse + r : nullptr;
         lv = lse2 * 0.6931471805599453f;
     }
+    if constexpr (VS) {
+        if (!p.o_part) {
+#pragma unroll
+            for (int dt = 0; dt < D / 16; ++dt) *reinterpret_cast<f32x4*>(dst + g * 4 + dt * 16) = (o[dt] * inv) * vs;
+            if (g == 0 && ldst) *ldst = lv;
+            return;
+        }
+    }
 #pragma unroll
     for (int dt = 0; dt < D / 16; ++dt) att_store_o(dst + g * 4, dt, o[dt], inv);
     if (g == 0 && ldst) *ldst = lv;
@@ -425,6 +440,22 @@ __device__ __forceinline__ float fa_widen(KV e) {
     if constexpr (std::is_same<KV, __bf16>::value) return __builtin_bit_cast(float, (unsigned)__builtin_bit_cast(unsigned short, e) << 16);
     else return (float)e;
 }
+// ---- KV = fa_e4m3: a pool of OCP e4m3fn bytes (bias 7, max 448, no infinities, NaN = 0x7F / 0xFF), read 8 bytes = 8 d of one key at a
+// time.  fa_fp8_widen8: the 8 bytes as fp32, exactly (v_cvt_pk_f32_fp8, two bytes each).  fa_fp8_heads: the workgroup's K / V head and
+// its two scales (null = 1), two scalar loads; no address is formed from either value. ----
+typedef unsigned char fa_e4m3;
+__device__ __forceinline__ void fa_fp8_widen8(const vec8<fa_e4m3> b, f32x4& lo, f32x4& hi) {
+    const vec2<unsigned> w = __builtin_bit_cast(vec2<unsigned>, b);
+    const vec2<float> a0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[0], false), a1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[0], true);
+    const vec2<float> a2 = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[1], false), a3 = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[1], true);
+    lo = f32x4{a0[0], a0[1], a1[0], a1[1]};
+    hi = f32x4{a2[0], a2[1], a3[0], a3[1]};
+}
+struct FaFp8Scales { float k, v; };
+__device__ __forceinline__ FaFp8Scales fa_fp8_scales(const FlashAttentionParams& p, const FaBlock& blk) {
+    const int kvh = blk.h0 / blk.G;                        // workgroup-uniform
+    return FaFp8Scales{p.k_scale ? p.k_scale[kvh] : 1.f, p.v_scale ? p.v_scale[kvh] : 1.f};
+}
 
 // ---- fp32: v_mfma_f32_16x16x4_f32, an exact fmaf chain per score and per output ----
 // LDS: Ks, Vs [64][D + 4] floats (D 128: 66 KB).  Staging item = (key, 4-wide d chunk), D / 16 items of K and of V per thread.
@@ -433,8 +464,9 @@ __device__ __forceinline__ float fa_widen(KV e) {
 // the float pool widened on the host would have put there.  A thread's items are whole keys: one table entry per item, as for KV = float.
 template <int D, bool BIAS, FaForm FORM, typename KV = float>
 __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const FlashAttentionParams pa) {
-    constexpr bool KV16 = !std::is_same<KV, float>::value;
-    static_assert(!KV16 || (FORM == FA_PAGED && !BIAS), "16-bit K / V storage exists for the paged form alone");
+    constexpr bool KV16 = !std::is_same<KV, float>::value;             // a narrow pool: 16-bit elements, or (KV8) e4m3 bytes on the same map
+    constexpr bool KV8 = std::is_same<KV, fa_e4m3>::value;
+    static_assert(!KV16 || (FORM == FA_PAGED && !BIAS), "16-bit and fp8 K / V storage exist for the paged form alone");
     constexpr int LD = D + 4, NI = D / 16, ND = D / 16, NC = D / 32;
     constexpr int NI16 = D / 32;                           // KV16: items per thread
     __shared__ __attribute__((aligned(16))) float Ks[FA_T * LD];
@@ -445,13 +477,15 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
     const FlashAttentionParams p = fa_params<FORM>(pa, rec);
     const FaBlock blk = fa_block_of<BIAS, FORM>(p, rec);
     const FaLane ln = fa_lane<FORM>(p, blk, wave, li);
+    FaFp8Scales fs{1.f, 1.f};
+    if constexpr (KV8) fs = fa_fp8_scales(p, blk);
     if constexpr (fa_splits(FORM)) {
         // nothing to walk (workgroup-uniform, before the first barrier): the empty markers of the real rows
         if (blk.kt0 >= blk.nkt) {
             f32x4 z[D / 16];
 #pragma unroll
             for (int dt = 0; dt < D / 16; ++dt) z[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-            fa_finish_split<D>(p, blk, ln, g, z, 0.f, ATT_NEG);
+            fa_finish_split<D, KV8>(p, blk, ln, g, z, 0.f, ATT_NEG, fs.v);
             return;
         }
     }
@@ -518,7 +552,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
 #pragma unroll
     for (int dt = 0; dt < ND; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
     float m = ATT_NEG, l = 0.f;
-    const float sc2 = p.scale * ATT_LOG2E;
+    const float sc2 = (KV8 ? p.scale * fs.k : p.scale) * ATT_LOG2E;
 
     const int kt_first = (FORM == FA_VARLEN || fa_splits(FORM)) ? blk.kt0 : 0;
     if constexpr (FORM == FA_PAGED) { pgs = fa_pages_of(p); fetch_pages(kt_first * FA_T); use_pages(); }
@@ -533,8 +567,15 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
 #pragma unroll
                 for (int hh = 0; hh < 2; ++hh) {
                     f32x4 kw, vw;
+                    if constexpr (KV8) {
+                        f32x4 k2[2], v2[2];
+                        fa_fp8_widen8(kr16[i], k2[0], k2[1]);
+                        fa_fp8_widen8(vr16[i], v2[0], v2[1]);
+                        kw = k2[hh]; vw = v2[hh];
+                    } else {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) { kw[e] = fa_widen<KV>(kr16[i][hh * 4 + e]); vw[e] = fa_widen<KV>(vr16[i][hh * 4 + e]); }
+                        for (int e = 0; e < 4; ++e) { kw[e] = fa_widen<KV>(kr16[i][hh * 4 + e]); vw[e] = fa_widen<KV>(vr16[i][hh * 4 + e]); }
+                    }
                     *reinterpret_cast<f32x4*>(Ks + t * LD + c8 + hh * 4) = kw;
                     *reinterpret_cast<f32x4*>(Vs + t * LD + c8 + hh * 4) = vw;
                 }
@@ -583,7 +624,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
             }
         }
     }
-    if constexpr (fa_splits(FORM)) fa_finish_split<D>(p, blk, ln, g, o, l, m);
+    if constexpr (fa_splits(FORM)) fa_finish_split<D, KV8>(p, blk, ln, g, o, l, m, fs.v);
     else fa_finish<ND, BIAS>(fa_lane_y<FORM>(p, blk, ln), g, o, l, m);
 }
 
@@ -601,8 +642,9 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
 template <typename E, int D, bool BIAS, FaForm FORM, typename KV = float>
 __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const FlashAttentionParams pa) {
     constexpr bool F16 = std::is_same<E, _Float16>::value;
-    constexpr bool KV16 = !std::is_same<KV, float>::value;
-    static_assert(!KV16 || (FORM == FA_PAGED && !BIAS && std::is_same<KV, E>::value), "16-bit K / V storage: the paged form, in the kernel's own type");
+    constexpr bool KV16 = !std::is_same<KV, float>::value;             // a narrow pool: elements of E, or (KV8) e4m3 bytes on the same map
+    constexpr bool KV8 = std::is_same<KV, fa_e4m3>::value;
+    static_assert(!KV16 || (FORM == FA_PAGED && !BIAS && (KV8 || std::is_same<KV, E>::value)), "narrow K / V storage: the paged form, in the kernel's own type or e4m3");
     constexpr int NP16 = D == 128 ? 2 : 1;        // KV16: staging passes
     constexpr int NP = D / 32, ND = D / 16;       // staging passes = MFMA k steps of a score tile; d tiles of O^T
     typedef vec8<E> ex8;
@@ -615,13 +657,15 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
     const FlashAttentionParams p = fa_params<FORM>(pa, rec);
     const FaBlock blk = fa_block_of<BIAS, FORM>(p, rec);
     const FaLane ln = fa_lane<FORM>(p, blk, wave, li);
+    FaFp8Scales fs{1.f, 1.f};
+    if constexpr (KV8) fs = fa_fp8_scales(p, blk);
     if constexpr (fa_splits(FORM)) {
         // nothing to walk (workgroup-uniform, before the first barrier): the empty markers of the real rows
         if (blk.kt0 >= blk.nkt) {
             f32x4 z[D / 16];
 #pragma unroll
             for (int dt = 0; dt < D / 16; ++dt) z[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-            fa_finish_split<D>(p, blk, ln, g, z, 0.f, ATT_NEG);
+            fa_finish_split<D, KV8>(p, blk, ln, g, z, 0.f, ATT_NEG, fs.v);
             return;
         }
     }
@@ -635,7 +679,8 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
     // staging: keys (2 tp, 2 tp + 1) of the tile, d = c4 .. c4 + 3 with c4 = 16 (hi + 2 pass) + 4 lo
     const int s_lo = tid & 3, s_tp = (tid >> 2) & 31, s_hi = tid >> 7;
     f32x4 kr[NP][2], vr[NP][2];
-    ex8 kr16[NP16][2], vr16[NP16][2];                      // KV16: the tile in flight, as stored
+    typedef vec8<typename std::conditional<KV8, fa_e4m3, E>::type> kv8_t;
+    kv8_t kr16[NP16][2], vr16[NP16][2];                    // KV16: the tile in flight, as stored
     const bool stages = D >= 64 || s_hi == 0;              // KV16, D = 32: the waves that hold items (wave-uniform)
     f32x4 bn[FA_T / 16];                                   // BIAS: the bias of the tile in kr / vr, loaded with it
     // FA_PAGED: the table entry of the thread's key pair of a tile: pn as fetch_pages loads it, a tile ahead; pe the one load_tile uses.
@@ -659,11 +704,11 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
                     for (int u = 0; u < 2; ++u) {
                         const int t = key0 + s_tp * 2 + u;
                         const long src = fa_page_row(pgs, pe, min(t, p.seq_kv - 1), p.kv_ss) + c8;
-                        kr16[ps][u] = *reinterpret_cast<const ex8*>(kb + src);
-                        vr16[ps][u] = *reinterpret_cast<const ex8*>(vb + src);
+                        kr16[ps][u] = *reinterpret_cast<const kv8_t*>(kb + src);
+                        vr16[ps][u] = *reinterpret_cast<const kv8_t*>(vb + src);
                         if (t >= p.seq_kv) {
 #pragma unroll
-                            for (int e = 0; e < 8; ++e) { kr16[ps][u][e] = (E)0.f; vr16[ps][u][e] = (E)0.f; }
+                            for (int e = 0; e < 8; ++e) { kr16[ps][u][e] = (KV)0.f; vr16[ps][u][e] = (KV)0.f; }
                         }
                     }
                 }
@@ -690,7 +735,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
 #pragma unroll
     for (int dt = 0; dt < ND; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
     float m = ATT_NEG, l = 0.f;
-    const float sc2 = p.scale * ATT_LOG2E;
+    const float sc2 = (KV8 ? p.scale * fs.k : p.scale) * ATT_LOG2E;
 
     const int kt_first = (FORM == FA_VARLEN || fa_splits(FORM)) ? blk.kt0 : 0;
     if constexpr (FORM == FA_PAGED) { pgs = fa_pages_of(p); fetch_pages(kt_first * FA_T); use_pages(); }
@@ -703,13 +748,30 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
 #pragma unroll
                 for (int ps = 0; ps < NP16; ++ps) {
                     const int c8 = (s_hi + 2 * ps) * 32 + s_lo * 8;
+                    if constexpr (KV8) {
+                        ex8 ke[2], ve[2];                      // the key pair's bytes widened exactly to E
 #pragma unroll
-                    for (int u = 0; u < 2; ++u) {
-                        const int t = s_tp * 2 + u;
-                        *reinterpret_cast<ex8*>(att_k_chunk<D>(Kp + t * D, t, c8 >> 3)) = kr16[ps][u];
+                        for (int u = 0; u < 2; ++u) {
+                            f32x4 a, b;
+                            fa_fp8_widen8(kr16[ps][u], a, b); ke[u] = att_round8<E>(a, b);
+                            fa_fp8_widen8(vr16[ps][u], a, b); ve[u] = att_round8<E>(a, b);
+                        }
+#pragma unroll
+                        for (int u = 0; u < 2; ++u) {
+                            const int t = s_tp * 2 + u;
+                            *reinterpret_cast<ex8*>(att_k_chunk<D>(Kp + t * D, t, c8 >> 3)) = ke[u];
+                        }
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) att_vt_store(Vt + (c8 + e) * FA_VT_LD, s_tp, ve[0][e], ve[1][e]);
+                    } else {
+#pragma unroll
+                        for (int u = 0; u < 2; ++u) {
+                            const int t = s_tp * 2 + u;
+                            *reinterpret_cast<ex8*>(att_k_chunk<D>(Kp + t * D, t, c8 >> 3)) = kr16[ps][u];
+                        }
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) att_vt_store(Vt + (c8 + e) * FA_VT_LD, s_tp, vr16[ps][0][e], vr16[ps][1][e]);
                     }
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) att_vt_store(Vt + (c8 + e) * FA_VT_LD, s_tp, vr16[ps][0][e], vr16[ps][1][e]);
                 }
             }
         } else {
@@ -762,7 +824,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
             for (int dt = 0; dt < ND; ++dt) o[dt] = att_mfma<F16>(att_vt_frag(Vt + (dt * 16 + li) * FA_VT_LD + g * 4, t), pf, o[dt]);
         }
     }
-    if constexpr (fa_splits(FORM)) fa_finish_split<D>(p, blk, ln, g, o, l, m);
+    if constexpr (fa_splits(FORM)) fa_finish_split<D, KV8>(p, blk, ln, g, o, l, m, fs.v);
     else fa_finish<ND, BIAS>(fa_lane_y<FORM>(p, blk, ln), g, o, l, m);
 }
 
@@ -779,7 +841,8 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
 // PAGED = false, which is the kernel of the split entry as it was. ----
 constexpr int FA_COMBINE_THREADS = 256;
 constexpr int FA_COMBINE_CHUNK = 8;
-template <bool PAGED>
+// VS (with PAGED; the fp8 pool): the row of y, after the select, is multiplied by v_scale of the row's K / V head; lse is not.
+template <bool PAGED, bool VS = false>
 __global__ void __launch_bounds__(FA_COMBINE_THREADS) flash_split_combine_kernel(const FlashAttentionParams p) {
     const int D4 = p.head_dim / 4;
     const long R = (long)p.batch * p.heads * p.seq_q;
@@ -825,6 +888,7 @@ __global__ void __launch_bounds__(FA_COMBINE_THREADS) flash_split_combine_kernel
     if constexpr (PAGED) {
         if (none) { yv = f32x4{0.f, 0.f, 0.f, 0.f}; lv = -__builtin_inff(); }
     }
+    if constexpr (VS) yv = yv * (p.v_scale ? p.v_scale[head / (p.heads / p.kv_heads)] : 1.f);
     *reinterpret_cast<f32x4*>(p.y + (b * p.q_sb + head * p.q_sh + query * p.q_ss + d)) = yv;
     if (d == 0 && p.lse) p.lse[r] = lv;
 }
@@ -846,9 +910,18 @@ void fa_launch_kv16(const FlashAttentionParams& p, dim3 grid, hipStream_t s) {
     else if (p.s16 == 1) hipLaunchKernelGGL((flash_attention_s16_kernel<__bf16, D, false, FA_PAGED, __bf16>), grid, block, 0, s, p);
     else hipLaunchKernelGGL((flash_attention_s16_kernel<_Float16, D, false, FA_PAGED, _Float16>), grid, block, 0, s, p);
 }
+// FA_PAGED over an e4m3 pool (p.kv_type FA_KV_FP8): any compute mode reads it
+template <int D>
+void fa_launch_kv8(const FlashAttentionParams& p, dim3 grid, hipStream_t s) {
+    const dim3 block(FA_THREADS);
+    if (p.s16 == 0) hipLaunchKernelGGL((flash_attention_f32_kernel<D, false, FA_PAGED, fa_e4m3>), grid, block, 0, s, p);
+    else if (p.s16 == 1) hipLaunchKernelGGL((flash_attention_s16_kernel<__bf16, D, false, FA_PAGED, fa_e4m3>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((flash_attention_s16_kernel<_Float16, D, false, FA_PAGED, fa_e4m3>), grid, block, 0, s, p);
+}
 template <int D>
 void fa_launch(const FlashAttentionParams& p, FaForm form, dim3 grid, hipStream_t s) {
     if (form == FA_VARLEN) fa_launch<D, false, FA_VARLEN>(p, grid, s);
+    else if (form == FA_PAGED && p.kv_type == FA_KV_FP8) fa_launch_kv8<D>(p, grid, s);
     else if (form == FA_PAGED && p.kv_type) fa_launch_kv16<D>(p, grid, s);
     else if (form == FA_PAGED) fa_launch<D, false, FA_PAGED>(p, grid, s);
     else if (form == FA_SPLIT) fa_launch<D, false, FA_SPLIT>(p, grid, s);
@@ -865,7 +938,9 @@ void fa_launch(const FlashAttentionParams& p, FaForm form, dim3 grid, hipStream_
 
 hipError_t launch_flash_attention(const FlashAttentionParams& p, hipStream_t s) {
     // a 16-bit pool exists for the paged form alone, and a 16-bit kernel reads only a pool of its own type
-    if (p.kv_type && (p.kv_type < 0 || p.kv_type > 2 || !p.block_table || p.plan || (p.s16 && p.s16 != p.kv_type))) return hipErrorInvalidValue;
+    // (an e4m3 pool, FA_KV_FP8, is read by every kernel; the scale arrays exist with it alone)
+    if (p.kv_type && (p.kv_type < 0 || p.kv_type > FA_KV_FP8 || !p.block_table || p.plan || (p.kv_type != FA_KV_FP8 && p.s16 && p.s16 != p.kv_type))) return hipErrorInvalidValue;
+    if (p.kv_type != FA_KV_FP8 && (p.k_scale || p.v_scale)) return hipErrorInvalidValue;
     if (p.plan) {
         // the packed batch: the record table was built and every value in it checked by the entry (brn_flash_varlen_plan.h); what is
         // checked here is what the kernels assume of the other arguments
@@ -907,7 +982,8 @@ hipError_t launch_flash_attention(const FlashAttentionParams& p, hipStream_t s) 
         else if (p.head_dim == 64) fa_launch<64>(p, form, grid, s);
         else fa_launch<128>(p, form, grid, s);
         const dim3 cgrid((unsigned)((quads + FA_COMBINE_THREADS - 1) / FA_COMBINE_THREADS));
-        if (S > 1 && paged) hipLaunchKernelGGL(flash_split_combine_kernel<true>, cgrid, dim3(FA_COMBINE_THREADS), 0, s, p);
+        if (S > 1 && p.kv_type == FA_KV_FP8) hipLaunchKernelGGL((flash_split_combine_kernel<true, true>), cgrid, dim3(FA_COMBINE_THREADS), 0, s, p);
+        else if (S > 1 && paged) hipLaunchKernelGGL(flash_split_combine_kernel<true>, cgrid, dim3(FA_COMBINE_THREADS), 0, s, p);
         else if (S > 1) hipLaunchKernelGGL(flash_split_combine_kernel<false>, cgrid, dim3(FA_COMBINE_THREADS), 0, s, p);
         return hipGetLastError();
     }

@@ -295,20 +295,21 @@ _KV_TYPE = {None: _ffi.BRN_KV_F32, "f32": _ffi.BRN_KV_F32, "bf16": _ffi.BRN_KV_B
 def _pool_arg(a, shape, kv_dtype, what):
     """a K / V pool of `kv_dtype` ("f32", "bf16", "f16") AS IT IS, never converted or copied (the append writes it in place) ->
     (pointer, loc, keepalive).  f32: float32 tensors / arrays.  bf16 / f16: torch.bfloat16 / torch.float16 tensors (host or device),
-    np.float16 arrays for f16, np.uint16 arrays of bit patterns for either (numpy has no bf16).  Anything else raises."""
+    np.float16 arrays for f16, np.uint16 arrays of bit patterns for either (numpy has no bf16).  "fp8" (the e4m3fn pool of the fp8
+    entries): torch.uint8 or torch.float8_e4m3fn tensors, np.uint8 arrays of the bytes.  Anything else raises."""
     if tuple(int(s) for s in a.shape) != tuple(shape):
         raise ValueError(f"{what}: expected shape {tuple(shape)}, got {tuple(a.shape)}")
     if T._is_torch(a):
         import torch
-        want = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}[kv_dtype]
-        if a.dtype != want:
-            raise TypeError(f"{what}: kv_dtype {kv_dtype!r} needs a {want} tensor, got {a.dtype}")
+        want = {"f32": (torch.float32,), "bf16": (torch.bfloat16,), "f16": (torch.float16,), "fp8": (torch.uint8, torch.float8_e4m3fn)}[kv_dtype]
+        if a.dtype not in want:
+            raise TypeError(f"{what}: kv_dtype {kv_dtype!r} needs a {' or '.join(str(w) for w in want)} tensor, got {a.dtype}")
         if not a.is_contiguous():
             raise ValueError(f"{what} must be contiguous")
         return a.data_ptr(), (_ffi.BRN_MEM_DEVICE if a.is_cuda else _ffi.BRN_MEM_HOST), a
     if not isinstance(a, np.ndarray):
         raise TypeError(f"{what} must be a torch tensor or a numpy array")
-    ok = {"f32": (np.float32,), "bf16": (np.uint16,), "f16": (np.float16, np.uint16)}[kv_dtype]
+    ok = {"f32": (np.float32,), "bf16": (np.uint16,), "f16": (np.float16, np.uint16), "fp8": (np.uint8,)}[kv_dtype]
     if a.dtype not in [np.dtype(t) for t in ok]:
         raise TypeError(f"{what}: kv_dtype {kv_dtype!r} needs a numpy array of {' or '.join(np.dtype(t).name for t in ok)}, got {a.dtype}")
     if not a.flags.c_contiguous:
@@ -333,6 +334,31 @@ def flash_attention_paged(q, k_pages, v_pages, block_table, kv_lens, max_kv_len=
     of bit patterns for either; a pool of another dtype raises.  ("f32" is the new entry on an fp32 pool: the bits of None.)"""
     if kv_dtype not in _KV_TYPE:
         raise ValueError(f"kv_dtype {kv_dtype!r} unknown (None, 'f32', 'bf16' or 'f16')")
+    return _flash_attention_paged(q, k_pages, v_pages, block_table, kv_lens, max_kv_len, causal, scale, layout, kv_splits, return_lse, return_partials, device, kv_dtype, None)
+
+
+def flash_attention_paged_fp8(q, k_pages, v_pages, k_scale, v_scale, block_table, kv_lens, max_kv_len=None, causal=False, scale=None, layout="bshd", kv_splits=0,
+                              return_lse=False, return_partials=False, device=0):
+    """brn_flash_attention_paged_fp8_forward: flash_attention_paged over a pool STORED in fp8.  k_pages, v_pages
+    [n_pages, page_size, kv_heads, head_dim] of OCP e4m3fn bytes, taken as they are: torch.uint8 or torch.float8_e4m3fn tensors (host or
+    device), np.uint8 arrays on the host.  k_scale, v_scale: [kv_heads] fp32 on q's side, or None = all ones; byte e of K head h stands
+    for k_scale[h] * e4m3(e), the same for V.  Everything else, the host-side checks included, is flash_attention_paged's.  One pool is
+    read by every compute mode; lse and the partials carry the bits of flash_attention_paged on the widened bytes at
+    scale * k_scale[h / G], y those bits times v_scale[h / G] (include/birefnet_hip.h)."""
+    return _flash_attention_paged(q, k_pages, v_pages, block_table, kv_lens, max_kv_len, causal, scale, layout, kv_splits, return_lse, return_partials, device, "fp8",
+                                  (k_scale, v_scale))
+
+
+def _scale_arg(a, kv_heads, what):
+    """a [kv_heads] fp32 scale array or None -> (pointer or None, loc or None, keepalive)"""
+    if a is None:
+        return None, None, None
+    p, loc, keep, _ = T.as_arg(a, (kv_heads,))
+    return p, loc, keep
+
+
+def _flash_attention_paged(q, k_pages, v_pages, block_table, kv_lens, max_kv_len, causal, scale, layout, kv_splits, return_lse, return_partials, device, kv_dtype, scales):
+    """the body of flash_attention_paged (scales None) and flash_attention_paged_fp8 (kv_dtype "fp8", scales = (k_scale, v_scale))"""
     lay = _ATTN_LAYOUT[layout]
     seq_axis, head_axis = (1, 2) if lay == _ffi.BRN_ATTN_BSHD else (2, 1)
     batch, hd = int(q.shape[0]), int(q.shape[3])
@@ -356,6 +382,10 @@ def flash_attention_paged(q, k_pages, v_pages, block_table, kv_lens, max_kv_len=
     pl, lloc, lkeep, lh = _int32_arg(kv_lens, (batch,), "kv_lens")
     if not (kloc == vloc == tloc == lloc == loc):
         raise ValueError("q, k_pages, v_pages, block_table and kv_lens must live on the same side")
+    if scales is not None:
+        (pks, ksloc, kskeep), (pvs, vsloc, vskeep) = (_scale_arg(a, kv_heads, n) for a, n in zip(scales, ("k_scale", "v_scale")))
+        if any(sl is not None and sl != loc for sl in (ksloc, vsloc)):
+            raise ValueError("k_scale and v_scale must live on q's side")
     if lh is not None and th is not None:
         if lh.size and (int(lh.min()) < 0 or int(lh.max()) > max_kv_len):
             raise ValueError(f"kv_lens must lie in 0 .. max_kv_len = {max_kv_len}")
@@ -372,6 +402,8 @@ def flash_attention_paged(q, k_pages, v_pages, block_table, kv_lens, max_kv_len=
             nws if ws is not None else 0, loc, T.device_of(keep, device), T.stream_of(keep))
     if kv_dtype is None:
         _ffi.check(_ffi.lib.brn_flash_attention_paged_forward(pq, pk, pv, pt, pl, *tail))
+    elif scales is not None:
+        _ffi.check(_ffi.lib.brn_flash_attention_paged_fp8_forward(pq, pk, pv, pks, pvs, pt, pl, *tail))
     else:
         _ffi.check(_ffi.lib.brn_flash_attention_paged_kv_forward(pq, pk, pv, _KV_TYPE[kv_dtype], pt, pl, *tail))
     out = (y,) + ((lse,) if return_lse else ())
@@ -393,6 +425,19 @@ def kv_cache_append(k_new, v_new, k_pages, v_pages, block_table, kv_lens, kv_dty
     table entry at a written position outside 0 .. n_pages - 1.  Device tensors are not read back: the library clamps their values."""
     if kv_dtype not in _KV_TYPE:
         raise ValueError(f"kv_dtype {kv_dtype!r} unknown (None, 'f32', 'bf16' or 'f16')")
+    return _kv_cache_append(k_new, v_new, k_pages, v_pages, block_table, kv_lens, kv_dtype or "f32", layout, update_lens, device, None)
+
+
+def kv_cache_append_fp8(k_new, v_new, k_pages, v_pages, k_scale, v_scale, block_table, kv_lens, layout="bshd", update_lens=True, device=0):
+    """brn_kv_cache_append_fp8: kv_cache_append into the fp8 pool of flash_attention_paged_fp8 (torch.uint8 / torch.float8_e4m3fn
+    tensors, np.uint8 arrays on the host; written in place).  k_scale, v_scale: [kv_heads] fp32 on k_new's side, or None = all ones.
+    An element x of head h is stored as the e4m3fn byte of clamp(x / scale[h], -448, 448), rounded to nearest even; a NaN becomes a NaN
+    byte.  The position rule, update_lens and the host-side checks are kv_cache_append's."""
+    return _kv_cache_append(k_new, v_new, k_pages, v_pages, block_table, kv_lens, "fp8", layout, update_lens, device, (k_scale, v_scale))
+
+
+def _kv_cache_append(k_new, v_new, k_pages, v_pages, block_table, kv_lens, kv_dtype, layout, update_lens, device, scales):
+    """the body of kv_cache_append (scales None) and kv_cache_append_fp8 (kv_dtype "fp8", scales = (k_scale, v_scale))"""
     lay = _ATTN_LAYOUT[layout]
     seq_axis, head_axis = (1, 2) if lay == _ffi.BRN_ATTN_BSHD else (2, 1)
     batch, hd = int(k_new.shape[0]), int(k_new.shape[3])
@@ -404,12 +449,16 @@ def kv_cache_append(k_new, v_new, k_pages, v_pages, block_table, kv_lens, kv_dty
     pool_shape = (n_pages, page_size, kv_heads, hd)
     pk, loc, keep, _ = T.as_arg(k_new)
     pv, vloc, vkeep, _ = T.as_arg(v_new, tuple(int(s) for s in k_new.shape))
-    ppk, kloc, kkeep = _pool_arg(k_pages, pool_shape, kv_dtype or "f32", "k_pages")
-    ppv, pvloc, pvkeep = _pool_arg(v_pages, pool_shape, kv_dtype or "f32", "v_pages")
+    ppk, kloc, kkeep = _pool_arg(k_pages, pool_shape, kv_dtype, "k_pages")
+    ppv, pvloc, pvkeep = _pool_arg(v_pages, pool_shape, kv_dtype, "v_pages")
     pt, tloc, tkeep, th = _int32_arg(block_table, (batch, max_pages), "block_table")
     pl, lloc, lkeep, lh = _int32_arg(kv_lens, (batch,), "kv_lens")
     if not (vloc == kloc == pvloc == tloc == lloc == loc):
         raise ValueError("k_new, v_new, k_pages, v_pages, block_table and kv_lens must live on the same side")
+    if scales is not None:
+        (pks, ksloc, kskeep), (pvs, vsloc, vskeep) = (_scale_arg(a, kv_heads, n) for a, n in zip(scales, ("k_scale", "v_scale")))
+        if any(sl is not None and sl != loc for sl in (ksloc, vsloc)):
+            raise ValueError("k_scale and v_scale must live on k_new's side")
     cap = max_pages * page_size
     if lh is not None and th is not None:
         if lh.size and (int(lh.min()) < 0 or int(lh.max()) > cap):
@@ -432,6 +481,10 @@ def kv_cache_append(k_new, v_new, k_pages, v_pages, block_table, kv_lens, kv_dty
         else:
             out = np.empty(batch, np.int32)
             po = out.ctypes.data
+    if scales is not None:
+        _ffi.check(_ffi.lib.brn_kv_cache_append_fp8(pk, pv, batch, seq_new, kv_heads, hd, lay, ppk, ppv, pks, pvs, pt, pl, po, n_pages, page_size, max_pages,
+                                                    loc, T.device_of(keep, device), T.stream_of(keep)))
+        return out
     _ffi.check(_ffi.lib.brn_kv_cache_append(pk, pv, batch, seq_new, kv_heads, hd, lay, ppk, ppv, _KV_TYPE[kv_dtype], pt, pl, po, n_pages, page_size, max_pages,
                                             loc, T.device_of(keep, device), T.stream_of(keep)))
     return out

@@ -512,8 +512,8 @@ typedef enum { BRN_KV_F32 = 0, BRN_KV_BF16 = 1, BRN_KV_F16 = 2 } brn_kv_type;
  * Limits (each violation is BRN_ERR_INVALID_ARG with the prefix "flash attention paged kv:" and a message naming the limit, checked
  * before the device): every limit of brn_flash_attention_paged_forward; kv_type one of the three; the pairing of pool and compute mode
  * above; BRN_MEM_DEVICE k_pages / v_pages 16-byte aligned whatever the type; the overlap rules count bytes.
- * Not provided: fp8 / int8 or otherwise scaled pages; a K-transposed page layout; 16-bit q / y; 16-bit tensors for the dense, split and
- * varlen entries; a window or a bias. */
+ * Not provided: fp8 / int8 or otherwise scaled pages (e4m3 pages with one scale per K / V head are brn_flash_attention_paged_fp8_forward
+ * below; int8 nowhere); a K-transposed page layout; 16-bit q / y; 16-bit tensors for the dense, split and varlen entries; a window or a bias. */
 brn_status brn_flash_attention_paged_kv_forward(const float* q, const void* k_pages, const void* v_pages, int kv_type,
                                                 const int* block_table, const int* kv_lens,
                                                 int batch, int seq_q, int max_kv_len, int heads, int kv_heads, int head_dim,
@@ -546,12 +546,54 @@ brn_status brn_flash_attention_paged_kv_forward(const float* q, const void* k_pa
  * block_table and kv_lens do not overlap the pool, k_pages and v_pages not each other, kv_lens_out nothing but (wholly) kv_lens, sizes in
  * bytes; BRN_MEM_DEVICE k_new, v_new, k_pages, v_pages 16-byte aligned, the int arrays 4-byte aligned.
  * Not provided: a per-sequence number of new tokens (seq_new is one integer); copy-on-write or reference counting of shared pages;
- * scaled (fp8 / int8) pages. */
+ * scaled (fp8 / int8) pages (an e4m3 pool with per-head scales is written by brn_kv_cache_append_fp8 below). */
 brn_status brn_kv_cache_append(const float* k_new, const float* v_new, int batch, int seq_new, int kv_heads, int head_dim, int layout,
                                void* k_pages, void* v_pages, int kv_type,
                                const int* block_table, const int* kv_lens, int* kv_lens_out,
                                int n_pages, int page_size, int max_pages,
                                brn_mem loc, int device_ordinal, void* stream);
+/* brn_flash_attention_paged_forward over a pool stored in fp8 with one fp32 scale per K / V head: twice the tokens of a 16-bit pool in
+ * the same memory and half its bytes on the rows that are bound by bytes.  Semantics, mask, clamps, plan, workspace layout, the defined
+ * empty row (y = 0, lse = -inf), the promise (allocates nothing, does not synchronise, may be captured) and every limit are those of
+ * brn_flash_attention_paged_forward; the arguments after kv_lens are its arguments after kv_lens, in its order.  What differs:
+ * k_pages, v_pages: [n_pages, page_size, kv_heads, head_dim], one byte per element, OCP e4m3fn (the gfx950 format, not MI300's fnuz:
+ * bias 7, largest value 448, no infinities, NaN = 0x7F / 0xFF), where `loc` says.  q, y, lse and the workspace stay fp32.
+ * k_scale, v_scale: [kv_heads] fp32, where `loc` says; NULL means all ones.  Byte e of K head h stands for k_scale[h] * e4m3(e), byte e
+ * of V head h for v_scale[h] * e4m3(e).  They are device data like the table and the lengths: the kernels read them, the host never does
+ * for BRN_MEM_DEVICE, they may change between graph replays, and no address depends on them.  A scale that is not finite and positive
+ * makes that head's results unspecified; it never causes an access outside the pool.
+ * Every e4m3 value is a bf16, an fp16 and an fp32 value, so ONE fp8 pool is read by every compute mode (brn_set_op_compute): each byte is
+ * widened exactly to the type the mode computes in, fp32 in the fp32-class modes, bf16 in BRN_BF16, fp16 in BRN_F16.
+ * The promise added, for any finite positive scales, with s the call's resolved scale and g = h / G the K / V head of query head h: lse
+ * and the partials in the workspace carry the bits of brn_flash_attention_paged_forward, in the same compute mode, on the fp32 pool that
+ * holds the widened bytes, called with scale = fl32(s * k_scale[g]); y carries fl32(v_scale[g] * y of that call).  v_scale multiplies a
+ * row's final y once, after normalisation; O_part / lse2_part are not scaled by it, and lse is the natural-log sum over the scaled scores.
+ * Limits (each violation is BRN_ERR_INVALID_ARG with the prefix "flash attention paged fp8:" and a message naming the limit, checked
+ * before the device): every limit of brn_flash_attention_paged_forward; BRN_MEM_DEVICE k_pages / v_pages 16-byte aligned, the two scale
+ * arrays 4-byte aligned; the overlap rules count bytes and include the two scale arrays.
+ * Not provided: computing scales (amax); per-page or per-token scales; e5m2; int8; fp8 q / y; the fp8 MFMA on the scores. */
+brn_status brn_flash_attention_paged_fp8_forward(const float* q, const void* k_pages, const void* v_pages,
+                                                 const float* k_scale, const float* v_scale,
+                                                 const int* block_table, const int* kv_lens,
+                                                 int batch, int seq_q, int max_kv_len, int heads, int kv_heads, int head_dim,
+                                                 int n_pages, int page_size, int max_pages,
+                                                 int layout, int causal, float scale, int kv_splits,
+                                                 float* y, float* lse, float* workspace, size_t workspace_floats,
+                                                 brn_mem loc, int device_ordinal, void* stream);
+/* brn_kv_cache_append into the fp8 pool of brn_flash_attention_paged_fp8_forward.  The rule is brn_kv_cache_append's, unchanged: the
+ * position rule, dropped positions, clamps, lengths written by a second launch, kv_lens_out in place; BRN_MEM_HOST stages the whole pool.
+ * k_pages, v_pages: bytes of OCP e4m3fn; k_scale, v_scale: [kv_heads] fp32 where `loc` says, NULL = all ones, device data as above.
+ * An element x of K head h is stored by three steps (V alike, with v_scale): t = x / k_scale[h], the correctly rounded fp32 division;
+ * t clamped to +-448, a NaN kept; t rounded to nearest even into e4m3fn.  So a value beyond the range saturates to +-448 whatever the
+ * conversion instruction does on overflow, +-0 and underflow keep their sign, and a NaN becomes a NaN byte (0x7F or 0xFF).
+ * Limits (BRN_ERR_INVALID_ARG, prefix "kv cache append fp8:", checked before the device): every limit of brn_kv_cache_append but kv_type;
+ * the scale arrays overlap neither the pool nor kv_lens_out, sizes in bytes; BRN_MEM_DEVICE scale arrays 4-byte aligned.
+ * Not provided: computing scales (amax); per-page or per-token scales; e5m2; int8; a per-sequence number of new tokens. */
+brn_status brn_kv_cache_append_fp8(const float* k_new, const float* v_new, int batch, int seq_new, int kv_heads, int head_dim, int layout,
+                                   void* k_pages, void* v_pages, const float* k_scale, const float* v_scale,
+                                   const int* block_table, const int* kv_lens, int* kv_lens_out,
+                                   int n_pages, int page_size, int max_pages,
+                                   brn_mem loc, int device_ordinal, void* stream);
 /* PatchMerging::forward (swin.rs:491-527): x [B,H*W,C] -> [B, ceil(H/2)*ceil(W/2), 2C]. */
 brn_status brn_patch_merging_forward(const float* x, int B, int H, int W, int C, const float* norm_g,
                                      const float* norm_b, const float* reduction_w, float* y, brn_mem loc,

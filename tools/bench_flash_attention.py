@@ -55,8 +55,13 @@ the same values (the yardstick: the older entry's kernels, never the code under 
 page 64 with a shuffled table, for the pairs bf16 on bf16, f16 on f16 and f32 on bf16; then brn_kv_cache_append (64 x 1 and 16 x 512 new
 tokens, lengths in place) beside a device-to-device copy of the bytes it writes.  Same protocol; --row picks an attention row, --mode a
 pair by its compute mode.  Written to profiles/flash_attention_paged_kv16_bench.json.
+--paged-fp8 times brn_flash_attention_paged_fp8_forward on an e4m3 pool (per-head scales on the device) beside
+brn_flash_attention_paged_kv_forward on the bf16 / fp16 pool holding the widened bytes (the yardstick: the parent's kernels; bf16 in modes
+bf16 and f32, f16 in mode f16), with brn_flash_attention_paged_forward on the fp32 pool for context, on the same rows, page 64, shuffled
+table, modes bf16, f16 and f32; then brn_kv_cache_append_fp8 beside a device-to-device copy of the bytes it writes.  Same protocol.
+Written to profiles/flash_attention_paged_fp8_bench.json.
 
-  python tools/bench_flash_attention.py [--bias | --gqa | --varlen | --splitkv | --paged | --paged-kv16] [--row N] [--mode f32|bf16|f16] [--json PATH]"""
+  python tools/bench_flash_attention.py [--bias | --gqa | --varlen | --splitkv | --paged | --paged-kv16 | --paged-fp8] [--row N] [--mode f32|bf16|f16] [--json PATH]"""
 import argparse
 import json
 import os
@@ -91,6 +96,7 @@ PAGED_KV16_PAIRS = [("bf16", "bf16"), ("f16", "f16"), ("f32", "bf16")]
 KV_APPEND_ROWS = [(64, 1, 8, 128, 64, 64), (16, 512, 8, 128, 64, 64)]
 KV_APPEND_TYPES = ["bf16", "f16", "f32"]
 PAGED_KV16_JSON = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "flash_attention_paged_kv16_bench.json")
+PAGED_FP8_JSON = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "flash_attention_paged_fp8_bench.json")
 PAGED_JSON = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "flash_attention_paged_bench.json")
 HBM_BYTES_PER_S = 8.0e12
 MODES = ["f32", "bf16", "f16"]
@@ -556,13 +562,90 @@ def bench_paged_kv16(row, pair):
     return [rec]
 
 
+def bench_paged_fp8(row, mode):
+    """brn_flash_attention_paged_fp8_forward on an e4m3 pool beside brn_flash_attention_paged_kv_forward on the 16-bit pool of the widened
+    bytes (the yardstick, the parent's kernels) and brn_flash_attention_paged_forward on the fp32 pool, in one compute mode; page 64,
+    shuffled table"""
+    import torch
+    import candle_birefnet_amd as cb
+    from candle_birefnet_amd import ops
+    lib = cb._ffi.lib
+    batch, seq_q, seq_kv, heads, kv_heads, hd, causal, ragged = row
+    page = PAGED_KV16_PAGE
+    kv = "f16" if mode == "f16" else "bf16"
+    tdt = torch.float16 if kv == "f16" else torch.bfloat16
+    g = torch.Generator(device="cuda").manual_seed(1)
+    q = torch.randn(batch, seq_q, heads, hd, device="cuda", generator=g)
+    lens_h = [512 + (seq_kv - 512) * b // (batch - 1) for b in range(batch)] if ragged else [seq_kv] * batch
+    lens = torch.tensor(lens_h, dtype=torch.int32, device="cuda")
+    n_pages, max_pages = batch * seq_kv // page, seq_kv // page
+    perm = torch.randperm(n_pages, device="cuda", generator=g)
+    table = perm.to(torch.int32).view(batch, max_pages).contiguous()
+    # one logical cache, three storage types: standard normal values / 2^-6, clamped, as e4m3 bytes; the same values in 16 bits and in fp32
+    pools8 = [(torch.randn(n_pages, page, kv_heads, hd, device="cuda", generator=g) * 64).clamp_(-448, 448).to(torch.float8_e4m3fn) for _ in range(2)]
+    pools16 = [a.to(tdt) for a in pools8]
+    pools32 = [a.float() for a in pools8]
+    k_scale, v_scale = (torch.full((kv_heads,), 2.0 ** -6, device="cuda") for _ in range(2))
+    stream = torch.cuda.current_stream().cuda_stream
+    R = batch * heads * seq_q
+    S, tps, need = ops.flash_attention_splitkv_plan(batch, seq_q, seq_kv, heads, kv_heads, hd, 0)
+    outs = [(torch.empty_like(q), torch.empty(R, device="cuda"), torch.empty(max(need, 4), device="cuda")) for _ in range(3)]
+    s = hd ** -0.5
+    ints = (batch, seq_q, seq_kv, heads, kv_heads, hd, n_pages, page, max_pages, 0, causal)
+
+    def fp8_pool():
+        y, lse, ws = outs[0]
+        cb._ffi.check(lib.brn_flash_attention_paged_fp8_forward(q.data_ptr(), pools8[0].data_ptr(), pools8[1].data_ptr(), k_scale.data_ptr(), v_scale.data_ptr(), table.data_ptr(),
+                                                                lens.data_ptr(), *ints, s, 0, y.data_ptr(), lse.data_ptr(), ws.data_ptr(), need, 1, 0, stream))
+        return y
+
+    def kv16_pool():
+        y, lse, ws = outs[1]
+        cb._ffi.check(lib.brn_flash_attention_paged_kv_forward(q.data_ptr(), pools16[0].data_ptr(), pools16[1].data_ptr(), cb._ffi.BRN_KV_BF16 if kv == "bf16" else cb._ffi.BRN_KV_F16,
+                                                               table.data_ptr(), lens.data_ptr(), *ints, s * 2.0 ** -6, 0, y.data_ptr(), lse.data_ptr(), ws.data_ptr(), need, 1, 0, stream))
+        return y
+
+    def fp32_pool():
+        y, lse, ws = outs[2]
+        cb._ffi.check(lib.brn_flash_attention_paged_forward(q.data_ptr(), pools32[0].data_ptr(), pools32[1].data_ptr(), table.data_ptr(), lens.data_ptr(), *ints, s * 2.0 ** -6, 0,
+                                                            y.data_ptr(), lse.data_ptr(), ws.data_ptr(), need, 1, 0, stream))
+        return y
+
+    ops.set_compute(mode)
+    try:
+        t8, t16, t32 = _time_alternating([fp8_pool, kv16_pool, fp32_pool])
+        assert all(bool(torch.isfinite(t[4]).all()) for t in (t8, t16, t32))
+        keys = sum(lens_h) * kv_heads * hd
+        tb = lambda nbytes, t: round(2 * nbytes * keys / (t[0] * 1e-3) / 1e12, 3)
+        rec = {"batch": batch, "seq_q": seq_q, "max_kv_len": seq_kv, "kv_lens": "all max_kv_len" if not ragged else lens_h, "heads": heads, "kv_heads": kv_heads,
+               "head_dim": hd, "mode": mode, "yardstick_kv_type": kv, "page_size": page, "table": "shuffled", "causal": causal, "S": S, "tiles_per_split": tps,
+               "fp8_pool_kv_bytes": 2 * keys, "kv16_pool_kv_bytes": 4 * keys, "fp32_pool_kv_bytes": 8 * keys,
+               "fp8_over_kv16": round(t8[0] / t16[0], 4), "fp8_over_fp32": round(t8[0] / t32[0], 4), "fp8_below_lowest_kv16_round_median": bool(t8[0] < t16[2]),
+               # y = v_scale * the yardstick's y with v_scale a power of two: the same bits scaled exactly
+               "same_bits_as_kv16_times_v_scale": bool(torch.equal(t8[4], t16[4] * 2.0 ** -6)),
+               "fp8_pool_tb_per_s": tb(1, t8), "kv16_pool_tb_per_s": tb(2, t16), "fp32_pool_tb_per_s": tb(4, t32)}
+        rec.update(_side("fp8_pool", t8))
+        rec.update(_side("kv16_pool", t16))
+        rec.update(_side("fp32_pool", t32))
+        print(f"{batch:3d} x {seq_q:2d} / {seq_kv:5d}{' ragged' if ragged else ''} x {heads} / {kv_heads} x {hd} {mode:4s} causal {causal} S {S}: "
+              f"fp8 pool {t8[0]:8.4f} ms [{t8[2]:.4f} .. {t8[3]:.4f}] {rec['fp8_pool_tb_per_s']:.2f} TB/s | {kv} pool {t16[0]:8.4f} ms [{t16[2]:.4f} .. {t16[3]:.4f}] "
+              f"{rec['kv16_pool_tb_per_s']:.2f} TB/s | fp32 pool {t32[0]:8.4f} ms {rec['fp32_pool_tb_per_s']:.2f} TB/s | x{rec['fp8_over_kv16']:.3f} of 16-bit, "
+              f"below its lowest round {rec['fp8_below_lowest_kv16_round_median']} bits {rec['same_bits_as_kv16_times_v_scale']}", flush=True)
+    finally:
+        ops.set_compute("f32")
+    del q, pools8, pools16, pools32, outs
+    torch.cuda.empty_cache()
+    return [rec]
+
+
 def bench_kv_append(row, kv):
-    """brn_kv_cache_append (rows + lengths, in place) beside a device-to-device copy of the bytes it writes, the bandwidth floor"""
+    """brn_kv_cache_append (rows + lengths, in place; kv "fp8": brn_kv_cache_append_fp8 with per-head scales) beside a device-to-device
+    copy of the bytes it writes, the bandwidth floor"""
     import torch
     import candle_birefnet_amd as cb
     lib = cb._ffi.lib
     batch, seq_new, kv_heads, hd, page, pages_per_seq = row
-    tdt = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}[kv]
+    tdt = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16, "fp8": torch.uint8}[kv]
     g = torch.Generator(device="cuda").manual_seed(2)
     k_new, v_new = (torch.randn(batch, seq_new, kv_heads, hd, device="cuda", generator=g) for _ in range(2))
     n_pages = batch * pages_per_seq
@@ -573,8 +656,14 @@ def bench_kv_append(row, kv):
     stream = torch.cuda.current_stream().cuda_stream
     src, dst = (torch.empty(2 * batch * seq_new * kv_heads * hd, device="cuda", dtype=tdt) for _ in range(2))
 
+    scales = [torch.full((kv_heads,), 0.0173, device="cuda") for _ in range(2)]
+
     def append():
         lens.copy_(start)
+        if kv == "fp8":
+            cb._ffi.check(lib.brn_kv_cache_append_fp8(k_new.data_ptr(), v_new.data_ptr(), batch, seq_new, kv_heads, hd, 0, kp.data_ptr(), vp.data_ptr(), scales[0].data_ptr(),
+                                                      scales[1].data_ptr(), table.data_ptr(), lens.data_ptr(), lens.data_ptr(), n_pages, page, pages_per_seq, 1, 0, stream))
+            return kp
         cb._ffi.check(lib.brn_kv_cache_append(k_new.data_ptr(), v_new.data_ptr(), batch, seq_new, kv_heads, hd, 0, kp.data_ptr(), vp.data_ptr(),
                                               {"f32": 0, "bf16": 1, "f16": 2}[kv], table.data_ptr(), lens.data_ptr(), lens.data_ptr(), n_pages, page, pages_per_seq, 1, 0, stream))
         return kp
@@ -602,6 +691,7 @@ if __name__ == "__main__":
     ap.add_argument("--splitkv", action="store_true", help="time brn_flash_attention_splitkv_forward at kv_splits 1 .. 64 and 0 beside the gqa entry")
     ap.add_argument("--paged", action="store_true", help="time brn_flash_attention_paged_forward (pages of 16 / 64 / 256, identity and shuffled tables) beside the split entry")
     ap.add_argument("--paged-kv16", action="store_true", help="time brn_flash_attention_paged_kv_forward on 16-bit pools beside the fp32-pool entry, and brn_kv_cache_append beside a copy")
+    ap.add_argument("--paged-fp8", action="store_true", help="time brn_flash_attention_paged_fp8_forward on an e4m3 pool beside the 16-bit-pool and fp32-pool entries, and brn_kv_cache_append_fp8 beside a copy")
     ap.add_argument("--row", type=int, choices=range(len(BIAS_ROWS)))
     ap.add_argument("--mode", choices=MODES)
     ap.add_argument("--json", help="write the records to this file")
@@ -610,8 +700,20 @@ if __name__ == "__main__":
     if cb.device_count() < 1:
         sys.exit("no HIP device: nothing is measured")
     recs = []
-    if a.bias + a.gqa + a.varlen + a.splitkv + a.paged + a.paged_kv16 > 1:
-        sys.exit("--bias, --gqa, --varlen, --splitkv, --paged and --paged-kv16 are separate tables: one at a time")
+    if a.bias + a.gqa + a.varlen + a.splitkv + a.paged + a.paged_kv16 + a.paged_fp8 > 1:
+        sys.exit("--bias, --gqa, --varlen, --splitkv, --paged, --paged-kv16 and --paged-fp8 are separate tables: one at a time")
+    if a.paged_fp8:
+        for row in (PAGED_ROWS if a.row is None else [PAGED_ROWS[a.row]] if a.row < len(PAGED_ROWS) else sys.exit(f"--row {a.row}: only {len(PAGED_ROWS)} rows in this table")):
+            for mode in (["bf16", "f16", "f32"] if a.mode is None else [a.mode]):
+                recs += bench_paged_fp8(row, mode)
+        appends = []
+        if a.row is None:
+            for row in KV_APPEND_ROWS:
+                appends += bench_kv_append(row, "fp8")
+        with open(a.json or PAGED_FP8_JSON, "w") as f:
+            json.dump({"tool": "tools/bench_flash_attention.py --paged-fp8", "warmup": GQA_WARMUP, "timed": GQA_ROUNDS * GQA_TIMED, "rows": recs, "append": appends}, f, indent=1)
+            f.write("\n")
+        sys.exit(0)
     if a.paged_kv16:
         for row in (PAGED_ROWS if a.row is None else [PAGED_ROWS[a.row]] if a.row < len(PAGED_ROWS) else sys.exit(f"--row {a.row}: only {len(PAGED_ROWS)} rows in this table")):
             for pair in PAGED_KV16_PAIRS:
