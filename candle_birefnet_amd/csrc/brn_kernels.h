@@ -258,8 +258,27 @@ struct KvAppendParams {
     // brn_kv_cache_append_fp8: kv_type FA_KV_FP8, an e4m3fn pool of bytes.  An element x of K head h is stored as the byte of
     // clamp(x / k_scale[h], +-448) rounded to nearest even (v_scale for V); [kv_heads] fp32 on the device, or null = all ones
     const float* k_scale; const float* v_scale;
+    // brn_kv_cache_append_rope / _rope_fp8: rope_cos non-null selects the kernels' rope instantiation.  K token t of entry b is rotated
+    // by the rule of RopeParams at table row min(L_b + t, rope_n_pos - 1), in fp32, before the cast; V is not.  Null: the plain append
+    const float* rope_cos; const float* rope_sin;   // [rope_n_pos][rope_dim / 2] fp32, 16-byte aligned
+    int rope_n_pos, rope_dim, rope_style;
 };
 hipError_t launch_kv_cache_append(const KvAppendParams& p, hipStream_t s);
+
+// brn_rope_forward (kernels/kv_cache.hip): y = x with the first rot_dim elements of every head row rotated in pairs by the caller's
+// table.  Row p = min(max(positions[b], 0) + t, n_pos - 1) for token t of batch entry b (positions null = 0); pair i of rot_dim / 2 is
+// (x[i], x[i + rot_dim / 2]) for style 0 (HALF) and (x[2i], x[2i + 1]) for style 1 (INTERLEAVED);
+// a' = fl(fl(a cos[p][i]) - fl(b sin[p][i])), b' = fl(fl(b cos[p][i]) + fl(a sin[p][i])), never fused; d >= rot_dim is copied.
+// positions holds UNVALIDATED device data: no address depends on it except through the clamp.  y may be x (the same strides)
+struct RopeParams {
+    const float* x; float* y;                 // fp32, 16-byte aligned, head_dim contiguous
+    long sb, ss, sh;                          // element strides of both: batch entry, token, head
+    const float* cos; const float* sin;       // [n_pos][rot_dim / 2] fp32, 16-byte aligned
+    const int* positions;                     // [batch] or null
+    int batch, seq, heads, head_dim;          // head_dim 32, 64 or 128; batch * seq * heads * head_dim / 8 < 2^31
+    int n_pos, rot_dim, style;                // 1 <= n_pos <= 2^24; rot_dim a multiple of 16, 16 .. head_dim; style 0 or 1
+};
+hipError_t launch_rope(const RopeParams& p, hipStream_t s);
 
 // the index kernels of the generic window route (kernels/window_generic.hip; geometry: kernels/window_generic_geometry.h), window sides
 // 2 .. 32 other than the fused kernels' 12 and 7.  One struct for the three; each launcher reads the fields its kernel needs

@@ -643,10 +643,23 @@ brn_status brn_flash_attention_paged_fp8_forward(const float* q, const void* k_p
 // seq_new tokens per sequence into the pool, behind the keys each sequence has (kernels/kv_cache.hip).  Like the paged attention entries it
 // reads neither block_table nor kv_lens on the host for BRN_MEM_DEVICE, allocates nothing and does not synchronise.  BRN_MEM_HOST (a test
 // convenience) stages the whole pool up and copies it back whole.
-// One body for brn_kv_cache_append and brn_kv_cache_append_fp8 (fp8 = true: an e4m3fn pool of bytes and the two scale arrays).
+// The caller's rotary table of brn_rope_forward and the two rope appends: [n_pos, rot_dim / 2] fp32 each
+struct RopeTable { const float* cos; const float* sin; int n_pos, rot_dim, style; };
+static size_t rope_table_floats(const RopeTable& r) { return (size_t)r.n_pos * (r.rot_dim / 2); }
+// (head_dim has been checked)
+static void rope_table_check(const char* who, const RopeTable& r, int head_dim) {
+    if (!r.cos || !r.sin) fail(BRN_ERR_INVALID_ARG, "%s: null cos or sin", who);
+    if (r.rot_dim < 16 || r.rot_dim > head_dim || r.rot_dim % 16)
+        fail(BRN_ERR_INVALID_ARG, "%s: rot_dim %d unsupported (rot_dim must be a multiple of 16 with 16 <= rot_dim <= head_dim = %d)", who, r.rot_dim, head_dim);
+    if (r.style != BRN_ROPE_HALF && r.style != BRN_ROPE_INTERLEAVED) fail(BRN_ERR_INVALID_ARG, "%s: style %d unknown (style must be 0 = HALF or 1 = INTERLEAVED)", who, r.style);
+    if (r.n_pos < 1 || r.n_pos > (1 << 24)) fail(BRN_ERR_INVALID_ARG, "%s: n_pos %d unsupported (1 <= n_pos <= 2^24)", who, r.n_pos);
+}
+
+// One body for brn_kv_cache_append and brn_kv_cache_append_fp8 (fp8 = true: an e4m3fn pool of bytes and the two scale arrays) and their
+// rope forms (rope non-null: K is rotated by the table before the cast).
 static void kv_cache_append_body(const char* who, const float* k_new, const float* v_new, int batch, int seq_new, int kv_heads, int head_dim, int layout, void* k_pages,
                                  void* v_pages, int kv_type, bool fp8, const float* k_scale, const float* v_scale, const int* block_table, const int* kv_lens,
-                                 int* kv_lens_out, int n_pages, int page_size, int max_pages, brn_mem loc, int device, void* stream) {
+                                 int* kv_lens_out, int n_pages, int page_size, int max_pages, brn_mem loc, int device, void* stream, const RopeTable* rope = nullptr) {
     {
         if (!k_new || !v_new || !k_pages || !v_pages) fail(BRN_ERR_INVALID_ARG, "%s: null k_new, v_new, k_pages or v_pages", who);
         if (!block_table || !kv_lens) fail(BRN_ERR_INVALID_ARG, "%s: null block_table or kv_lens", who);
@@ -654,6 +667,7 @@ static void kv_cache_append_body(const char* who, const float* k_new, const floa
         else kv_type_check(who, kv_type);
         if (!(head_dim == 32 || head_dim == 64 || head_dim == 128))
             fail(BRN_ERR_INVALID_ARG, "%s: head_dim %d unsupported (head_dim must be 32, 64 or 128)", who, head_dim);
+        if (rope) rope_table_check(who, *rope, head_dim);
         if (batch < 1 || kv_heads < 1) fail(BRN_ERR_INVALID_ARG, "%s: batch %d, kv_heads %d unsupported (batch >= 1, kv_heads >= 1)", who, batch, kv_heads);
         if (seq_new < 1 || seq_new > 65536) fail(BRN_ERR_INVALID_ARG, "%s: seq_new %d unsupported (1 <= seq_new <= 65536)", who, seq_new);
         if (layout != BRN_ATTN_BSHD && layout != BRN_ATTN_BHSD) fail(BRN_ERR_INVALID_ARG, "%s: layout %d unknown (layout must be 0 = BSHD or 1 = BHSD)", who, layout);
@@ -668,7 +682,9 @@ static void kv_cache_append_body(const char* who, const float* k_new, const floa
         const size_t pool_floats = npool * kv_type_bytes(kv_type) / 4, ntab = (size_t)batch * max_pages;
         const struct { const void* p; size_t n; const char* name; } ins[] = {{k_new, nnew * 4, "k_new"}, {v_new, nnew * 4, "v_new"}, {block_table, ntab * 4, "block_table"},
                                                                              {kv_lens, (size_t)batch * 4, "kv_lens"}, {k_scale, (size_t)kv_heads * 4, "k_scale"},
-                                                                             {v_scale, (size_t)kv_heads * 4, "v_scale"}};
+                                                                             {v_scale, (size_t)kv_heads * 4, "v_scale"},
+                                                                             {rope ? rope->cos : nullptr, rope ? rope_table_floats(*rope) * 4 : 0, "cos"},
+                                                                             {rope ? rope->sin : nullptr, rope ? rope_table_floats(*rope) * 4 : 0, "sin"}};
         for (const auto& in : ins)
             if (bytes_overlap(in.p, in.n, k_pages, pool_floats * 4) || bytes_overlap(in.p, in.n, v_pages, pool_floats * 4))
                 fail(BRN_ERR_INVALID_ARG, "%s: %s must not overlap the pool", who, in.name);
@@ -686,9 +702,14 @@ static void kv_cache_append_body(const char* who, const float* k_new, const floa
             fail(BRN_ERR_INVALID_ARG, "%s: device block_table, kv_lens and kv_lens_out must be 4-byte aligned", who);
         if (loc == BRN_MEM_DEVICE && ((reinterpret_cast<uintptr_t>(k_scale) | reinterpret_cast<uintptr_t>(v_scale)) & 3))
             fail(BRN_ERR_INVALID_ARG, "%s: device k_scale and v_scale must be 4-byte aligned", who);
+        if (rope && loc == BRN_MEM_DEVICE && !all_aligned16({rope->cos, rope->sin})) fail(BRN_ERR_INVALID_ARG, "%s: device cos and sin must be 16-byte aligned", who);
         ensure_device(device);
         Staging st(stream, loc);
         KvAppendParams p{};
+        if (rope) {
+            p.rope_cos = st.in(rope->cos, rope_table_floats(*rope)); p.rope_sin = st.in(rope->sin, rope_table_floats(*rope));
+            p.rope_n_pos = rope->n_pos; p.rope_dim = rope->rot_dim; p.rope_style = rope->style;
+        }
         if (k_scale) p.k_scale = st.in(k_scale, (size_t)kv_heads);
         if (v_scale) p.v_scale = st.in(v_scale, (size_t)kv_heads);
         p.k_new = st.in(k_new, nnew); p.v_new = st.in(v_new, nnew);
@@ -734,6 +755,68 @@ brn_status brn_kv_cache_append_fp8(const float* k_new, const float* v_new, int b
     return guarded([&] {
         kv_cache_append_body("kv cache append fp8", k_new, v_new, batch, seq_new, kv_heads, head_dim, layout, k_pages, v_pages, FA_KV_FP8, true, k_scale, v_scale, block_table,
                              kv_lens, kv_lens_out, n_pages, page_size, max_pages, loc, device, stream);
+    });
+}
+
+brn_status brn_kv_cache_append_rope(const float* k_new, const float* v_new, int batch, int seq_new, int kv_heads, int head_dim, int layout, const float* cos,
+                                    const float* sin, int n_pos, int rot_dim, int style, void* k_pages, void* v_pages, int kv_type, const int* block_table,
+                                    const int* kv_lens, int* kv_lens_out, int n_pages, int page_size, int max_pages, brn_mem loc, int device, void* stream) {
+    return guarded([&] {
+        const RopeTable rope{cos, sin, n_pos, rot_dim, style};
+        kv_cache_append_body("kv cache append rope", k_new, v_new, batch, seq_new, kv_heads, head_dim, layout, k_pages, v_pages, kv_type, false, nullptr, nullptr, block_table,
+                             kv_lens, kv_lens_out, n_pages, page_size, max_pages, loc, device, stream, &rope);
+    });
+}
+
+brn_status brn_kv_cache_append_rope_fp8(const float* k_new, const float* v_new, int batch, int seq_new, int kv_heads, int head_dim, int layout, const float* cos,
+                                        const float* sin, int n_pos, int rot_dim, int style, void* k_pages, void* v_pages, const float* k_scale, const float* v_scale,
+                                        const int* block_table, const int* kv_lens, int* kv_lens_out, int n_pages, int page_size, int max_pages, brn_mem loc,
+                                        int device, void* stream) {
+    return guarded([&] {
+        const RopeTable rope{cos, sin, n_pos, rot_dim, style};
+        kv_cache_append_body("kv cache append rope fp8", k_new, v_new, batch, seq_new, kv_heads, head_dim, layout, k_pages, v_pages, FA_KV_FP8, true, k_scale, v_scale,
+                             block_table, kv_lens, kv_lens_out, n_pages, page_size, max_pages, loc, device, stream, &rope);
+    });
+}
+
+// Rotary embedding of q (or of k at prefill) by the caller's table (kernels/kv_cache.hip, RopeParams).  positions is device data for
+// BRN_MEM_DEVICE: never read on the host, clamped by the kernel; the call allocates nothing and does not synchronise.
+brn_status brn_rope_forward(const float* x, int batch, int seq, int heads, int head_dim, int layout, const float* cos, const float* sin, int n_pos, int rot_dim,
+                            int style, const int* positions, float* y, brn_mem loc, int device, void* stream) {
+    return guarded([&] {
+        const char* who = "rope";
+        if (!x || !y) fail(BRN_ERR_INVALID_ARG, "%s: null x or y", who);
+        if (!(head_dim == 32 || head_dim == 64 || head_dim == 128))
+            fail(BRN_ERR_INVALID_ARG, "%s: head_dim %d unsupported (head_dim must be 32, 64 or 128)", who, head_dim);
+        const RopeTable rope{cos, sin, n_pos, rot_dim, style};
+        rope_table_check(who, rope, head_dim);
+        if (batch < 1 || heads < 1) fail(BRN_ERR_INVALID_ARG, "%s: batch %d, heads %d unsupported (batch >= 1, heads >= 1)", who, batch, heads);
+        if (seq < 1 || seq > 65536) fail(BRN_ERR_INVALID_ARG, "%s: seq %d unsupported (1 <= seq <= 65536)", who, seq);
+        if (layout != BRN_ATTN_BSHD && layout != BRN_ATTN_BHSD) fail(BRN_ERR_INVALID_ARG, "%s: layout %d unknown (layout must be 0 = BSHD or 1 = BHSD)", who, layout);
+        // the grid: a thread per 8 elements of a row at the most
+        const long long per_b = (long long)seq * heads * (head_dim / 8);
+        if (per_b > 0x7fffffffLL || per_b * batch > 0x7fffffffLL)
+            fail(BRN_ERR_INVALID_ARG, "%s: batch %d, seq %d, heads %d too large (batch * seq * heads * head_dim / 8 < 2^31)", who, batch, seq, heads);
+        const size_t n = (size_t)batch * seq * heads * head_dim, ntab = rope_table_floats(rope);
+        if (y != x && bytes_overlap(x, n * 4, y, n * 4)) fail(BRN_ERR_INVALID_ARG, "%s: y must be x itself (in place) or not overlap x", who);
+        const struct { const void* p; size_t n; const char* name; } ins[] = {{cos, ntab * 4, "cos"}, {sin, ntab * 4, "sin"}, {positions, (size_t)batch * 4, "positions"}};
+        for (const auto& in : ins)
+            if (bytes_overlap(in.p, in.n, y, n * 4)) fail(BRN_ERR_INVALID_ARG, "%s: %s must not overlap y", who, in.name);
+        if (loc == BRN_MEM_DEVICE && !all_aligned16({x, y, cos, sin})) fail(BRN_ERR_INVALID_ARG, "%s: device x, y, cos and sin must be 16-byte aligned", who);
+        if (loc == BRN_MEM_DEVICE && (reinterpret_cast<uintptr_t>(positions) & 3)) fail(BRN_ERR_INVALID_ARG, "%s: device positions must be 4-byte aligned", who);
+        ensure_device(device);
+        Staging st(stream, loc);
+        RopeParams p{};
+        p.x = st.in(x, n); p.y = st.out(y, n);
+        p.cos = st.in(cos, ntab); p.sin = st.in(sin, ntab);
+        if (positions) p.positions = reinterpret_cast<const int*>(st.in(reinterpret_cast<const float*>(positions), (size_t)batch));
+        p.batch = batch; p.seq = seq; p.heads = heads; p.head_dim = head_dim;
+        const long d = head_dim;
+        if (layout == BRN_ATTN_BSHD) { p.ss = heads * d; p.sh = d; p.sb = seq * p.ss; }
+        else { p.ss = d; p.sh = seq * d; p.sb = heads * p.sh; }
+        p.n_pos = n_pos; p.rot_dim = rot_dim; p.style = style;
+        BRN_HIP(launch_rope(p, (hipStream_t)stream));
+        st.finish();
     });
 }
 

@@ -18,6 +18,10 @@
 // selects in plain C++, which keep a NaN; t rounded to nearest even by v_cvt_pk_fp8_f32.  Saturation is the clamp's, so it does not
 // depend on what the instruction does on overflow; +-0 and underflow keep their sign; a NaN becomes a NaN byte.  The thread map is the
 // same: 8 d per thread, one 8-byte store of K and of V.  No address depends on a scale.
+//
+// brn_rope_forward (rope_kernel) and the rope instantiation kv_append_rows_kernel<KV, true> (brn_kv_cache_append_rope / _rope_fp8) rotate
+// pairs of a row by the caller's cos / sin table; RopeParams in brn_kernels.h states the rule.  The table row is min(position, n_pos - 1),
+// the position device data, clamped like the lengths; the rotation is two rounded products and one rounded sum, never an fma (rope_pair).
 #include "../brn_kernels.h"
 #include "attention_mfma.h"
 #include <type_traits>
@@ -52,6 +56,48 @@ __device__ __forceinline__ void kv_store8_fp8(kv_e4m3* dst, const f32x4 a, const
 }
 
 template <typename KV>
+__device__ __forceinline__ void kv_put8(void* pages, long dst, const f32x4 a, const f32x4 b, const float* scale, int h) {
+    if constexpr (std::is_same<KV, kv_e4m3>::value) kv_store8_fp8(static_cast<KV*>(pages) + dst, a, b, scale ? scale[h] : 1.f);
+    else kv_store8(static_cast<KV*>(pages) + dst, a, b);
+}
+
+__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+
+// ---- the rotation (RopeParams in brn_kernels.h states the rule) ----
+// one pair: two rounded products, then one rounded difference / sum (the rule is promised bit for bit).  The pragma keeps the four
+// products out of an fma under hipcc's default -ffp-contract=fast-honor-pragmas and under on / off, which is every way the Makefile
+// builds this file; an explicit -ffp-contract=fast would let the backend fuse in spite of it and must not be given to this file
+__device__ __forceinline__ void rope_pair(float a, float b, float c, float s, float& ra, float& rb) {
+#pragma clang fp contract(off)
+    const float ac = a * c, bs = b * s, bc = b * c, as = a * s;
+    ra = ac - bs;
+    rb = bc + as;
+}
+// HALF: lo = x[8c .. 8c + 8), hi = x[8c + rot_dim / 2 ..), cs / sn = the table row's [8c .. 8c + 8)
+__device__ __forceinline__ void rope_half8(f32x4& lo0, f32x4& lo1, f32x4& hi0, f32x4& hi1, const float* cs, const float* sn) {
+    const f32x4 c0 = ld4(cs), c1 = ld4(cs + 4), s0 = ld4(sn), s1 = ld4(sn + 4);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        float a, b;
+        rope_pair(lo0[j], hi0[j], c0[j], s0[j], a, b); lo0[j] = a; hi0[j] = b;
+        rope_pair(lo1[j], hi1[j], c1[j], s1[j], a, b); lo1[j] = a; hi1[j] = b;
+    }
+}
+// INTERLEAVED: x0, x1 = x[8c .. 8c + 8), cs / sn = the table row's [4c .. 4c + 4)
+__device__ __forceinline__ void rope_inter8(f32x4& x0, f32x4& x1, const float* cs, const float* sn) {
+    const f32x4 c = ld4(cs), s = ld4(sn);
+    float a, b;
+    rope_pair(x0[0], x0[1], c[0], s[0], a, b); x0[0] = a; x0[1] = b;
+    rope_pair(x0[2], x0[3], c[1], s[1], a, b); x0[2] = a; x0[3] = b;
+    rope_pair(x1[0], x1[1], c[2], s[2], a, b); x1[0] = a; x1[1] = b;
+    rope_pair(x1[2], x1[3], c[3], s[3], a, b); x1[2] = a; x1[3] = b;
+}
+
+// ROPE (brn_kv_cache_append_rope / _rope_fp8): K is rotated at table row min(pos, rope_n_pos - 1) before the store; V and everything
+// else is the plain append's.  The thread map stays one thread per 8 d of a row; for K in HALF style the thread of chunk c < rope_dim / 16
+// also takes chunk c + rope_dim / 16 (both members of its pairs), the threads of those upper chunks touch V alone.  Every element of
+// k_new is still read once and every pool element written once
+template <typename KV, bool ROPE>
 __global__ void __launch_bounds__(KV_THREADS) kv_append_rows_kernel(const KvAppendParams p) {
     const int C8 = p.head_dim >> 3;
     const long idx = (long)blockIdx.x * KV_THREADS + threadIdx.x;
@@ -67,20 +113,72 @@ __global__ void __launch_bounds__(KV_THREADS) kv_append_rows_kernel(const KvAppe
     const int page = min(max(p.block_table[(long)b * p.max_pages + slot], 0), p.n_pages - 1);
     const long dst = (long)page * p.page_stride + (pos & ((1 << p.page_log2) - 1)) * p.kv_ss + h * p.head_dim + c8;
     const long src = b * p.new_sb + t * p.new_ss + h * p.new_sh + c8;
-    const f32x4 k0 = *reinterpret_cast<const f32x4*>(p.k_new + src), k1 = *reinterpret_cast<const f32x4*>(p.k_new + src + 4);
-    const f32x4 v0 = *reinterpret_cast<const f32x4*>(p.v_new + src), v1 = *reinterpret_cast<const f32x4*>(p.v_new + src + 4);
-    if constexpr (std::is_same<KV, kv_e4m3>::value) {
-        kv_store8_fp8(static_cast<KV*>(p.k_pages) + dst, k0, k1, p.k_scale ? p.k_scale[h] : 1.f);
-        kv_store8_fp8(static_cast<KV*>(p.v_pages) + dst, v0, v1, p.v_scale ? p.v_scale[h] : 1.f);
+    if constexpr (ROPE) {
+        const int half = p.rope_dim >> 1;
+        const float* cs = p.rope_cos + (long)min(pos, (long)p.rope_n_pos - 1) * half;
+        const float* sn = p.rope_sin + (cs - p.rope_cos);
+        if (p.rope_style == 0) {
+            if (c8 < half) {
+                f32x4 lo0 = ld4(p.k_new + src), lo1 = ld4(p.k_new + src + 4), hi0 = ld4(p.k_new + src + half), hi1 = ld4(p.k_new + src + half + 4);
+                rope_half8(lo0, lo1, hi0, hi1, cs + c8, sn + c8);
+                kv_put8<KV>(p.k_pages, dst, lo0, lo1, p.k_scale, h);
+                kv_put8<KV>(p.k_pages, dst + half, hi0, hi1, p.k_scale, h);
+            } else if (c8 >= p.rope_dim) kv_put8<KV>(p.k_pages, dst, ld4(p.k_new + src), ld4(p.k_new + src + 4), p.k_scale, h);
+        } else {
+            f32x4 k0 = ld4(p.k_new + src), k1 = ld4(p.k_new + src + 4);
+            if (c8 < p.rope_dim) rope_inter8(k0, k1, cs + (c8 >> 1), sn + (c8 >> 1));
+            kv_put8<KV>(p.k_pages, dst, k0, k1, p.k_scale, h);
+        }
+        kv_put8<KV>(p.v_pages, dst, ld4(p.v_new + src), ld4(p.v_new + src + 4), p.v_scale, h);
     } else {
-        kv_store8(static_cast<KV*>(p.k_pages) + dst, k0, k1);
-        kv_store8(static_cast<KV*>(p.v_pages) + dst, v0, v1);
+        const f32x4 k0 = ld4(p.k_new + src), k1 = ld4(p.k_new + src + 4);
+        const f32x4 v0 = ld4(p.v_new + src), v1 = ld4(p.v_new + src + 4);
+        kv_put8<KV>(p.k_pages, dst, k0, k1, p.k_scale, h);
+        kv_put8<KV>(p.v_pages, dst, v0, v1, p.v_scale, h);
     }
+}
+
+// brn_rope_forward: one thread = 8 consecutive d of a (b, t, head) row, two 16-byte loads and stores; in HALF style the thread of chunk
+// c < rot_dim / 16 owns chunk c + rot_dim / 16 too, so a row has head_dim / 8 - rot_dim / 16 threads and both members of every pair are in
+// one thread's registers before either is written: y may be x.  Chunks at or past rot_dim are copied.  Threads run d-fastest, then head,
+// then token.  The table row comes from device data through a clamp
+__global__ void __launch_bounds__(KV_THREADS) rope_kernel(const RopeParams p) {
+    const int C8 = p.head_dim >> 3, R16 = p.rot_dim >> 4, half = p.rot_dim >> 1;
+    const int W = p.style == 0 ? C8 - R16 : C8;
+    const long idx = (long)blockIdx.x * KV_THREADS + threadIdx.x;
+    const long per_b = (long)p.seq * p.heads * W;
+    if (idx >= per_b * p.batch) return;
+    const int b = (int)(idx / per_b);
+    const int r = (int)(idx - b * per_b);                          // < seq * heads * head_dim / 8 (launch_rope: < 2^31)
+    const int t = r / (p.heads * W), hw = r - t * (p.heads * W);
+    const int h = hw / W, w = hw - h * W;
+    const long P = p.positions ? max(p.positions[b], 0) : 0;
+    const long row = min(P + t, (long)p.n_pos - 1);
+    const float* cs = p.cos + row * half;
+    const float* sn = p.sin + row * half;
+    const long off = b * p.sb + t * p.ss + h * p.sh;
+    if (p.style == 0 && w < R16) {
+        const long o = off + w * 8;
+        f32x4 lo0 = ld4(p.x + o), lo1 = ld4(p.x + o + 4), hi0 = ld4(p.x + o + half), hi1 = ld4(p.x + o + half + 4);
+        rope_half8(lo0, lo1, hi0, hi1, cs + w * 8, sn + w * 8);
+        *reinterpret_cast<f32x4*>(p.y + o) = lo0; *reinterpret_cast<f32x4*>(p.y + o + 4) = lo1;
+        *reinterpret_cast<f32x4*>(p.y + o + half) = hi0; *reinterpret_cast<f32x4*>(p.y + o + half + 4) = hi1;
+        return;
+    }
+    const int c8 = (p.style == 0 ? w + R16 : w) * 8;               // HALF: the chunks past rot_dim; INTERLEAVED: every chunk
+    f32x4 x0 = ld4(p.x + off + c8), x1 = ld4(p.x + off + c8 + 4);
+    if (p.style != 0 && c8 < p.rot_dim) rope_inter8(x0, x1, cs + (c8 >> 1), sn + (c8 >> 1));
+    *reinterpret_cast<f32x4*>(p.y + off + c8) = x0; *reinterpret_cast<f32x4*>(p.y + off + c8 + 4) = x1;
 }
 
 __global__ void __launch_bounds__(KV_THREADS) kv_append_lens_kernel(const KvAppendParams p) {
     for (int b = threadIdx.x; b < p.batch; b += KV_THREADS)
         p.kv_lens_out[b] = (int)min((long)min(max(p.kv_lens[b], 0), p.cap) + p.seq_new, (long)p.cap);
+}
+
+// what both launchers ask of a table: the kernels index it with nothing but a clamped row and chunk offsets below rot_dim / 2
+bool rope_table_ok(const float* cs, const float* sn, int n_pos, int rot_dim, int style, int head_dim) {
+    return cs && sn && n_pos >= 1 && n_pos <= (1 << 24) && rot_dim >= 16 && rot_dim <= head_dim && rot_dim % 16 == 0 && (style == 0 || style == 1);
 }
 
 }  // namespace
@@ -96,11 +194,30 @@ hipError_t launch_kv_cache_append(const KvAppendParams& p, hipStream_t s) {
     const long blocks = (per_b * p.batch + KV_THREADS - 1) / KV_THREADS;
     if (per_b > 0x7fffffffL || blocks > 0x7fffffffL) return hipErrorInvalidValue;
     const dim3 grid((unsigned)blocks), block(KV_THREADS);
-    if (p.kv_type == 0) hipLaunchKernelGGL(kv_append_rows_kernel<float>, grid, block, 0, s, p);
-    else if (p.kv_type == 1) hipLaunchKernelGGL(kv_append_rows_kernel<__bf16>, grid, block, 0, s, p);
-    else if (p.kv_type == 2) hipLaunchKernelGGL(kv_append_rows_kernel<_Float16>, grid, block, 0, s, p);
-    else hipLaunchKernelGGL(kv_append_rows_kernel<kv_e4m3>, grid, block, 0, s, p);
+    if (p.rope_cos) {
+        if (!rope_table_ok(p.rope_cos, p.rope_sin, p.rope_n_pos, p.rope_dim, p.rope_style, p.head_dim)) return hipErrorInvalidValue;
+        if (p.kv_type == 0) hipLaunchKernelGGL((kv_append_rows_kernel<float, true>), grid, block, 0, s, p);
+        else if (p.kv_type == 1) hipLaunchKernelGGL((kv_append_rows_kernel<__bf16, true>), grid, block, 0, s, p);
+        else if (p.kv_type == 2) hipLaunchKernelGGL((kv_append_rows_kernel<_Float16, true>), grid, block, 0, s, p);
+        else hipLaunchKernelGGL((kv_append_rows_kernel<kv_e4m3, true>), grid, block, 0, s, p);
+    } else if (p.rope_sin) return hipErrorInvalidValue;
+    else if (p.kv_type == 0) hipLaunchKernelGGL((kv_append_rows_kernel<float, false>), grid, block, 0, s, p);
+    else if (p.kv_type == 1) hipLaunchKernelGGL((kv_append_rows_kernel<__bf16, false>), grid, block, 0, s, p);
+    else if (p.kv_type == 2) hipLaunchKernelGGL((kv_append_rows_kernel<_Float16, false>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((kv_append_rows_kernel<kv_e4m3, false>), grid, block, 0, s, p);
     if (p.kv_lens_out) hipLaunchKernelGGL(kv_append_lens_kernel, dim3(1), block, 0, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_rope(const RopeParams& p, hipStream_t s) {
+    if (!(p.head_dim == 32 || p.head_dim == 64 || p.head_dim == 128) || p.batch < 1 || p.heads < 1 || p.seq < 1 || p.seq > 65536 || !p.x || !p.y ||
+        !rope_table_ok(p.cos, p.sin, p.n_pos, p.rot_dim, p.style, p.head_dim))
+        return hipErrorInvalidValue;
+    const int W = p.head_dim / 8 - (p.style == 0 ? p.rot_dim / 16 : 0);
+    const long per_b = (long)p.seq * p.heads * (p.head_dim / 8);
+    if (per_b > 0x7fffffffL || per_b * p.batch > 0x7fffffffL) return hipErrorInvalidValue;
+    const long blocks = ((long)p.batch * p.seq * p.heads * W + KV_THREADS - 1) / KV_THREADS;
+    hipLaunchKernelGGL(rope_kernel, dim3((unsigned)blocks), dim3(KV_THREADS), 0, s, p);
     return hipGetLastError();
 }
 

@@ -436,8 +436,95 @@ def kv_cache_append_fp8(k_new, v_new, k_pages, v_pages, k_scale, v_scale, block_
     return _kv_cache_append(k_new, v_new, k_pages, v_pages, block_table, kv_lens, "fp8", layout, update_lens, device, (k_scale, v_scale))
 
 
-def _kv_cache_append(k_new, v_new, k_pages, v_pages, block_table, kv_lens, kv_dtype, layout, update_lens, device, scales):
-    """the body of kv_cache_append (scales None) and kv_cache_append_fp8 (kv_dtype "fp8", scales = (k_scale, v_scale))"""
+_ROPE_STYLE = {"half": _ffi.BRN_ROPE_HALF, "interleaved": _ffi.BRN_ROPE_INTERLEAVED}
+
+
+def rope_table(n_pos, rot_dim, theta=10000.0):
+    """(cos, sin), each [n_pos, rot_dim / 2] float32: the angles p * theta^(-2 i / rot_dim) computed in float64 with numpy and rounded to
+    fp32 once.  A convenience: the library takes any table (a scaled or interpolated one included) and promises its result for the
+    table it is given, not for this one."""
+    n_pos, rot_dim = int(n_pos), int(rot_dim)
+    if n_pos < 1 or rot_dim < 2 or rot_dim % 2:
+        raise ValueError("rope_table needs n_pos >= 1 and an even rot_dim >= 2")
+    ang = np.arange(n_pos, dtype=np.float64)[:, None] * float(theta) ** (-np.arange(0, rot_dim, 2, dtype=np.float64) / rot_dim)[None, :]
+    return np.cos(ang).astype(np.float32), np.sin(ang).astype(np.float32)
+
+
+def _rope_table_arg(cos, sin, loc):
+    """the two halves of a table on the side `loc` -> (cos pointer, sin pointer, n_pos, rot_dim, keepalives)"""
+    if len(cos.shape) != 2:
+        raise ValueError("cos and sin must be [n_pos, rot_dim / 2]")
+    n_pos, half = int(cos.shape[0]), int(cos.shape[1])
+    pc, cloc, ckeep, _ = T.as_arg(cos, (n_pos, half))
+    ps, sloc, skeep, _ = T.as_arg(sin, (n_pos, half))
+    if not (cloc == sloc == loc):
+        raise ValueError("cos and sin must live on the side of the tensor they rotate")
+    return pc, ps, n_pos, 2 * half, (ckeep, skeep)
+
+
+def rope(x, cos, sin, positions=None, rot_dim=None, style="half", layout="bshd", out=None, device=0):
+    """brn_rope_forward: x (fp32; layout "bshd" [batch, seq, heads, head_dim] or "bhsd") with the first rot_dim elements of every head
+    row rotated in pairs; cos, sin [n_pos, rot_dim / 2] fp32 (rope_table makes the usual one), all on x's side.  Token t of batch entry b
+    uses table row min(max(positions[b], 0) + t, n_pos - 1); positions [batch] int32 or None = all 0.  style "half" pairs x[i] with
+    x[i + rot_dim / 2] (NeoX / Llama), "interleaved" pairs x[2i] with x[2i + 1] (GPT-J); a' = fl(fl(a cos) - fl(b sin)),
+    b' = fl(fl(b cos) + fl(a sin)) in fp32, never fused; elements past rot_dim are copied.  rot_dim None: what the table says; a value
+    must agree with it.  out: None = a new array beside x; x itself = in place; any other array of x's shape on x's side.
+    For host inputs only, the wrapper refuses max(positions) + seq > n_pos (the library would clamp it to the last row).  Device
+    tensors are not read back."""
+    lay = _ATTN_LAYOUT[layout]
+    seq_axis, head_axis = (1, 2) if lay == _ffi.BRN_ATTN_BSHD else (2, 1)
+    shape = tuple(int(v) for v in x.shape)
+    batch, hd, seq, heads = shape[0], shape[3], shape[seq_axis], shape[head_axis]
+    px, loc, keep, _ = T.as_arg(x)
+    pc, ps, n_pos, rd, rkeep = _rope_table_arg(cos, sin, loc)
+    if rot_dim is not None and int(rot_dim) != rd:
+        raise ValueError(f"rot_dim {rot_dim} does not agree with the table's {rd} (cos and sin are [n_pos, rot_dim / 2])")
+    pp, ph = None, None
+    if positions is not None:
+        pp, ploc, pkeep, ph = _int32_arg(positions, (batch,), "positions")
+        if ploc != loc:
+            raise ValueError("positions must live on x's side")
+    pmax = max(int(ph.max()), 0) if ph is not None and ph.size else 0
+    if loc == _ffi.BRN_MEM_HOST and pmax + seq > n_pos:
+        raise ValueError(f"max(positions) + seq = {pmax + seq} runs past the table (n_pos = {n_pos})")
+    if out is None:
+        y = T.alloc_like(keep, shape)
+    elif out is x:
+        if keep is not x and not (T._is_torch(x) and keep.data_ptr() == x.data_ptr()):
+            raise TypeError("out=x needs x as a contiguous float32 tensor or array (it is written in place)")
+        y = x
+    else:
+        if tuple(int(v) for v in out.shape) != shape:
+            raise ValueError(f"out: expected shape {shape}, got {tuple(out.shape)}")
+        py, yloc, ykeep, _ = T.as_arg(out)
+        if yloc != loc or (ykeep is not out and not (T._is_torch(out) and ykeep.data_ptr() == out.data_ptr())):
+            raise TypeError("out must be a contiguous float32 tensor or array on x's side (it is written in place)")
+        y = out
+    _ffi.check(_ffi.lib.brn_rope_forward(px, batch, seq, heads, hd, lay, pc, ps, n_pos, rd, _ROPE_STYLE[style], pp, T.ptr_of(y), loc,
+                                         T.device_of(keep, device), T.stream_of(keep)))
+    return y
+
+
+def kv_cache_append_rope(k_new, v_new, cos, sin, k_pages, v_pages, block_table, kv_lens, kv_dtype=None, style="half", layout="bshd", update_lens=True, device=0):
+    """brn_kv_cache_append_rope: kv_cache_append with K token t of batch entry b rotated by rope's rule at table row
+    min(L_b + t, n_pos - 1), the position it takes in the cache, in fp32 before the cast; V is not rotated.  cos, sin: the table of rope
+    on k_new's side (rot_dim is the table's).  The pool and the lengths carry the bits of kv_cache_append on
+    rope(k_new, cos, sin, positions=kv_lens).  Everything else is kv_cache_append's.
+    For host inputs only, the wrapper also refuses max(min(L_b + seq_new, cap)) > n_pos.  Device tensors are not read back."""
+    if kv_dtype not in _KV_TYPE:
+        raise ValueError(f"kv_dtype {kv_dtype!r} unknown (None, 'f32', 'bf16' or 'f16')")
+    return _kv_cache_append(k_new, v_new, k_pages, v_pages, block_table, kv_lens, kv_dtype or "f32", layout, update_lens, device, None, (cos, sin, style))
+
+
+def kv_cache_append_rope_fp8(k_new, v_new, cos, sin, k_pages, v_pages, k_scale, v_scale, block_table, kv_lens, style="half", layout="bshd", update_lens=True, device=0):
+    """brn_kv_cache_append_rope_fp8: kv_cache_append_fp8 with K rotated as in kv_cache_append_rope, in fp32, in front of the fp8 store
+    (divide by the head's scale, clamp to +-448, round to nearest even)."""
+    return _kv_cache_append(k_new, v_new, k_pages, v_pages, block_table, kv_lens, "fp8", layout, update_lens, device, (k_scale, v_scale), (cos, sin, style))
+
+
+def _kv_cache_append(k_new, v_new, k_pages, v_pages, block_table, kv_lens, kv_dtype, layout, update_lens, device, scales, rope=None):
+    """the body of kv_cache_append (scales None) and kv_cache_append_fp8 (kv_dtype "fp8", scales = (k_scale, v_scale)); rope =
+    (cos, sin, style): their rope forms"""
     lay = _ATTN_LAYOUT[layout]
     seq_axis, head_axis = (1, 2) if lay == _ffi.BRN_ATTN_BSHD else (2, 1)
     batch, hd = int(k_new.shape[0]), int(k_new.shape[3])
@@ -460,6 +547,11 @@ def _kv_cache_append(k_new, v_new, k_pages, v_pages, block_table, kv_lens, kv_dt
         if any(sl is not None and sl != loc for sl in (ksloc, vsloc)):
             raise ValueError("k_scale and v_scale must live on k_new's side")
     cap = max_pages * page_size
+    if rope is not None:
+        pc, ps, n_pos, rd, rkeep = _rope_table_arg(rope[0], rope[1], loc)    # (a name of its own: tkeep keeps block_table's copy alive)
+        table = (pc, ps, n_pos, rd, _ROPE_STYLE[rope[2]])
+        if lh is not None and lh.size and int(np.minimum(np.clip(lh, 0, cap).astype(np.int64) + seq_new, cap).max()) > n_pos:
+            raise ValueError(f"max(min(L_b + seq_new, cap)) runs past the table (n_pos = {n_pos})")
     if lh is not None and th is not None:
         if lh.size and (int(lh.min()) < 0 or int(lh.max()) > cap):
             raise ValueError(f"kv_lens must lie in 0 .. max_pages * page_size = {cap}")
@@ -481,12 +573,13 @@ def _kv_cache_append(k_new, v_new, k_pages, v_pages, block_table, kv_lens, kv_dt
         else:
             out = np.empty(batch, np.int32)
             po = out.ctypes.data
+    head = (pk, pv, batch, seq_new, kv_heads, hd, lay)
+    tail = (pt, pl, po, n_pages, page_size, max_pages, loc, T.device_of(keep, device), T.stream_of(keep))
     if scales is not None:
-        _ffi.check(_ffi.lib.brn_kv_cache_append_fp8(pk, pv, batch, seq_new, kv_heads, hd, lay, ppk, ppv, pks, pvs, pt, pl, po, n_pages, page_size, max_pages,
-                                                    loc, T.device_of(keep, device), T.stream_of(keep)))
-        return out
-    _ffi.check(_ffi.lib.brn_kv_cache_append(pk, pv, batch, seq_new, kv_heads, hd, lay, ppk, ppv, _KV_TYPE[kv_dtype], pt, pl, po, n_pages, page_size, max_pages,
-                                            loc, T.device_of(keep, device), T.stream_of(keep)))
+        fn, pool = (_ffi.lib.brn_kv_cache_append_fp8 if rope is None else _ffi.lib.brn_kv_cache_append_rope_fp8), (ppk, ppv, pks, pvs)
+    else:
+        fn, pool = (_ffi.lib.brn_kv_cache_append if rope is None else _ffi.lib.brn_kv_cache_append_rope), (ppk, ppv, _KV_TYPE[kv_dtype])
+    _ffi.check(fn(*head, *(table if rope is not None else ()), *pool, *tail))
     return out
 
 

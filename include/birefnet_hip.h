@@ -594,6 +594,65 @@ brn_status brn_kv_cache_append_fp8(const float* k_new, const float* v_new, int b
                                    const int* block_table, const int* kv_lens, int* kv_lens_out,
                                    int n_pages, int page_size, int max_pages,
                                    brn_mem loc, int device_ordinal, void* stream);
+/* Rotary position embedding: y = x with the first rot_dim elements of every head row rotated in pairs by the angles of the row's
+ * position.  It is the step a decoder applies to q and to the new k before attention; with positions = kv_lens it rotates q at the
+ * positions the new keys are about to take, on the device, so rope + brn_kv_cache_append_rope + paged attention is one captured graph.
+ * x, y: fp32, [batch, seq, heads, head_dim] (layout BRN_ATTN_BSHD) or [batch, heads, seq, head_dim] (BRN_ATTN_BHSD).
+ * The table: cos, sin are [n_pos, rot_dim / 2] fp32, contiguous, supplied by the caller, where `loc` says.  The library evaluates no sine
+ * or cosine: every frequency-scaling scheme is a different table, and the result is promised bit for bit.
+ * The rule, for a row x[0 .. head_dim) at table row p and i in 0 .. rot_dim / 2: style BRN_ROPE_HALF (NeoX / Llama) pairs a = x[i] with
+ * b = x[i + rot_dim / 2], style BRN_ROPE_INTERLEAVED (GPT-J) pairs a = x[2i] with b = x[2i + 1]; the pair is written back to its two places as
+ *   a' = fl(fl(a * cos[p][i]) - fl(b * sin[p][i])),   b' = fl(fl(b * cos[p][i]) + fl(a * sin[p][i])),
+ * all in fp32: two rounded products, then one rounded difference or sum, never a fused multiply-add.  Elements d >= rot_dim are copied
+ * with their bits (partial rotary), a NaN's payload included.
+ * positions: [batch] int32 where `loc` says, or NULL = all 0.  They are device data and are clamped, never trusted: with
+ * P_b = max(positions[b], 0), token t of batch entry b uses table row p = min(P_b + t, n_pos - 1), the sum formed without int32 overflow.
+ * A position past the table reads the last row: a wrong rotation for that token, never a read outside the table.  No address depends on
+ * a device value other than through this clamp.
+ * y may be x itself, wholly (in place): both members of a pair are in one thread's registers before either is written.
+ * With BRN_MEM_DEVICE the call allocates nothing, does not synchronise the stream and may be captured.
+ * Limits (each violation is BRN_ERR_INVALID_ARG with the prefix "rope:" and a message naming the limit, checked before the device): x, y,
+ * cos, sin not NULL; head_dim 32, 64 or 128; rot_dim a multiple of 16 with 16 <= rot_dim <= head_dim; style 0 or 1; 1 <= n_pos <= 2^24;
+ * batch >= 1, heads >= 1; 1 <= seq <= 65536; layout 0 or 1; batch * seq * heads * head_dim / 8 < 2^31; y is x or does not overlap x; cos,
+ * sin and positions do not overlap y, sizes in bytes; BRN_MEM_DEVICE x, y, cos, sin 16-byte aligned, positions 4-byte aligned.
+ * Not provided: computing the table on the device; per-token position arrays (positions are P_b + t); rotating q inside the append
+ * call; 16-bit x / y; rotation inside the attention kernels; a per-sequence seq_new. */
+typedef enum { BRN_ROPE_HALF = 0, BRN_ROPE_INTERLEAVED = 1 } brn_rope_style;
+brn_status brn_rope_forward(const float* x, int batch, int seq, int heads, int head_dim, int layout,
+                            const float* cos, const float* sin, int n_pos, int rot_dim, int style,
+                            const int* positions,
+                            float* y, brn_mem loc, int device_ordinal, void* stream);
+/* brn_kv_cache_append with the new keys rotated on their way into the pool: a key is read once, rotated in registers, rounded once and
+ * written once.  It is brn_kv_cache_append in every respect (the arguments up to layout and from k_pages on are its arguments, in its
+ * order) except that K token t of batch entry b is rotated by the rule of brn_rope_forward at P_b = L_b, the append's own clamped length:
+ * table row min(L_b + t, n_pos - 1), the position the token takes in the cache.  The rotation is finished in fp32, then cast once.  V is
+ * not rotated.  The position rule, the page clamp, dropped positions, kv_lens_out written by the later launch and the in-place form are
+ * unchanged; cos, sin, n_pos, rot_dim and style are brn_rope_forward's.
+ * The promise: for every pool type, the pool and kv_lens_out carry the bits of brn_kv_cache_append called on
+ * k' = brn_rope_forward(k_new, positions = kv_lens).
+ * Limits (BRN_ERR_INVALID_ARG, prefix "kv cache append rope:", checked before the device): every limit of brn_kv_cache_append; cos, sin
+ * not NULL; rot_dim a multiple of 16 with 16 <= rot_dim <= head_dim; style 0 or 1; 1 <= n_pos <= 2^24; cos and sin overlap neither the
+ * pool nor kv_lens_out, sizes in bytes; BRN_MEM_DEVICE cos, sin 16-byte aligned.
+ * Not provided: computing the table on the device; per-token position arrays; rotating q inside the append call (brn_rope_forward with
+ * positions = kv_lens, before the append); 16-bit k_new / v_new; rotation inside the attention kernels; a per-sequence seq_new. */
+brn_status brn_kv_cache_append_rope(const float* k_new, const float* v_new, int batch, int seq_new, int kv_heads, int head_dim, int layout,
+                                    const float* cos, const float* sin, int n_pos, int rot_dim, int style,
+                                    void* k_pages, void* v_pages, int kv_type,
+                                    const int* block_table, const int* kv_lens, int* kv_lens_out,
+                                    int n_pages, int page_size, int max_pages,
+                                    brn_mem loc, int device_ordinal, void* stream);
+/* The same insertion into brn_kv_cache_append_fp8: K is rotated as above, in fp32, in front of the fp8 store's three steps (divide by the
+ * head's scale, clamp to +-448, round to nearest even).  The pool and kv_lens_out carry the bits of brn_kv_cache_append_fp8 called on
+ * k' = brn_rope_forward(k_new, positions = kv_lens).
+ * Limits (BRN_ERR_INVALID_ARG, prefix "kv cache append rope fp8:", checked before the device): every limit of brn_kv_cache_append_fp8 and
+ * the table limits of brn_kv_cache_append_rope.
+ * Not provided: what brn_kv_cache_append_fp8 and brn_kv_cache_append_rope do not provide. */
+brn_status brn_kv_cache_append_rope_fp8(const float* k_new, const float* v_new, int batch, int seq_new, int kv_heads, int head_dim, int layout,
+                                        const float* cos, const float* sin, int n_pos, int rot_dim, int style,
+                                        void* k_pages, void* v_pages, const float* k_scale, const float* v_scale,
+                                        const int* block_table, const int* kv_lens, int* kv_lens_out,
+                                        int n_pages, int page_size, int max_pages,
+                                        brn_mem loc, int device_ordinal, void* stream);
 /* PatchMerging::forward (swin.rs:491-527): x [B,H*W,C] -> [B, ceil(H/2)*ceil(W/2), 2C]. */
 brn_status brn_patch_merging_forward(const float* x, int B, int H, int W, int C, const float* norm_g,
                                      const float* norm_b, const float* reduction_w, float* y, brn_mem loc,

@@ -172,6 +172,19 @@ extern "C" {
                                    layout: c_int, k_pages: *mut c_void, v_pages: *mut c_void, k_scale: *const c_float, v_scale: *const c_float,
                                    block_table: *const c_int, kv_lens: *const c_int, kv_lens_out: *mut c_int, n_pages: c_int, page_size: c_int,
                                    max_pages: c_int, loc: c_int, device_ordinal: c_int, stream: *mut c_void) -> c_int;
+    pub fn brn_rope_forward(x: *const c_float, batch: c_int, seq: c_int, heads: c_int, head_dim: c_int, layout: c_int, cos: *const c_float,
+                            sin: *const c_float, n_pos: c_int, rot_dim: c_int, style: c_int, positions: *const c_int, y: *mut c_float,
+                            loc: c_int, device_ordinal: c_int, stream: *mut c_void) -> c_int;
+    pub fn brn_kv_cache_append_rope(k_new: *const c_float, v_new: *const c_float, batch: c_int, seq_new: c_int, kv_heads: c_int, head_dim: c_int,
+                                    layout: c_int, cos: *const c_float, sin: *const c_float, n_pos: c_int, rot_dim: c_int, style: c_int,
+                                    k_pages: *mut c_void, v_pages: *mut c_void, kv_type: c_int, block_table: *const c_int,
+                                    kv_lens: *const c_int, kv_lens_out: *mut c_int, n_pages: c_int, page_size: c_int, max_pages: c_int,
+                                    loc: c_int, device_ordinal: c_int, stream: *mut c_void) -> c_int;
+    pub fn brn_kv_cache_append_rope_fp8(k_new: *const c_float, v_new: *const c_float, batch: c_int, seq_new: c_int, kv_heads: c_int, head_dim: c_int,
+                                        layout: c_int, cos: *const c_float, sin: *const c_float, n_pos: c_int, rot_dim: c_int, style: c_int,
+                                        k_pages: *mut c_void, v_pages: *mut c_void, k_scale: *const c_float, v_scale: *const c_float,
+                                        block_table: *const c_int, kv_lens: *const c_int, kv_lens_out: *mut c_int, n_pages: c_int, page_size: c_int,
+                                        max_pages: c_int, loc: c_int, device_ordinal: c_int, stream: *mut c_void) -> c_int;
     pub fn brn_patch_merging_forward(x: *const c_float, b: c_int, h: c_int, w: c_int, c: c_int, norm_g: *const c_float,
                                      norm_b: *const c_float, reduction_w: *const c_float, y: *mut c_float, loc: c_int,
                                      device_ordinal: c_int, stream: *mut c_void) -> c_int;

@@ -60,8 +60,12 @@ brn_flash_attention_paged_kv_forward on the bf16 / fp16 pool holding the widened
 bf16 and f32, f16 in mode f16), with brn_flash_attention_paged_forward on the fp32 pool for context, on the same rows, page 64, shuffled
 table, modes bf16, f16 and f32; then brn_kv_cache_append_fp8 beside a device-to-device copy of the bytes it writes.  Same protocol.
 Written to profiles/flash_attention_paged_fp8_bench.json.
+--rope times, per pool type (bf16, f16, f32, fp8) at the append's two shapes, four sides alternating with the same protocol:
+brn_kv_cache_append_rope (HALF, rot_dim = head_dim), brn_kv_cache_append alone, the two-call form (brn_rope_forward on k_new into a
+buffer at positions = kv_lens, then brn_kv_cache_append of it) and a device-to-device copy of the bytes written.  Written to
+profiles/flash_attention_rope_bench.json.
 
-  python tools/bench_flash_attention.py [--bias | --gqa | --varlen | --splitkv | --paged | --paged-kv16 | --paged-fp8] [--row N] [--mode f32|bf16|f16] [--json PATH]"""
+  python tools/bench_flash_attention.py [--bias | --gqa | --varlen | --splitkv | --paged | --paged-kv16 | --paged-fp8 | --rope] [--row N] [--mode f32|bf16|f16] [--json PATH]"""
 import argparse
 import json
 import os
@@ -97,6 +101,7 @@ KV_APPEND_ROWS = [(64, 1, 8, 128, 64, 64), (16, 512, 8, 128, 64, 64)]
 KV_APPEND_TYPES = ["bf16", "f16", "f32"]
 PAGED_KV16_JSON = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "flash_attention_paged_kv16_bench.json")
 PAGED_FP8_JSON = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "flash_attention_paged_fp8_bench.json")
+ROPE_JSON = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "flash_attention_rope_bench.json")
 PAGED_JSON = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "flash_attention_paged_bench.json")
 HBM_BYTES_PER_S = 8.0e12
 MODES = ["f32", "bf16", "f16"]
@@ -683,6 +688,76 @@ def bench_kv_append(row, kv):
     return [rec]
 
 
+def bench_rope(row, kv):
+    """brn_kv_cache_append_rope (kv "fp8": _rope_fp8) beside the plain append, the two-call form rope(k_new) -> append and a
+    device-to-device copy of the bytes written; all sides rewind the lengths first"""
+    import torch
+    import candle_birefnet_amd as cb
+    from candle_birefnet_amd import ops
+    lib = cb._ffi.lib
+    batch, seq_new, kv_heads, hd, page, pages_per_seq = row
+    tdt = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16, "fp8": torch.uint8}[kv]
+    g = torch.Generator(device="cuda").manual_seed(2)
+    k_new, v_new = (torch.randn(batch, seq_new, kv_heads, hd, device="cuda", generator=g) for _ in range(2))
+    k_rot = torch.empty_like(k_new)
+    n_pages = batch * pages_per_seq
+    kp, vp = (torch.zeros(n_pages, page, kv_heads, hd, device="cuda", dtype=tdt) for _ in range(2))
+    table = torch.randperm(n_pages, device="cuda", generator=g).to(torch.int32).view(batch, pages_per_seq).contiguous()
+    start = torch.full((batch,), page * pages_per_seq // 2 - 1, dtype=torch.int32, device="cuda")
+    lens = start.clone()
+    n_pos = page * pages_per_seq
+    cos, sin = (torch.from_numpy(a).cuda() for a in ops.rope_table(n_pos, hd))
+    stream = torch.cuda.current_stream().cuda_stream
+    src, dst = (torch.empty(2 * batch * seq_new * kv_heads * hd, device="cuda", dtype=tdt) for _ in range(2))
+    scales = [torch.full((kv_heads,), 0.0173, device="cuda") for _ in range(2)]
+    head = (batch, seq_new, kv_heads, hd, 0)
+    rope_args = (cos.data_ptr(), sin.data_ptr(), n_pos, hd, 0)
+    pool = (kp.data_ptr(), vp.data_ptr()) + ((scales[0].data_ptr(), scales[1].data_ptr()) if kv == "fp8" else ({"f32": 0, "bf16": 1, "f16": 2}[kv],))
+    tail = (table.data_ptr(), lens.data_ptr(), lens.data_ptr(), n_pages, page, pages_per_seq, 1, 0, stream)
+    plain_fn, rope_fn = (lib.brn_kv_cache_append_fp8, lib.brn_kv_cache_append_rope_fp8) if kv == "fp8" else (lib.brn_kv_cache_append, lib.brn_kv_cache_append_rope)
+
+    def fused():
+        lens.copy_(start)
+        cb._ffi.check(rope_fn(k_new.data_ptr(), v_new.data_ptr(), *head, *rope_args, *pool, *tail))
+        return kp
+
+    def plain():
+        lens.copy_(start)
+        cb._ffi.check(plain_fn(k_new.data_ptr(), v_new.data_ptr(), *head, *pool, *tail))
+        return kp
+
+    def two_calls():
+        lens.copy_(start)
+        cb._ffi.check(lib.brn_rope_forward(k_new.data_ptr(), *head, *rope_args, lens.data_ptr(), k_rot.data_ptr(), 1, 0, stream))
+        cb._ffi.check(plain_fn(k_rot.data_ptr(), v_new.data_ptr(), *head, *pool, *tail))
+        return kp
+
+    def copy():
+        lens.copy_(start)
+        dst.copy_(src)
+        return dst
+
+    two_calls()
+    want = kp.clone()
+    kp.zero_()
+    fused()
+    torch.cuda.synchronize()
+    bits_equal = bool(torch.equal(kp.view(torch.uint8), want.view(torch.uint8)))
+    tf, tp, t2, tc = _time_alternating([fused, plain, two_calls, copy])
+    written = src.numel() * src.element_size()
+    read = 2 * 4 * batch * seq_new * kv_heads * hd
+    rec = {"batch": batch, "seq_new": seq_new, "kv_heads": kv_heads, "head_dim": hd, "page_size": page, "kv_type": kv, "style": "half", "rot_dim": hd, "bytes_written": written,
+           "bytes_read": read, "fused_bits_equal_two_calls": bits_equal, "fused_over_plain": round(tf[0] / tp[0], 3), "two_calls_over_plain": round(t2[0] / tp[0], 3),
+           "fused_over_copy": round(tf[0] / tc[0], 3), "fused_bytes_per_s": round((read + written) / (tf[0] * 1e-3), 0), "plain_bytes_per_s": round((read + written) / (tp[0] * 1e-3), 0),
+           "two_calls_bytes_per_s": round((read + written + read) / (t2[0] * 1e-3), 0), "copy_bytes_per_s": round(2 * written / (tc[0] * 1e-3), 0),
+           "note": "every side includes one copy of the lengths (batch ints); bytes per second count reads + writes (the two-call form moves k_new three times)"}
+    for name, t in (("append_rope", tf), ("append", tp), ("rope_then_append", t2), ("copy", tc)):
+        rec.update(_side(name, t))
+    print(f"rope {batch:3d} x {seq_new:3d} x {kv_heads} x {hd} -> {kv:4s}: fused {tf[0]:.4f} ms [{tf[2]:.4f} .. {tf[3]:.4f}] | append {tp[0]:.4f} [{tp[2]:.4f} .. {tp[3]:.4f}] | "
+          f"rope + append {t2[0]:.4f} [{t2[2]:.4f} .. {t2[3]:.4f}] | copy {tc[0]:.4f} [{tc[2]:.4f} .. {tc[3]:.4f}] | bits equal {bits_equal}", flush=True)
+    return [rec]
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--bias", action="store_true", help="time brn_flash_attention_bias_forward beside the bias-free call and torch + bias")
@@ -692,6 +767,7 @@ if __name__ == "__main__":
     ap.add_argument("--paged", action="store_true", help="time brn_flash_attention_paged_forward (pages of 16 / 64 / 256, identity and shuffled tables) beside the split entry")
     ap.add_argument("--paged-kv16", action="store_true", help="time brn_flash_attention_paged_kv_forward on 16-bit pools beside the fp32-pool entry, and brn_kv_cache_append beside a copy")
     ap.add_argument("--paged-fp8", action="store_true", help="time brn_flash_attention_paged_fp8_forward on an e4m3 pool beside the 16-bit-pool and fp32-pool entries, and brn_kv_cache_append_fp8 beside a copy")
+    ap.add_argument("--rope", action="store_true", help="time brn_kv_cache_append_rope beside the plain append, rope + append in two calls, and a copy")
     ap.add_argument("--row", type=int, choices=range(len(BIAS_ROWS)))
     ap.add_argument("--mode", choices=MODES)
     ap.add_argument("--json", help="write the records to this file")
@@ -700,8 +776,16 @@ if __name__ == "__main__":
     if cb.device_count() < 1:
         sys.exit("no HIP device: nothing is measured")
     recs = []
-    if a.bias + a.gqa + a.varlen + a.splitkv + a.paged + a.paged_kv16 + a.paged_fp8 > 1:
-        sys.exit("--bias, --gqa, --varlen, --splitkv, --paged, --paged-kv16 and --paged-fp8 are separate tables: one at a time")
+    if a.bias + a.gqa + a.varlen + a.splitkv + a.paged + a.paged_kv16 + a.paged_fp8 + a.rope > 1:
+        sys.exit("--bias, --gqa, --varlen, --splitkv, --paged, --paged-kv16, --paged-fp8 and --rope are separate tables: one at a time")
+    if a.rope:
+        for row in (KV_APPEND_ROWS if a.row is None else [KV_APPEND_ROWS[a.row]] if a.row < len(KV_APPEND_ROWS) else sys.exit(f"--row {a.row}: only {len(KV_APPEND_ROWS)} rows in this table")):
+            for kv in KV_APPEND_TYPES + ["fp8"]:
+                recs += bench_rope(row, kv)
+        with open(a.json or ROPE_JSON, "w") as f:
+            json.dump({"tool": "tools/bench_flash_attention.py --rope", "warmup": GQA_WARMUP, "timed": GQA_ROUNDS * GQA_TIMED, "rows": recs}, f, indent=1)
+            f.write("\n")
+        sys.exit(0)
     if a.paged_fp8:
         for row in (PAGED_ROWS if a.row is None else [PAGED_ROWS[a.row]] if a.row < len(PAGED_ROWS) else sys.exit(f"--row {a.row}: only {len(PAGED_ROWS)} rows in this table")):
             for mode in (["bf16", "f16", "f32"] if a.mode is None else [a.mode]):
