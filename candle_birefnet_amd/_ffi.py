@@ -17,6 +17,7 @@ BRN_ACT_NONE, BRN_ACT_RELU, BRN_ACT_GELU_ERF = 0, 1, 2
 BRN_ATTN_BSHD, BRN_ATTN_BHSD = 0, 1
 BRN_KV_F32, BRN_KV_BF16, BRN_KV_F16 = 0, 1, 2
 BRN_ROPE_HALF, BRN_ROPE_INTERLEAVED = 0, 1
+BRN_POOL_F32, BRN_POOL_BF16, BRN_POOL_F16, BRN_POOL_E4M3 = 0, 1, 2, 3
 
 BRN_ERR_INVALID_ARG, BRN_ERR_MISSING_TENSOR, BRN_ERR_SHAPE, BRN_ERR_NO_DEVICE, BRN_ERR_HIP, BRN_ERR_OOM = 1, 2, 3, 4, 5, 6
 ERR_NAMES = {1: "INVALID_ARG", 2: "MISSING_TENSOR", 3: "SHAPE", 4: "NO_DEVICE", 5: "HIP", 6: "OOM"}
@@ -128,6 +129,12 @@ _sig("brn_kv_cache_append_rope", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C
      C.c_int, C.c_int, C.c_int, _vp)
 _sig("brn_kv_cache_append_rope_fp8", C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int,
      C.c_int, C.c_int, C.c_int, C.c_int, _vp)
+_sig("brn_flash_attention_paged_varlen_plan", C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+     C.POINTER(C.c_size_t), C.POINTER(C.c_size_t))
+_sig("brn_flash_attention_paged_varlen_forward", C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+     C.c_int, C.c_int, C.c_float, C.c_int, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_int, C.c_int, _vp)
+_sig("brn_kv_cache_append_varlen", C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp,
+     C.c_size_t, C.c_int, C.c_int, _vp)
 _sig("brn_patch_merging_forward", C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp)
 _sig("brn_deform_conv2d_forward", C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int,
      C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp)
@@ -153,7 +160,7 @@ DECLARED = [
     "brn_forward", "brn_model_backbone_forward", "brn_model_squeeze_forward", "brn_model_decoder_forward",
     "brn_model_set_streams", "brn_model_set_profiling", "brn_model_last_timings", "brn_model_last_kernel_stats", "brn_kernel_family_name",
     "brn_swin_create", "brn_swin_destroy", "brn_swin_forward", "brn_linear_forward", "brn_linear_residual_layer_norm_forward", "brn_layer_norm_forward",
-    "brn_conv2d_forward", "brn_upsample_bilinear2d", "brn_window_attention_forward", "brn_attention_forward", "brn_flash_attention_forward", "brn_flash_attention_bias_forward", "brn_flash_attention_gqa_forward", "brn_flash_attention_varlen_forward", "brn_flash_attention_splitkv_plan", "brn_flash_attention_splitkv_forward", "brn_flash_attention_paged_forward", "brn_flash_attention_paged_kv_forward", "brn_kv_cache_append", "brn_flash_attention_paged_fp8_forward", "brn_kv_cache_append_fp8", "brn_rope_forward", "brn_kv_cache_append_rope", "brn_kv_cache_append_rope_fp8", "brn_patch_merging_forward",
+    "brn_conv2d_forward", "brn_upsample_bilinear2d", "brn_window_attention_forward", "brn_attention_forward", "brn_flash_attention_forward", "brn_flash_attention_bias_forward", "brn_flash_attention_gqa_forward", "brn_flash_attention_varlen_forward", "brn_flash_attention_splitkv_plan", "brn_flash_attention_splitkv_forward", "brn_flash_attention_paged_forward", "brn_flash_attention_paged_kv_forward", "brn_kv_cache_append", "brn_flash_attention_paged_fp8_forward", "brn_kv_cache_append_fp8", "brn_rope_forward", "brn_kv_cache_append_rope", "brn_kv_cache_append_rope_fp8", "brn_flash_attention_paged_varlen_plan", "brn_flash_attention_paged_varlen_forward", "brn_kv_cache_append_varlen", "brn_patch_merging_forward",
     "brn_deform_conv2d_forward", "brn_deform_conv2d_offsets_forward", "brn_aspp_deformable_forward", "brn_decblk_forward", "brn_set_op_compute", "brn_preprocess_image", "brn_postprocess_mask", "brn_infer_images_u8",
 ]
 

@@ -236,6 +236,15 @@ struct FlashAttentionParams {
     // fp32 on the device, or null = all ones; device data like the table: read by the kernels alone, no address depends on them.  K / V
     // head g's workgroups run with scale * k_scale[g] in the place of scale, and a row's final y is multiplied by v_scale[g] once
     const float* k_scale; const float* v_scale;
+    // brn_flash_attention_paged_varlen_forward; pv_plan == null = the kernels above, untouched.  With a plan: the paged form (any kv_type)
+    // over a packed batch of new tokens.  batch = 1 and seq_q = pv_total_q describe q, y [total_q, heads, head_dim], lse [heads, total_q]
+    // and the partials (row r = h * total_q + token); block_table is [pv_n_seqs][max_pages], kv_lens [pv_n_seqs].  pv_cu is UNVALIDATED
+    // device data, read by the plan kernel alone, which writes pv_plan (brn_flash_paged_varlen_plan.h) ahead of the main launch; each
+    // workgroup takes its sequence, seq_q = n_b, seq_kv = len_b, causal_off and its bases from the plan (fa_params).  pv_row0 is the
+    // kernels' own: the workgroup's s_b
+    const int* pv_cu;             // [pv_n_seqs + 1]
+    int* pv_plan;                 // fa_pv_plan_ints(pv_n_seqs) ints
+    int pv_n_seqs, pv_total_q, pv_row0;
 };
 constexpr int FA_KV_FP8 = 3;      // FlashAttentionParams::kv_type / KvAppendParams::kv_type of an e4m3fn pool (not a brn_kv_type: the public enum keeps its three values)
 hipError_t launch_flash_attention(const FlashAttentionParams& p, hipStream_t s);
@@ -262,8 +271,17 @@ struct KvAppendParams {
     // by the rule of RopeParams at table row min(L_b + t, rope_n_pos - 1), in fp32, before the cast; V is not.  Null: the plain append
     const float* rope_cos; const float* rope_sin;   // [rope_n_pos][rope_dim / 2] fp32, 16-byte aligned
     int rope_n_pos, rope_dim, rope_style;
+    // brn_kv_cache_append_varlen: pv_cu non-null selects the packed form (no rope).  k_new, v_new are [pv_total_q, kv_heads, head_dim]
+    // (new_ss / new_sh; new_sb and seq_new are not read), batch = pv_n_seqs.  The plan kernel turns pv_cu (UNVALIDATED device data) into
+    // the starts s_b in pv_plan first; token s_b + t of sequence b becomes key L_b + t, kv_lens_out[b] = min(L_b + n_b, cap)
+    const int* pv_cu;             // [pv_n_seqs + 1]
+    int* pv_plan;                 // fa_pv_plan_ints(pv_n_seqs) ints
+    int pv_n_seqs, pv_total_q;
 };
 hipError_t launch_kv_cache_append(const KvAppendParams& p, hipStream_t s);
+// the device-side plan of the two packed paged entries (kernels/kv_cache.hip; the rule: brn_flash_paged_varlen_plan.h): one workgroup
+// turns cu [n_seqs + 1] into plan's starts and tile prefix for groups of G query heads
+hipError_t launch_paged_varlen_plan(const int* cu, int n_seqs, int total_q, int G, int* plan, hipStream_t s);
 
 // brn_rope_forward (kernels/kv_cache.hip): y = x with the first rot_dim elements of every head row rotated in pairs by the caller's
 // table.  Row p = min(max(positions[b], 0) + t, n_pos - 1) for token t of batch entry b (positions null = 0); pair i of rot_dim / 2 is

@@ -2,6 +2,7 @@
 // weights per call, in the arithmetic brn_set_op_compute selected on the calling thread.  Weights are always host pointers; x / y /
 // residual follow `loc`.
 #include "brn_api_util.h"
+#include "brn_flash_paged_varlen_plan.h"
 #include "brn_flash_split_plan.h"
 #include "brn_flash_varlen_plan.h"
 #include "brn_graph.h"
@@ -816,6 +817,230 @@ brn_status brn_rope_forward(const float* x, int batch, int seq, int heads, int h
         else { p.ss = d; p.sh = seq * d; p.sb = heads * p.sh; }
         p.n_pos = n_pos; p.rot_dim = rot_dim; p.style = style;
         BRN_HIP(launch_rope(p, (hipStream_t)stream));
+        st.finish();
+    });
+}
+
+// The packed batch over the paged pool: a mixed prefill / decode step in one call.  cu_seqlens_q is device data like the table and the
+// lengths: never read on the host for BRN_MEM_DEVICE, made harmless by the rule of brn_flash_paged_varlen_plan.h, which a one-workgroup
+// kernel evaluates into plan_workspace ahead of the main launch.  The host sizes the grid with T_max, the split with max_kv_len.  The calls
+// allocate nothing and do not synchronise.  BRN_MEM_HOST (a test convenience) stages every output up as well as down, so that the rows
+// no kernel writes (padding) come back as they went.
+static const char* const PAGED_VARLEN = "flash attention paged varlen";
+static const char* const APPEND_VARLEN = "kv cache append varlen";
+static const char* const POOL_TYPE_NAME[4] = {"f32", "bf16", "f16", "e4m3"};
+static void pool_type_check(const char* who, int pool_type, const float* k_scale, const float* v_scale) {
+    if (pool_type < BRN_POOL_F32 || pool_type > BRN_POOL_E4M3)
+        fail(BRN_ERR_INVALID_ARG, "%s: pool_type %d unknown (pool_type must be 0 = f32, 1 = bf16, 2 = f16 or 3 = e4m3)", who, pool_type);
+    if (pool_type != BRN_POOL_E4M3 && (k_scale || v_scale))
+        fail(BRN_ERR_INVALID_ARG, "%s: k_scale and v_scale must be NULL unless pool_type is 3 = e4m3 (pool_type %d = %s)", who, pool_type, POOL_TYPE_NAME[pool_type]);
+}
+// the sizes of a pack: 1 <= n_seqs <= 65536, total_q >= 1, G * total_q < 2^31 (G = 1 for the append)
+static void pack_check(const char* who, int total_q, int n_seqs, int G) {
+    if (n_seqs < 1 || n_seqs > FA_PV_MAX_SEQS) fail(BRN_ERR_INVALID_ARG, "%s: n_seqs %d unsupported (1 <= n_seqs <= 65536)", who, n_seqs);
+    if (total_q < 1) fail(BRN_ERR_INVALID_ARG, "%s: total_q %d unsupported (total_q >= 1)", who, total_q);
+    if ((long long)G * total_q > 0x7fffffffLL)
+        fail(BRN_ERR_INVALID_ARG, "%s: total_q %d too large with G = heads / kv_heads = %d (G * total_q < 2^31)", who, total_q, G);
+}
+static void plan_workspace_check(const char* who, const int* plan_workspace, size_t plan_ints, int n_seqs) {
+    const size_t need = fa_pv_plan_ints(n_seqs);
+    if (!plan_workspace || plan_ints < need)
+        fail(BRN_ERR_INVALID_ARG, "%s: plan_workspace %s (it must hold 2 * (n_seqs + 1) = %zu ints, plan_ints %zu)", who, plan_workspace ? "too small" : "is NULL", need, plan_ints);
+    if (reinterpret_cast<uintptr_t>(plan_workspace) & 3) fail(BRN_ERR_INVALID_ARG, "%s: plan_workspace must be 4-byte aligned", who);
+}
+struct PvPlan { int S, tps; long long t_max; size_t workspace_floats, plan_ints; };
+// every check the plan entry can make, and the split: nkt and the normalisation are flash_split_plan's, the base grid is T_max * kv_heads
+static PvPlan paged_varlen_plan_checked(const char* who, int total_q, int n_seqs, int max_kv_len, int heads, int kv_heads, int head_dim, int kv_splits) {
+    if (!(head_dim == 32 || head_dim == 64 || head_dim == 128))
+        fail(BRN_ERR_INVALID_ARG, "%s: head_dim %d unsupported (head_dim must be 32, 64 or 128)", who, head_dim);
+    if (heads < 1) fail(BRN_ERR_INVALID_ARG, "%s: heads %d unsupported (heads >= 1)", who, heads);
+    if (kv_heads < 1 || kv_heads > heads || heads % kv_heads)
+        fail(BRN_ERR_INVALID_ARG, "%s: kv_heads %d unsupported with heads %d (1 <= kv_heads <= heads, heads %% kv_heads == 0)", who, kv_heads, heads);
+    const int G = heads / kv_heads;
+    pack_check(who, total_q, n_seqs, G);
+    if (max_kv_len < 1 || max_kv_len > 65536) fail(BRN_ERR_INVALID_ARG, "%s: max_kv_len %d unsupported (1 <= max_kv_len <= 65536)", who, max_kv_len);
+    splitkv_check_splits(who, kv_splits);
+    PvPlan pl;
+    pl.t_max = fa_pv_max_tiles(G, total_q, n_seqs);
+    const int nkt = (max_kv_len + FA_SPLIT_TILE - 1) / FA_SPLIT_TILE;
+    const int ask = kv_splits ? kv_splits : flash_split_auto((long long)kv_heads * pl.t_max, nkt);
+    pl.tps = (nkt + ask - 1) / ask;
+    pl.S = (nkt + pl.tps - 1) / pl.tps;
+    if (pl.t_max * kv_heads * pl.S > 0x7fffffffLL)
+        fail(BRN_ERR_INVALID_ARG, "%s: %lld row tiles x kv_heads %d x %d splits too large (T_max * kv_heads * S < 2^31, T_max = (G * total_q + 63 * min(n_seqs, total_q)) / 64)",
+             who, pl.t_max, kv_heads, pl.S);
+    pl.workspace_floats = (size_t)pl.S * heads * total_q * ((size_t)head_dim + 1);
+    pl.plan_ints = fa_pv_plan_ints(n_seqs);
+    return pl;
+}
+
+brn_status brn_flash_attention_paged_varlen_plan(int total_q, int n_seqs, int max_kv_len, int heads, int kv_heads, int head_dim, int kv_splits,
+                                                 int* splits_out, int* tiles_per_split_out, size_t* workspace_floats_out, size_t* plan_ints_out) {
+    return guarded([&] {
+        const PvPlan pl = paged_varlen_plan_checked(PAGED_VARLEN, total_q, n_seqs, max_kv_len, heads, kv_heads, head_dim, kv_splits);
+        if (splits_out) *splits_out = pl.S;
+        if (tiles_per_split_out) *tiles_per_split_out = pl.tps;
+        if (workspace_floats_out) *workspace_floats_out = pl.workspace_floats;
+        if (plan_ints_out) *plan_ints_out = pl.plan_ints;
+    });
+}
+
+// BRN_MEM_HOST: an output that is only partly written goes up before it comes down
+static float* stage_inout(Staging& st, float* p, size_t n, void* stream) {
+    if (st.loc == BRN_MEM_DEVICE) return p;
+    float* d = st.out(p, n);
+    BRN_HIP(hipMemcpyAsync(d, p, n * sizeof(float), hipMemcpyHostToDevice, (hipStream_t)stream));
+    return d;
+}
+
+brn_status brn_flash_attention_paged_varlen_forward(const float* q, const void* k_pages, const void* v_pages, int pool_type, const float* k_scale,
+                                                    const float* v_scale, const int* block_table, const int* kv_lens, const int* cu_seqlens_q, int total_q,
+                                                    int n_seqs, int max_kv_len, int heads, int kv_heads, int head_dim, int n_pages, int page_size, int max_pages,
+                                                    int causal, float scale, int kv_splits, float* y, float* lse, float* workspace, size_t workspace_floats,
+                                                    int* plan_workspace, size_t plan_ints, brn_mem loc, int device, void* stream) {
+    return guarded([&] {
+        const char* who = PAGED_VARLEN;
+        if (!q || !k_pages || !v_pages || !y) fail(BRN_ERR_INVALID_ARG, "%s: null q, k_pages, v_pages or y", who);
+        if (!block_table || !kv_lens || !cu_seqlens_q) fail(BRN_ERR_INVALID_ARG, "%s: null block_table, kv_lens or cu_seqlens_q", who);
+        pool_type_check(who, pool_type, k_scale, v_scale);
+        const int s16 = attention_op_s16();
+        if ((pool_type == BRN_POOL_BF16 || pool_type == BRN_POOL_F16) && s16 && s16 != pool_type)
+            fail(BRN_ERR_INVALID_ARG, "%s: pool_type %s cannot be read in compute mode %s (a 16-bit compute mode reads a pool of its own type or an e4m3 pool; the fp32-class modes read every pool)",
+                 who, POOL_TYPE_NAME[pool_type], KV_TYPE_NAME[s16]);
+        const int page_log2 = paged_pool_check(who, n_pages, page_size, max_pages);
+        const PvPlan pl = paged_varlen_plan_checked(who, total_q, n_seqs, max_kv_len, heads, kv_heads, head_dim, kv_splits);
+        if (max_kv_len > (long long)max_pages * page_size)
+            fail(BRN_ERR_INVALID_ARG, "%s: max_kv_len %d unsupported with max_pages %d of page_size %d (1 <= max_kv_len <= min(65536, max_pages * page_size))",
+                 who, max_kv_len, max_pages, page_size);
+        if (causal != 0 && causal != 1) fail(BRN_ERR_INVALID_ARG, "%s: causal %d (causal must be 0 or 1)", who, causal);
+        if (!scale_arg_ok(scale)) fail(BRN_ERR_INVALID_ARG, "%s: scale must be finite and >= 0 (0 = head_dim^-0.5)", who);
+        const size_t nq = (size_t)total_q * heads * head_dim, npool = (size_t)n_pages * page_size * kv_heads * head_dim;
+        const size_t pool_floats = npool * kv_type_bytes(pool_type) / 4;
+        const size_t R = (size_t)heads * total_q, ntab = (size_t)n_seqs * max_pages;
+        const size_t need = pl.S > 1 ? pl.workspace_floats : 0;
+        if (need && (!workspace || workspace_floats < need))
+            fail(BRN_ERR_INVALID_ARG, "%s: workspace %s for %d splits (it must hold S * heads * total_q * (head_dim + 1) = %zu floats, workspace_floats %zu)",
+                 who, workspace ? "too small" : "is NULL", pl.S, need, workspace_floats);
+        plan_workspace_check(who, plan_workspace, plan_ints, n_seqs);
+        float* const ws = need ? workspace : nullptr;
+        const struct { const void* p; size_t n; } ins[] = {{q, nq * 4}, {k_pages, pool_floats * 4}, {v_pages, pool_floats * 4}, {block_table, ntab * 4}, {kv_lens, (size_t)n_seqs * 4},
+                                                           {cu_seqlens_q, ((size_t)n_seqs + 1) * 4}, {k_scale, (size_t)kv_heads * 4}, {v_scale, (size_t)kv_heads * 4}};
+        const struct { const void* p; size_t n; const char* name; } outs[] = {{y, nq * 4, "y"}, {lse, lse ? R * 4 : 0, "lse"}, {ws, need * 4, "workspace"},
+                                                                             {plan_workspace, pl.plan_ints * 4, "plan_workspace"}};
+        for (int a = 0; a < 4; ++a) {
+            if (!outs[a].p) continue;
+            for (const auto& in : ins)
+                if (bytes_overlap(in.p, in.n, outs[a].p, outs[a].n)) fail(BRN_ERR_INVALID_ARG, "%s: %s must not overlap an input", who, outs[a].name);
+            for (int b = 0; b < a; ++b)
+                if (outs[b].p && bytes_overlap(outs[b].p, outs[b].n, outs[a].p, outs[a].n))
+                    fail(BRN_ERR_INVALID_ARG, "%s: %s and %s must not overlap", who, outs[b].name, outs[a].name);
+        }
+        if (loc == BRN_MEM_DEVICE && !all_aligned16({q, static_cast<const float*>(k_pages), static_cast<const float*>(v_pages), y, lse, ws}))
+            fail(BRN_ERR_INVALID_ARG, "%s: device q, k_pages, v_pages, y, lse and workspace must be 16-byte aligned", who);
+        if ((reinterpret_cast<uintptr_t>(block_table) | reinterpret_cast<uintptr_t>(kv_lens) | reinterpret_cast<uintptr_t>(cu_seqlens_q)) & 3)
+            fail(BRN_ERR_INVALID_ARG, "%s: block_table, kv_lens and cu_seqlens_q must be 4-byte aligned", who);
+        if (loc == BRN_MEM_DEVICE && ((reinterpret_cast<uintptr_t>(k_scale) | reinterpret_cast<uintptr_t>(v_scale)) & 3))
+            fail(BRN_ERR_INVALID_ARG, "%s: device k_scale and v_scale must be 4-byte aligned", who);
+        ensure_device(device);
+        Staging st(stream, loc);
+        FlashAttentionParams p{};
+        if (k_scale) p.k_scale = st.in(k_scale, (size_t)kv_heads);
+        if (v_scale) p.v_scale = st.in(v_scale, (size_t)kv_heads);
+        p.q = st.in(q, nq); p.k = st.in(static_cast<const float*>(k_pages), pool_floats); p.v = st.in(static_cast<const float*>(v_pages), pool_floats);
+        p.block_table = reinterpret_cast<const int*>(st.in(reinterpret_cast<const float*>(block_table), ntab));
+        p.kv_lens = reinterpret_cast<const int*>(st.in(reinterpret_cast<const float*>(kv_lens), (size_t)n_seqs));
+        p.pv_cu = reinterpret_cast<const int*>(st.in(reinterpret_cast<const float*>(cu_seqlens_q), (size_t)n_seqs + 1));
+        p.pv_plan = loc == BRN_MEM_DEVICE ? plan_workspace : reinterpret_cast<int*>(st.dalloc(pl.plan_ints));
+        p.pv_n_seqs = n_seqs; p.pv_total_q = total_q;
+        p.y = stage_inout(st, y, nq, stream);
+        // the layout of the split entry at batch 1, seq_q = total_q; each workgroup's own seq_q, seq_kv and causal_off come from the plan
+        p.batch = 1; p.heads = heads; p.kv_heads = kv_heads; p.seq_q = total_q; p.seq_kv = max_kv_len; p.head_dim = head_dim;
+        const long d = head_dim;
+        p.q_ss = heads * d; p.q_sh = d; p.q_sb = total_q * p.q_ss;
+        p.kv_ss = kv_heads * d; p.kv_sh = d; p.kv_sb = 0;
+        p.page_stride = (long)page_size * p.kv_ss; p.page_log2 = page_log2; p.n_pages = n_pages; p.max_pages = max_pages;
+        p.kv_type = pool_type;
+        p.causal = causal; p.causal_off = 0;
+        p.scale = scale_or_default(scale, head_dim);
+        p.s16 = s16;
+        p.kv_splits = pl.S; p.tiles_per_split = pl.tps;
+        if (lse) p.lse = stage_inout(st, lse, R, stream);
+        if (need) {
+            p.o_part = stage_inout(st, ws, need, stream);
+            p.lse2_part = p.o_part + (size_t)pl.S * R * head_dim;
+        }
+        BRN_HIP(launch_flash_attention(p, (hipStream_t)stream));
+        st.finish();
+    });
+}
+
+brn_status brn_kv_cache_append_varlen(const float* k_new, const float* v_new, const int* cu_seqlens_q, int total_q, int n_seqs, int kv_heads, int head_dim,
+                                      void* k_pages, void* v_pages, int pool_type, const float* k_scale, const float* v_scale, const int* block_table,
+                                      const int* kv_lens, int* kv_lens_out, int n_pages, int page_size, int max_pages, int* plan_workspace, size_t plan_ints,
+                                      brn_mem loc, int device, void* stream) {
+    return guarded([&] {
+        const char* who = APPEND_VARLEN;
+        if (!k_new || !v_new || !k_pages || !v_pages) fail(BRN_ERR_INVALID_ARG, "%s: null k_new, v_new, k_pages or v_pages", who);
+        if (!block_table || !kv_lens || !cu_seqlens_q) fail(BRN_ERR_INVALID_ARG, "%s: null block_table, kv_lens or cu_seqlens_q", who);
+        pool_type_check(who, pool_type, k_scale, v_scale);
+        if (!(head_dim == 32 || head_dim == 64 || head_dim == 128))
+            fail(BRN_ERR_INVALID_ARG, "%s: head_dim %d unsupported (head_dim must be 32, 64 or 128)", who, head_dim);
+        if (kv_heads < 1) fail(BRN_ERR_INVALID_ARG, "%s: kv_heads %d unsupported (kv_heads >= 1)", who, kv_heads);
+        pack_check(who, total_q, n_seqs, 1);
+        const int page_log2 = paged_pool_check(who, n_pages, page_size, max_pages);
+        if ((long long)max_pages * page_size > 0x7fffffffLL)
+            fail(BRN_ERR_INVALID_ARG, "%s: max_pages %d of page_size %d too large (max_pages * page_size < 2^31)", who, max_pages, page_size);
+        // the grid: a thread per 8 elements of a new row of K and of V
+        if (((long long)total_q * kv_heads * (head_dim / 8) + 255) / 256 > 0x7fffffffLL)
+            fail(BRN_ERR_INVALID_ARG, "%s: total_q %d, kv_heads %d too large (total_q * kv_heads * head_dim / 8 / 256 < 2^31)", who, total_q, kv_heads);
+        plan_workspace_check(who, plan_workspace, plan_ints, n_seqs);
+        const size_t nnew = (size_t)total_q * kv_heads * head_dim, npool = (size_t)n_pages * page_size * kv_heads * head_dim;
+        const size_t pool_floats = npool * kv_type_bytes(pool_type) / 4, ntab = (size_t)n_seqs * max_pages, nplan = fa_pv_plan_ints(n_seqs);
+        const struct { const void* p; size_t n; const char* name; } ins[] = {{k_new, nnew * 4, "k_new"}, {v_new, nnew * 4, "v_new"}, {block_table, ntab * 4, "block_table"},
+                                                                             {kv_lens, (size_t)n_seqs * 4, "kv_lens"}, {cu_seqlens_q, ((size_t)n_seqs + 1) * 4, "cu_seqlens_q"},
+                                                                             {k_scale, (size_t)kv_heads * 4, "k_scale"}, {v_scale, (size_t)kv_heads * 4, "v_scale"}};
+        for (const auto& in : ins) {
+            if (bytes_overlap(in.p, in.n, k_pages, pool_floats * 4) || bytes_overlap(in.p, in.n, v_pages, pool_floats * 4))
+                fail(BRN_ERR_INVALID_ARG, "%s: %s must not overlap the pool", who, in.name);
+            if (bytes_overlap(in.p, in.n, plan_workspace, nplan * 4)) fail(BRN_ERR_INVALID_ARG, "%s: plan_workspace must not overlap %s", who, in.name);
+        }
+        if (bytes_overlap(k_pages, pool_floats * 4, v_pages, pool_floats * 4)) fail(BRN_ERR_INVALID_ARG, "%s: k_pages and v_pages must not overlap", who);
+        if (bytes_overlap(k_pages, pool_floats * 4, plan_workspace, nplan * 4) || bytes_overlap(v_pages, pool_floats * 4, plan_workspace, nplan * 4))
+            fail(BRN_ERR_INVALID_ARG, "%s: plan_workspace must not overlap the pool", who);
+        if (kv_lens_out && kv_lens_out != kv_lens) {
+            for (const auto& in : ins)
+                if (bytes_overlap(in.p, in.n, kv_lens_out, (size_t)n_seqs * 4)) fail(BRN_ERR_INVALID_ARG, "%s: kv_lens_out must not overlap %s (kv_lens itself, the in-place form, excepted)", who, in.name);
+            if (bytes_overlap(k_pages, pool_floats * 4, kv_lens_out, (size_t)n_seqs * 4) || bytes_overlap(v_pages, pool_floats * 4, kv_lens_out, (size_t)n_seqs * 4))
+                fail(BRN_ERR_INVALID_ARG, "%s: kv_lens_out must not overlap the pool", who);
+        }
+        if (kv_lens_out && bytes_overlap(kv_lens_out, (size_t)n_seqs * 4, plan_workspace, nplan * 4)) fail(BRN_ERR_INVALID_ARG, "%s: plan_workspace must not overlap kv_lens_out", who);
+        if (loc == BRN_MEM_DEVICE && !all_aligned16({k_new, v_new, static_cast<const float*>(k_pages), static_cast<const float*>(v_pages)}))
+            fail(BRN_ERR_INVALID_ARG, "%s: device k_new, v_new, k_pages and v_pages must be 16-byte aligned", who);
+        if ((reinterpret_cast<uintptr_t>(block_table) | reinterpret_cast<uintptr_t>(kv_lens) | reinterpret_cast<uintptr_t>(kv_lens_out) | reinterpret_cast<uintptr_t>(cu_seqlens_q)) & 3)
+            fail(BRN_ERR_INVALID_ARG, "%s: block_table, kv_lens, kv_lens_out and cu_seqlens_q must be 4-byte aligned", who);
+        if (loc == BRN_MEM_DEVICE && ((reinterpret_cast<uintptr_t>(k_scale) | reinterpret_cast<uintptr_t>(v_scale)) & 3))
+            fail(BRN_ERR_INVALID_ARG, "%s: device k_scale and v_scale must be 4-byte aligned", who);
+        ensure_device(device);
+        Staging st(stream, loc);
+        KvAppendParams p{};
+        if (k_scale) p.k_scale = st.in(k_scale, (size_t)kv_heads);
+        if (v_scale) p.v_scale = st.in(v_scale, (size_t)kv_heads);
+        p.k_new = st.in(k_new, nnew); p.v_new = st.in(v_new, nnew);
+        p.k_pages = stage_inout(st, static_cast<float*>(k_pages), pool_floats, stream);       // BRN_MEM_HOST: the pool goes up whole and comes back whole
+        p.v_pages = stage_inout(st, static_cast<float*>(v_pages), pool_floats, stream);
+        p.block_table = reinterpret_cast<const int*>(st.in(reinterpret_cast<const float*>(block_table), ntab));
+        p.kv_lens = reinterpret_cast<const int*>(st.in(reinterpret_cast<const float*>(kv_lens), (size_t)n_seqs));
+        if (kv_lens_out) p.kv_lens_out = reinterpret_cast<int*>(st.out(reinterpret_cast<float*>(kv_lens_out), (size_t)n_seqs));
+        p.pv_cu = reinterpret_cast<const int*>(st.in(reinterpret_cast<const float*>(cu_seqlens_q), (size_t)n_seqs + 1));
+        p.pv_plan = loc == BRN_MEM_DEVICE ? plan_workspace : reinterpret_cast<int*>(st.dalloc(nplan));
+        p.pv_n_seqs = n_seqs; p.pv_total_q = total_q;
+        p.kv_type = pool_type;
+        p.batch = n_seqs; p.seq_new = 0; p.kv_heads = kv_heads; p.head_dim = head_dim;
+        const long d = head_dim;
+        p.new_ss = kv_heads * d; p.new_sh = d; p.new_sb = 0;
+        p.kv_ss = kv_heads * d; p.page_stride = (long)page_size * p.kv_ss;
+        p.page_log2 = page_log2; p.n_pages = n_pages; p.max_pages = max_pages; p.cap = max_pages * page_size;
+        BRN_HIP(launch_kv_cache_append(p, (hipStream_t)stream));
         st.finish();
     });
 }

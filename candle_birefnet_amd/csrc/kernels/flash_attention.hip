@@ -88,8 +88,21 @@
 // after it see the fp32 pool of the widened bytes.  k_scale[g] joins the score scale once per workgroup (fl32(scale * k_scale[g]) where
 // the other forms have scale), v_scale[g] multiplies a row's final y once: in fa_finish_split when S == 1, in
 // flash_split_combine_kernel<true, true> when S > 1; partials and lse never see v_scale.  DESIGN.md 3.2k.
+// FA_PAGED_VARLEN (brn_flash_attention_paged_varlen_forward): the sixth form, FA_PAGED with a workgroup's rows taken from a device-side
+// plan instead of blockIdx arithmetic: a packed batch [total_q, heads, head_dim] of new tokens whose cu_seqlens_q lives on the device.
+// paged_varlen_plan_kernel (kernels/kv_cache.hip; the rule: brn_flash_paged_varlen_plan.h) runs first on the stream and leaves the clamped
+// starts s_b and the prefix of row tiles per sequence; the grid holds T_max * kv_heads * S workgroups, (row tile, K / V head, split).
+// fa_params finds the tile's sequence by bisection of the prefix (scalar loads), returns before the first barrier when the tile is past
+// the real count, and otherwise rewrites the arguments into those of an FA_PAGED workgroup of that sequence ALONE: batch 1, seq_q = n_b,
+// seq_kv = len_b, causal_off = len_b - n_b, q / y based at token s_b, the table at the sequence's row.  The table schedule, the clamps,
+// the zero-select, the staging, the scales and the walk are FA_PAGED's, untouched.  What a row IS stays n_b's business (fa_lane: masks,
+// pad rows); WHERE it goes is total_q's: fa_finish_split<.., PV> stores y, lse and the partials at r = head * total_q + s_b + query of
+// R = heads * total_q rows, the split entry's layout at batch 1, seq_q = total_q.  flash_split_combine_kernel<true, VS, PV> runs over
+// those R rows and skips the tokens outside [s_0, s_n): padding rows are written by no kernel.  A sequence's bits are those of the FA_PAGED
+// kernels called on it alone.  Every instantiation of the five older forms is the kernel it was, instruction for instruction.  DESIGN.md 3.2m.
 #include "../brn_kernels.h"
 #include "../brn_flash_varlen_plan.h"
+#include "../brn_flash_paged_varlen_plan.h"
 #include "attention_mfma.h"
 #include <type_traits>
 
@@ -104,9 +117,12 @@ constexpr int FA_VT_LD = 72;         // 16-bit kernel: elements per LDS row of V
 
 // the three forms of the kernels: a workgroup per (batch entry, head, 64 queries); per (batch entry, K / V head, 64 packed rows); per
 // (record of a packed batch, K / V head), with a window; per (batch entry, K / V head, 64 packed rows, split over keys); the same over pages
-enum FaForm { FA_PLAIN = 0, FA_PACKED = 1, FA_VARLEN = 2, FA_SPLIT = 3, FA_PAGED = 4 };
+// (FA_PAGED_VARLEN: FA_PAGED with the workgroup's rows taken from the device-side plan of a packed batch)
+enum FaForm { FA_PLAIN = 0, FA_PACKED = 1, FA_VARLEN = 2, FA_SPLIT = 3, FA_PAGED = 4, FA_PAGED_VARLEN = 5 };
+// the forms with K / V in the pages of a pool
+constexpr bool fa_paged(FaForm f) { return f == FA_PAGED || f == FA_PAGED_VARLEN; }
 // the forms whose walk is one split's range and whose finish is fa_finish_split (FA_PAGED: FA_SPLIT at the workgroup's own seq_kv, K / V in pages)
-constexpr bool fa_splits(FaForm f) { return f == FA_SPLIT || f == FA_PAGED; }
+constexpr bool fa_splits(FaForm f) { return f == FA_SPLIT || fa_paged(f); }
 
 // which (batch entry, head, query tile) this workgroup owns, where its operands start and how many K / V tiles it walks
 struct FaBlock {
@@ -172,6 +188,27 @@ __device__ __forceinline__ FaBlock fa_block_varlen(const FlashAttentionParams& p
 __device__ __forceinline__ FaBlock fa_block_split(const FlashAttentionParams& p) {
     const unsigned S = (unsigned)p.kv_splits, wg = blockIdx.x / S;
     FaBlock r = fa_block_gqa<false>(p, wg);
+    r.kt0 = (int)(blockIdx.x - wg * S) * p.tiles_per_split;
+    r.nkt = min(r.nkt, r.kt0 + p.tiles_per_split);
+    return r;
+}
+// FA_PAGED_VARLEN: the workgroup is (row tile of the plan, K / V head, split); fa_params has turned the arguments into those of the tile's
+// own sequence (q, y and the table based at it, batch 1, seq_q = n_b, seq_kv = len_b) and left the tile's first packed row in rec.q0.
+// From there it is fa_block_gqa's tile and fa_block_split's range, restated without the grid arithmetic
+__device__ __forceinline__ FaBlock fa_block_paged_varlen(const FlashAttentionParams& p, const FaVarlenRecord& rec) {
+    const unsigned S = (unsigned)p.kv_splits, wg = blockIdx.x / S;
+    const int kvh = (int)(wg % (unsigned)p.kv_heads);
+    FaBlock r;
+    r.G = p.heads / p.kv_heads;
+    r.q = p.q; r.y = p.y;
+    r.k = p.k + kvh * p.kv_sh;
+    r.v = p.v + kvh * p.kv_sh;
+    r.bias = nullptr;
+    r.h0 = kvh * r.G;
+    r.q0 = rec.q0;
+    r.rem = r.G * p.seq_q - 1 - r.q0;
+    r.nkt = (p.seq_kv + FA_T - 1) / FA_T;
+    if (p.causal) r.nkt = min(r.nkt, ((r.q0 + min(FA_BQ - 1, r.rem)) / r.G + p.causal_off) / FA_T + 1);
     r.kt0 = (int)(blockIdx.x - wg * S) * p.tiles_per_split;
     r.nkt = min(r.nkt, r.kt0 + p.tiles_per_split);
     return r;
@@ -361,13 +398,45 @@ __device__ __forceinline__ FlashAttentionParams fa_params(const FlashAttentionPa
         p.seq_kv = min(max(pa.kv_lens[fa_split_of(pa).b], 0), pa.seq_kv);       // workgroup-uniform: one scalar load
         p.causal_off = pa.causal ? p.seq_kv - pa.seq_q : 0;
         return p;
+    } else if constexpr (FORM == FA_PAGED_VARLEN) {
+        // the workgroup's row tile (blockIdx.x / S / kv_heads) among the plan's: its sequence b is the one whose tile range holds it
+        // (bisection of the prefix, workgroup-uniform scalar loads), its first packed row 64 * (tile - prefix[b]).  rec.len_q = 0 tells
+        // the kernel that there is no such tile (the grid is sized by T_max) and it returns before its first barrier.  The plan is the
+        // library's own, written by paged_varlen_plan_kernel just before; its values are clamped all the same before they bound a row
+        FlashAttentionParams p = pa;
+        const int n = pa.pv_n_seqs, total_q = pa.pv_total_q;
+        const int* starts = pa.pv_plan + fa_pv_starts_at();
+        const int* prefix = pa.pv_plan + fa_pv_tiles_at(n);
+        const int tile = (int)(blockIdx.x / (unsigned)pa.kv_splits / (unsigned)pa.kv_heads);
+        rec = FaVarlenRecord{};
+        if (tile >= prefix[n]) return p;
+        int lo = 0, hi = n;
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (prefix[mid] <= tile) lo = mid; else hi = mid;
+        }
+        const int b = lo;
+        const int s_b = min(max(starts[b], 0), total_q), n_b = min(max(starts[b + 1] - s_b, 0), total_q - s_b);
+        const long q0 = (long)(tile - prefix[b]) * FA_BQ;
+        if (q0 < 0 || q0 >= (long)(pa.heads / pa.kv_heads) * n_b) return p;
+        rec.q_start = s_b; rec.len_q = n_b; rec.q0 = (int)q0;
+        p.batch = 1; p.seq_q = n_b; p.pv_row0 = s_b;
+        p.q = pa.q + (long)s_b * pa.q_ss;
+        p.y = pa.y + (long)s_b * pa.q_ss;
+        p.block_table = pa.block_table + (long)b * pa.max_pages;
+        p.seq_kv = min(max(pa.kv_lens[b], 0), pa.seq_kv);
+        p.causal_off = pa.causal ? p.seq_kv - n_b : 0;
+        return p;
     } else return pa;
 }
 // FA_PAGED: where key t (already clamped below the sequence's length) of the workgroup's batch entry lives: its table entry, and the
 // offset of its row from the K / V head's base in the pool (64-bit), the page number clamped into the pool
 struct FaPages { const int* table; long stride; int lg, mask, last; };
+template <FaForm FORM>
 __device__ __forceinline__ FaPages fa_pages_of(const FlashAttentionParams& p) {
-    return FaPages{p.block_table + (long)fa_split_of(p).b * p.max_pages, p.page_stride, p.page_log2, (1 << p.page_log2) - 1, p.n_pages - 1};
+    // (FA_PAGED_VARLEN: fa_params has based the table at the workgroup's sequence)
+    if constexpr (FORM == FA_PAGED_VARLEN) return FaPages{p.block_table, p.page_stride, p.page_log2, (1 << p.page_log2) - 1, p.n_pages - 1};
+    else return FaPages{p.block_table + (long)fa_split_of(p).b * p.max_pages, p.page_stride, p.page_log2, (1 << p.page_log2) - 1, p.n_pages - 1};
 }
 __device__ __forceinline__ int fa_page_entry(const FaPages& pg, int t) { return pg.table[t >> pg.lg]; }
 __device__ __forceinline__ long fa_page_row(const FaPages& pg, int entry, int t, long kv_ss) {
@@ -376,6 +445,7 @@ __device__ __forceinline__ long fa_page_row(const FaPages& pg, int entry, int t,
 template <bool BIAS, FaForm FORM>
 __device__ __forceinline__ FaBlock fa_block_of(const FlashAttentionParams& p, const FaVarlenRecord& rec) {
     if constexpr (FORM == FA_VARLEN) return fa_block_varlen(p, rec);
+    else if constexpr (FORM == FA_PAGED_VARLEN) return fa_block_paged_varlen(p, rec);
     else return fa_block<BIAS, FORM>(p);
 }
 // the 4 partial sums of a query are added, and the query's row of y (null: a pad query) is stored
@@ -397,7 +467,9 @@ __device__ __forceinline__ void fa_finish(float* yrow, int g, const f32x4 (&o)[N
 // S > 1 (p.o_part): row r = (batch entry * heads + head) * seq_q + query of the workspace's O_part[split] and lse2_part[split], 64-bit
 // offsets.  S == 1: the row of y, and lse[r] = ln 2 * (m + log2 l) where lse is wanted.
 // VS (the fp8 pool): the S == 1 row of y is fl32(vs * fl32(o * inv)), vs = v_scale of the workgroup's K / V head; a partial is not scaled.
-template <int D, bool VS = false>
+// PV (FA_PAGED_VARLEN): p.seq_q is the sequence's n_b and masks alone; a row's place is r = head * total_q + s_b + query among
+// R = heads * total_q rows (the split entry's layout at batch 1, seq_q = total_q), the split the workgroup's own blockIdx.x % S
+template <int D, bool VS = false, bool PV = false>
 __device__ __forceinline__ void fa_finish_split(const FlashAttentionParams& p, const FaBlock& blk, const FaLane& ln, int g, const f32x4 (&o)[D / 16], float l, float m, float vs = 1.f) {
     const float lsum = att_group_sum(l);
     const bool empty = !(lsum > 0.f);
@@ -405,11 +477,11 @@ __device__ __forceinline__ void fa_finish_split(const FlashAttentionParams& p, c
     const float lse2 = empty ? -__builtin_inff() : m + __builtin_amdgcn_logf(lsum);
     if (ln.yrow < 0) return;
     const int row = ln.yrow, query = row / blk.G, head = blk.h0 + (row - query * blk.G);
-    const FaSplit sp = fa_split_of(p);
-    const long r = ((long)sp.b * p.heads + head) * p.seq_q + query;
+    const FaSplit sp = PV ? FaSplit{0, (int)(blockIdx.x % (unsigned)p.kv_splits)} : fa_split_of(p);
+    const long r = PV ? (long)head * p.pv_total_q + p.pv_row0 + query : ((long)sp.b * p.heads + head) * p.seq_q + query;
     float* dst; float* ldst; float lv = lse2;
     if (p.o_part) {
-        const long R = (long)p.batch * p.heads * p.seq_q;
+        const long R = PV ? (long)p.heads * p.pv_total_q : (long)p.batch * p.heads * p.seq_q;
         dst = p.o_part + ((long)sp.split * R + r) * D;
         ldst = p.lse2_part + ((long)sp.split * R + r);
     } else {
@@ -466,7 +538,7 @@ template <int D, bool BIAS, FaForm FORM, typename KV = float>
 __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const FlashAttentionParams pa) {
     constexpr bool KV16 = !std::is_same<KV, float>::value;             // a narrow pool: 16-bit elements, or (KV8) e4m3 bytes on the same map
     constexpr bool KV8 = std::is_same<KV, fa_e4m3>::value;
-    static_assert(!KV16 || (FORM == FA_PAGED && !BIAS), "16-bit and fp8 K / V storage exist for the paged form alone");
+    static_assert(!KV16 || (fa_paged(FORM) && !BIAS), "16-bit and fp8 K / V storage exist for the paged forms alone");
     constexpr int LD = D + 4, NI = D / 16, ND = D / 16, NC = D / 32;
     constexpr int NI16 = D / 32;                           // KV16: items per thread
     __shared__ __attribute__((aligned(16))) float Ks[FA_T * LD];
@@ -475,6 +547,9 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
     const int li = lane & 15, g = lane >> 4;
     FaVarlenRecord rec;
     const FlashAttentionParams p = fa_params<FORM>(pa, rec);
+    if constexpr (FORM == FA_PAGED_VARLEN) {
+        if (rec.len_q == 0) return;                        // past the plan's real tiles (workgroup-uniform, before the first barrier)
+    }
     const FaBlock blk = fa_block_of<BIAS, FORM>(p, rec);
     const FaLane ln = fa_lane<FORM>(p, blk, wave, li);
     FaFp8Scales fs{1.f, 1.f};
@@ -485,7 +560,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
             f32x4 z[D / 16];
 #pragma unroll
             for (int dt = 0; dt < D / 16; ++dt) z[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-            fa_finish_split<D, KV8>(p, blk, ln, g, z, 0.f, ATT_NEG, fs.v);
+            fa_finish_split<D, KV8, FORM == FA_PAGED_VARLEN>(p, blk, ln, g, z, 0.f, ATT_NEG, fs.v);
             return;
         }
     }
@@ -540,7 +615,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
         for (int i = 0; i < NI; ++i) {
             const int idx = tid + i * FA_THREADS, t = key0 + idx / (D / 4), c4 = (idx % (D / 4)) * 4;
             long src;
-            if constexpr (FORM == FA_PAGED) src = fa_page_row(pgs, pe[i], min(t, p.seq_kv - 1), p.kv_ss) + c4;
+            if constexpr (fa_paged(FORM)) src = fa_page_row(pgs, pe[i], min(t, p.seq_kv - 1), p.kv_ss) + c4;
             else src = min(t, p.seq_kv - 1) * p.kv_ss + c4;
             kr[i] = *reinterpret_cast<const f32x4*>(blk.k + src);
             vr[i] = *reinterpret_cast<const f32x4*>(blk.v + src);
@@ -555,9 +630,9 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
     const float sc2 = (KV8 ? p.scale * fs.k : p.scale) * ATT_LOG2E;
 
     const int kt_first = (FORM == FA_VARLEN || fa_splits(FORM)) ? blk.kt0 : 0;
-    if constexpr (FORM == FA_PAGED) { pgs = fa_pages_of(p); fetch_pages(kt_first * FA_T); use_pages(); }
+    if constexpr (fa_paged(FORM)) { pgs = fa_pages_of<FORM>(p); fetch_pages(kt_first * FA_T); use_pages(); }
     load_tile(kt_first * FA_T);
-    if constexpr (FORM == FA_PAGED) fetch_pages((kt_first + 1) * FA_T);      // (a key past the sequence is clamped into it: a valid entry, not used)
+    if constexpr (fa_paged(FORM)) fetch_pages((kt_first + 1) * FA_T);      // (a key past the sequence is clamped into it: a valid entry, not used)
     for (int kt = kt_first; kt < blk.nkt; ++kt) {
         __syncthreads();                                   // every wave is done reading the previous tile
         if constexpr (KV16) {
@@ -596,7 +671,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
             for (int s = 0; s < FA_T / 16; ++s) st[s] = bn[s];
         }
         if (kt + 1 < blk.nkt) {
-            if constexpr (FORM == FA_PAGED) { use_pages(); fetch_pages((kt + 2) * FA_T); }   // tile kt + 2's entries go out ahead of tile kt + 1's K / V
+            if constexpr (fa_paged(FORM)) { use_pages(); fetch_pages((kt + 2) * FA_T); }   // tile kt + 2's entries go out ahead of tile kt + 1's K / V
             load_tile((kt + 1) * FA_T);
         }
 #pragma unroll
@@ -624,7 +699,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_f32_kernel(const F
             }
         }
     }
-    if constexpr (fa_splits(FORM)) fa_finish_split<D, KV8>(p, blk, ln, g, o, l, m, fs.v);
+    if constexpr (fa_splits(FORM)) fa_finish_split<D, KV8, FORM == FA_PAGED_VARLEN>(p, blk, ln, g, o, l, m, fs.v);
     else fa_finish<ND, BIAS>(fa_lane_y<FORM>(p, blk, ln), g, o, l, m);
 }
 
@@ -644,7 +719,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
     constexpr bool F16 = std::is_same<E, _Float16>::value;
     constexpr bool KV16 = !std::is_same<KV, float>::value;             // a narrow pool: elements of E, or (KV8) e4m3 bytes on the same map
     constexpr bool KV8 = std::is_same<KV, fa_e4m3>::value;
-    static_assert(!KV16 || (FORM == FA_PAGED && !BIAS && (KV8 || std::is_same<KV, E>::value)), "narrow K / V storage: the paged form, in the kernel's own type or e4m3");
+    static_assert(!KV16 || (fa_paged(FORM) && !BIAS && (KV8 || std::is_same<KV, E>::value)), "narrow K / V storage: the paged forms, in the kernel's own type or e4m3");
     constexpr int NP16 = D == 128 ? 2 : 1;        // KV16: staging passes
     constexpr int NP = D / 32, ND = D / 16;       // staging passes = MFMA k steps of a score tile; d tiles of O^T
     typedef vec8<E> ex8;
@@ -655,6 +730,9 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
     const int li = lane & 15, g = lane >> 4;
     FaVarlenRecord rec;
     const FlashAttentionParams p = fa_params<FORM>(pa, rec);
+    if constexpr (FORM == FA_PAGED_VARLEN) {
+        if (rec.len_q == 0) return;                        // past the plan's real tiles (workgroup-uniform, before the first barrier)
+    }
     const FaBlock blk = fa_block_of<BIAS, FORM>(p, rec);
     const FaLane ln = fa_lane<FORM>(p, blk, wave, li);
     FaFp8Scales fs{1.f, 1.f};
@@ -665,7 +743,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
             f32x4 z[D / 16];
 #pragma unroll
             for (int dt = 0; dt < D / 16; ++dt) z[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-            fa_finish_split<D, KV8>(p, blk, ln, g, z, 0.f, ATT_NEG, fs.v);
+            fa_finish_split<D, KV8, FORM == FA_PAGED_VARLEN>(p, blk, ln, g, z, 0.f, ATT_NEG, fs.v);
             return;
         }
     }
@@ -722,7 +800,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
             for (int u = 0; u < 2; ++u) {
                 const int t = key0 + s_tp * 2 + u;
                 long src;
-                if constexpr (FORM == FA_PAGED) src = fa_page_row(pgs, pe, min(t, p.seq_kv - 1), p.kv_ss) + c4;
+                if constexpr (fa_paged(FORM)) src = fa_page_row(pgs, pe, min(t, p.seq_kv - 1), p.kv_ss) + c4;
                 else src = min(t, p.seq_kv - 1) * p.kv_ss + c4;
                 kr[ps][u] = *reinterpret_cast<const f32x4*>(blk.k + src);
                 vr[ps][u] = *reinterpret_cast<const f32x4*>(blk.v + src);
@@ -738,9 +816,9 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
     const float sc2 = (KV8 ? p.scale * fs.k : p.scale) * ATT_LOG2E;
 
     const int kt_first = (FORM == FA_VARLEN || fa_splits(FORM)) ? blk.kt0 : 0;
-    if constexpr (FORM == FA_PAGED) { pgs = fa_pages_of(p); fetch_pages(kt_first * FA_T); use_pages(); }
+    if constexpr (fa_paged(FORM)) { pgs = fa_pages_of<FORM>(p); fetch_pages(kt_first * FA_T); use_pages(); }
     load_tile(kt_first * FA_T);
-    if constexpr (FORM == FA_PAGED) fetch_pages((kt_first + 1) * FA_T);      // (a key past the sequence is clamped into it: a valid entry, not used)
+    if constexpr (fa_paged(FORM)) fetch_pages((kt_first + 1) * FA_T);      // (a key past the sequence is clamped into it: a valid entry, not used)
     for (int kt = kt_first; kt < blk.nkt; ++kt) {
         __syncthreads();                                   // every wave is done reading the previous tile
         if constexpr (KV16) {
@@ -798,7 +876,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
             for (int s = 0; s < FA_T / 16; ++s) st[s] = bn[s];
         }
         if (kt + 1 < blk.nkt) {
-            if constexpr (FORM == FA_PAGED) { use_pages(); fetch_pages((kt + 2) * FA_T); }   // tile kt + 2's entries go out ahead of tile kt + 1's K / V
+            if constexpr (fa_paged(FORM)) { use_pages(); fetch_pages((kt + 2) * FA_T); }   // tile kt + 2's entries go out ahead of tile kt + 1's K / V
             load_tile((kt + 1) * FA_T);
         }
 #pragma unroll
@@ -824,7 +902,7 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
             for (int dt = 0; dt < ND; ++dt) o[dt] = att_mfma<F16>(att_vt_frag(Vt + (dt * 16 + li) * FA_VT_LD + g * 4, t), pf, o[dt]);
         }
     }
-    if constexpr (fa_splits(FORM)) fa_finish_split<D, KV8>(p, blk, ln, g, o, l, m, fs.v);
+    if constexpr (fa_splits(FORM)) fa_finish_split<D, KV8, FORM == FA_PAGED_VARLEN>(p, blk, ln, g, o, l, m, fs.v);
     else fa_finish<ND, BIAS>(fa_lane_y<FORM>(p, blk, ln), g, o, l, m);
 }
 
@@ -842,13 +920,20 @@ __global__ void __launch_bounds__(FA_THREADS) flash_attention_s16_kernel(const F
 constexpr int FA_COMBINE_THREADS = 256;
 constexpr int FA_COMBINE_CHUNK = 8;
 // VS (with PAGED; the fp8 pool): the row of y, after the select, is multiplied by v_scale of the row's K / V head; lse is not.
-template <bool PAGED, bool VS = false>
+// PV (with PAGED; brn_flash_attention_paged_varlen_forward: batch 1, seq_q = total_q, row r = head * total_q + token): a token outside the
+// plan's [s_0, s_n) is padding, no kernel wrote its partials, and its thread returns before it reads or writes anything of the row.
+template <bool PAGED, bool VS = false, bool PV = false>
 __global__ void __launch_bounds__(FA_COMBINE_THREADS) flash_split_combine_kernel(const FlashAttentionParams p) {
     const int D4 = p.head_dim / 4;
     const long R = (long)p.batch * p.heads * p.seq_q;
     const long idx = (long)blockIdx.x * FA_COMBINE_THREADS + threadIdx.x;
     if (idx >= R * D4) return;
     const long r = idx / D4;
+    if constexpr (PV) {
+        const int* starts = p.pv_plan + fa_pv_starts_at();
+        const int token = (int)(r % p.seq_q);
+        if (token < starts[0] || token >= starts[p.pv_n_seqs]) return;
+    }
     const int d = (int)(idx - r * D4) * 4;
     const int S = p.kv_splits;
     float M = -__builtin_inff();
@@ -918,9 +1003,25 @@ void fa_launch_kv8(const FlashAttentionParams& p, dim3 grid, hipStream_t s) {
     else if (p.s16 == 1) hipLaunchKernelGGL((flash_attention_s16_kernel<__bf16, D, false, FA_PAGED, fa_e4m3>), grid, block, 0, s, p);
     else hipLaunchKernelGGL((flash_attention_s16_kernel<_Float16, D, false, FA_PAGED, fa_e4m3>), grid, block, 0, s, p);
 }
+// FA_PAGED_VARLEN: the pool types and pairings of FA_PAGED (launch_flash_attention has refused every other)
+template <int D>
+void fa_launch_paged_varlen(const FlashAttentionParams& p, dim3 grid, hipStream_t s) {
+    const dim3 block(FA_THREADS);
+    constexpr FaForm F = FA_PAGED_VARLEN;
+    if (p.kv_type == 0) fa_launch<D, false, F>(p, grid, s);
+    else if (p.kv_type == FA_KV_FP8) {
+        if (p.s16 == 0) hipLaunchKernelGGL((flash_attention_f32_kernel<D, false, F, fa_e4m3>), grid, block, 0, s, p);
+        else if (p.s16 == 1) hipLaunchKernelGGL((flash_attention_s16_kernel<__bf16, D, false, F, fa_e4m3>), grid, block, 0, s, p);
+        else hipLaunchKernelGGL((flash_attention_s16_kernel<_Float16, D, false, F, fa_e4m3>), grid, block, 0, s, p);
+    } else if (p.s16 == 0 && p.kv_type == 1) hipLaunchKernelGGL((flash_attention_f32_kernel<D, false, F, __bf16>), grid, block, 0, s, p);
+    else if (p.s16 == 0) hipLaunchKernelGGL((flash_attention_f32_kernel<D, false, F, _Float16>), grid, block, 0, s, p);
+    else if (p.s16 == 1) hipLaunchKernelGGL((flash_attention_s16_kernel<__bf16, D, false, F, __bf16>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((flash_attention_s16_kernel<_Float16, D, false, F, _Float16>), grid, block, 0, s, p);
+}
 template <int D>
 void fa_launch(const FlashAttentionParams& p, FaForm form, dim3 grid, hipStream_t s) {
     if (form == FA_VARLEN) fa_launch<D, false, FA_VARLEN>(p, grid, s);
+    else if (form == FA_PAGED_VARLEN) fa_launch_paged_varlen<D>(p, grid, s);
     else if (form == FA_PAGED && p.kv_type == FA_KV_FP8) fa_launch_kv8<D>(p, grid, s);
     else if (form == FA_PAGED && p.kv_type) fa_launch_kv16<D>(p, grid, s);
     else if (form == FA_PAGED) fa_launch<D, false, FA_PAGED>(p, grid, s);
@@ -941,6 +1042,33 @@ hipError_t launch_flash_attention(const FlashAttentionParams& p, hipStream_t s) 
     // (an e4m3 pool, FA_KV_FP8, is read by every kernel; the scale arrays exist with it alone)
     if (p.kv_type && (p.kv_type < 0 || p.kv_type > FA_KV_FP8 || !p.block_table || p.plan || (p.kv_type != FA_KV_FP8 && p.s16 && p.s16 != p.kv_type))) return hipErrorInvalidValue;
     if (p.kv_type != FA_KV_FP8 && (p.k_scale || p.v_scale)) return hipErrorInvalidValue;
+    if (p.pv_plan) {
+        // the packed paged batch: batch 1 and seq_q = pv_total_q lay out q, y, lse and the partials; the split is FA_PAGED's at
+        // seq_kv = max_kv_len; the grid holds T_max row tiles (brn_flash_paged_varlen_plan.h), the plan kernel runs first on the stream
+        const int G = p.kv_heads >= 1 && p.heads >= 1 && p.heads % p.kv_heads == 0 ? p.heads / p.kv_heads : 0;
+        if (!(p.head_dim == 32 || p.head_dim == 64 || p.head_dim == 128) || G < 1 || p.batch != 1 || p.plan || p.bias || p.n_bias || p.causal_off || p.s16 < 0 || p.s16 > 2 ||
+            !(p.scale > 0.f) || !p.pv_cu || p.pv_n_seqs < 1 || p.pv_n_seqs > FA_PV_MAX_SEQS || p.pv_total_q < 1 || p.seq_q != p.pv_total_q || (long)G * p.pv_total_q > 0x7fffffffL ||
+            p.seq_kv < 1 || p.seq_kv > 65536 || !p.block_table || !p.kv_lens || p.page_log2 < 4 || p.page_log2 > 8 || p.n_pages < 1 || p.max_pages < 1 ||
+            ((long)p.n_pages << p.page_log2) > 0x7fffffffL || ((long)p.max_pages << p.page_log2) < p.seq_kv || p.kv_sb != 0 || p.kv_sh != p.head_dim ||
+            p.kv_ss != (long)p.kv_heads * p.head_dim || p.page_stride != (p.kv_ss << p.page_log2) || p.q_sh != p.head_dim || p.q_ss != (long)p.heads * p.head_dim)
+            return hipErrorInvalidValue;
+        const int nkt = (p.seq_kv + FA_T - 1) / FA_T, S = p.kv_splits, tps = p.tiles_per_split;
+        const long nwg = fa_pv_max_tiles(G, p.pv_total_q, p.pv_n_seqs) * p.kv_heads * S;
+        const long quads = (long)p.heads * p.pv_total_q * (p.head_dim / 4);
+        if (S < 1 || tps < 1 || (long)(S - 1) * tps >= nkt || (long)S * tps < nkt || nwg < 1 || nwg > 0x7fffffffL || (S > 1) != (p.o_part != nullptr) ||
+            (S > 1) != (p.lse2_part != nullptr) || (quads + FA_COMBINE_THREADS - 1) / FA_COMBINE_THREADS > 0x7fffffffL)
+            return hipErrorInvalidValue;
+        const hipError_t e = launch_paged_varlen_plan(p.pv_cu, p.pv_n_seqs, p.pv_total_q, G, p.pv_plan, s);
+        if (e != hipSuccess) return e;
+        const dim3 grid((unsigned)nwg);
+        if (p.head_dim == 32) fa_launch<32>(p, FA_PAGED_VARLEN, grid, s);
+        else if (p.head_dim == 64) fa_launch<64>(p, FA_PAGED_VARLEN, grid, s);
+        else fa_launch<128>(p, FA_PAGED_VARLEN, grid, s);
+        const dim3 cgrid((unsigned)((quads + FA_COMBINE_THREADS - 1) / FA_COMBINE_THREADS));
+        if (S > 1 && p.kv_type == FA_KV_FP8) hipLaunchKernelGGL((flash_split_combine_kernel<true, true, true>), cgrid, dim3(FA_COMBINE_THREADS), 0, s, p);
+        else if (S > 1) hipLaunchKernelGGL((flash_split_combine_kernel<true, false, true>), cgrid, dim3(FA_COMBINE_THREADS), 0, s, p);
+        return hipGetLastError();
+    }
     if (p.plan) {
         // the packed batch: the record table was built and every value in it checked by the entry (brn_flash_varlen_plan.h); what is
         // checked here is what the kernels assume of the other arguments

@@ -22,7 +22,15 @@
 // brn_rope_forward (rope_kernel) and the rope instantiation kv_append_rows_kernel<KV, true> (brn_kv_cache_append_rope / _rope_fp8) rotate
 // pairs of a row by the caller's cos / sin table; RopeParams in brn_kernels.h states the rule.  The table row is min(position, n_pos - 1),
 // the position device data, clamped like the lengths; the rotation is two rounded products and one rounded sum, never an fma (rope_pair).
+//
+// VARLEN (brn_kv_cache_append_varlen): the new tokens are a packed batch [total_q, kv_heads, head_dim] with cu_seqlens_q on the device.
+// paged_varlen_plan_kernel (one workgroup, launched first; also the plan of brn_flash_attention_paged_varlen_forward) applies the rule of
+// brn_flash_paged_varlen_plan.h: the clamped running maximum s_b, and the prefix of row tiles the attention kernels use.  The rows kernel
+// keeps its thread map with the token in the place of (b, t): a token outside [s_0, s_n) is padding and returns; otherwise its sequence
+// is the b with s_b <= token < s_{b+1}, found by bisection of the monotone starts, t = token - s_b, and everything from pos on is the
+// plain append's.  kv_append_lens_varlen_kernel writes min(L_b + n_b, cap) afterwards.  DESIGN.md 3.2m.
 #include "../brn_kernels.h"
+#include "../brn_flash_paged_varlen_plan.h"
 #include "attention_mfma.h"
 #include <type_traits>
 
@@ -138,6 +146,41 @@ __global__ void __launch_bounds__(KV_THREADS) kv_append_rows_kernel(const KvAppe
     }
 }
 
+// the sequence of a packed token: the b in 0 .. n - 1 with starts[b] <= token < starts[b + 1] (starts non-decreasing, starts[0] <= token <
+// starts[n] checked by the caller); empty sequences (equal starts) are stepped over
+__device__ __forceinline__ int pv_sequence_of(const int* starts, int n, int token) {
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (starts[mid] <= token) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+// VARLEN (brn_kv_cache_append_varlen): the plain append's thread map with the packed token in the place of (b, t); from pos on, its rule
+template <typename KV>
+__global__ void __launch_bounds__(KV_THREADS) kv_append_rows_varlen_kernel(const KvAppendParams p) {
+    const int C8 = p.head_dim >> 3;
+    const long idx = (long)blockIdx.x * KV_THREADS + threadIdx.x;
+    const long per_t = (long)p.kv_heads * C8;
+    if (idx >= per_t * p.pv_total_q) return;
+    const int token = (int)(idx / per_t), hc = (int)(idx - token * per_t);
+    const int h = hc / C8, c8 = (hc - h * C8) * 8;
+    const int* starts = p.pv_plan + fa_pv_starts_at();
+    if (token < starts[0] || token >= starts[p.pv_n_seqs]) return;     // padding: nothing read from the table, nothing written
+    const int b = pv_sequence_of(starts, p.pv_n_seqs, token);
+    const int t = token - min(max(starts[b], 0), token);               // (starts[b] <= token here; the clamp keeps t >= 0 whatever the plan holds)
+    const long pos = (long)min(max(p.kv_lens[b], 0), p.cap) + t;
+    if (pos >= p.cap) return;                                          // dropped: nothing read from the table, nothing written
+    const int slot = min((int)(pos >> p.page_log2), p.max_pages - 1);
+    const int page = min(max(p.block_table[(long)b * p.max_pages + slot], 0), p.n_pages - 1);
+    const long dst = (long)page * p.page_stride + (pos & ((1 << p.page_log2) - 1)) * p.kv_ss + h * p.head_dim + c8;
+    const long src = token * p.new_ss + h * p.new_sh + c8;
+    const f32x4 k0 = ld4(p.k_new + src), k1 = ld4(p.k_new + src + 4);
+    const f32x4 v0 = ld4(p.v_new + src), v1 = ld4(p.v_new + src + 4);
+    kv_put8<KV>(p.k_pages, dst, k0, k1, p.k_scale, h);
+    kv_put8<KV>(p.v_pages, dst, v0, v1, p.v_scale, h);
+}
+
 // brn_rope_forward: one thread = 8 consecutive d of a (b, t, head) row, two 16-byte loads and stores; in HALF style the thread of chunk
 // c < rot_dim / 16 owns chunk c + rot_dim / 16 too, so a row has head_dim / 8 - rot_dim / 16 threads and both members of every pair are in
 // one thread's registers before either is written: y may be x.  Chunks at or past rot_dim are copied.  Threads run d-fastest, then head,
@@ -176,6 +219,52 @@ __global__ void __launch_bounds__(KV_THREADS) kv_append_lens_kernel(const KvAppe
         p.kv_lens_out[b] = (int)min((long)min(max(p.kv_lens[b], 0), p.cap) + p.seq_new, (long)p.cap);
 }
 
+// ---- the device-side plan of the packed paged entries: brn_flash_paged_varlen_plan.h states the rule, this kernel evaluates it with one
+// workgroup.  Thread i owns a contiguous chunk of the n_seqs + 1 entries of cu: the chunk's clamped maximum, the running maximum of the
+// chunks before it (LDS), then the starts of its chunk; the tile counts go the same way with a sum.  Every store is a lane's own. ----
+constexpr int PV_THREADS = 256;
+__global__ void __launch_bounds__(PV_THREADS) paged_varlen_plan_kernel(const int* cu, int n_seqs, int total_q, int G, int* plan) {
+    __shared__ int cmax[PV_THREADS];
+    __shared__ int csum[PV_THREADS];
+    const int tid = threadIdx.x, n1 = n_seqs + 1;
+    const int per = (n1 + PV_THREADS - 1) / PV_THREADS;
+    const int i0 = min(tid * per, n1), i1 = min(i0 + per, n1);
+    int* starts = plan + fa_pv_starts_at();
+    int* tiles = plan + fa_pv_tiles_at(n_seqs);
+    int mx = 0;
+    for (int i = i0; i < i1; ++i) mx = fa_pv_max(mx, fa_pv_clamp(cu[i], total_q));
+    cmax[tid] = mx;
+    __syncthreads();
+    int before = 0;
+    for (int j = 0; j < tid; ++j) before = fa_pv_max(before, cmax[j]);
+    // the starts of the chunk, and the tiles of its sequences: s_{i + 1} = max(s_i, c_{i + 1})
+    int run = before, sum = 0;
+    for (int i = i0; i < i1; ++i) {
+        run = fa_pv_max(run, fa_pv_clamp(cu[i], total_q));
+        starts[i] = run;
+        if (i < n_seqs) sum += fa_pv_tiles(G, fa_pv_max(run, fa_pv_clamp(cu[i + 1], total_q)) - run);
+    }
+    csum[tid] = sum;
+    __syncthreads();
+    int acc = 0;
+    for (int j = 0; j < tid; ++j) acc += csum[j];
+    run = before;
+    for (int i = i0; i < i1; ++i) {
+        run = fa_pv_max(run, fa_pv_clamp(cu[i], total_q));
+        tiles[i] = acc;
+        if (i < n_seqs) acc += fa_pv_tiles(G, fa_pv_max(run, fa_pv_clamp(cu[i + 1], total_q)) - run);
+    }
+}
+
+// VARLEN: kv_lens_out[b] = min(L_b + n_b, cap), n_b from the plan's starts; launched after the rows, so kv_lens_out may be kv_lens
+__global__ void __launch_bounds__(KV_THREADS) kv_append_lens_varlen_kernel(const KvAppendParams p) {
+    const int* starts = p.pv_plan + fa_pv_starts_at();
+    for (int b = threadIdx.x; b < p.pv_n_seqs; b += KV_THREADS) {
+        const int n = min(max(starts[b + 1] - starts[b], 0), p.pv_total_q);
+        p.kv_lens_out[b] = (int)min((long)min(max(p.kv_lens[b], 0), p.cap) + n, (long)p.cap);
+    }
+}
+
 // what both launchers ask of a table: the kernels index it with nothing but a clamped row and chunk offsets below rot_dim / 2
 bool rope_table_ok(const float* cs, const float* sn, int n_pos, int rot_dim, int style, int head_dim) {
     return cs && sn && n_pos >= 1 && n_pos <= (1 << 24) && rot_dim >= 16 && rot_dim <= head_dim && rot_dim % 16 == 0 && (style == 0 || style == 1);
@@ -183,8 +272,33 @@ bool rope_table_ok(const float* cs, const float* sn, int n_pos, int rot_dim, int
 
 }  // namespace
 
+hipError_t launch_paged_varlen_plan(const int* cu, int n_seqs, int total_q, int G, int* plan, hipStream_t s) {
+    if (!cu || !plan || n_seqs < 1 || n_seqs > FA_PV_MAX_SEQS || total_q < 1 || G < 1 || (long)G * total_q > 0x7fffffffL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(paged_varlen_plan_kernel, dim3(1), dim3(PV_THREADS), 0, s, cu, n_seqs, total_q, G, plan);
+    return hipGetLastError();
+}
+
 hipError_t launch_kv_cache_append(const KvAppendParams& p, hipStream_t s) {
     const long cap = (long)p.max_pages << p.page_log2;
+    if (p.pv_cu) {
+        // the packed form: batch = pv_n_seqs sequences, the tokens [pv_total_q, kv_heads, head_dim]; no rope
+        if (!(p.head_dim == 32 || p.head_dim == 64 || p.head_dim == 128) || p.kv_heads < 1 || p.batch != p.pv_n_seqs || p.pv_total_q < 1 || !p.pv_plan || p.rope_cos || p.rope_sin ||
+            p.kv_type < 0 || p.kv_type > FA_KV_FP8 || (p.kv_type != FA_KV_FP8 && (p.k_scale || p.v_scale)) || !p.k_new || !p.v_new || !p.k_pages || !p.v_pages || !p.block_table || !p.kv_lens ||
+            p.page_log2 < 4 || p.page_log2 > 8 || p.n_pages < 1 || p.max_pages < 1 || ((long)p.n_pages << p.page_log2) > 0x7fffffffL || cap > 0x7fffffffL || p.cap != cap ||
+            p.kv_ss != (long)p.kv_heads * p.head_dim || p.page_stride != (p.kv_ss << p.page_log2))
+            return hipErrorInvalidValue;
+        const long blocks = ((long)p.pv_total_q * p.kv_heads * (p.head_dim / 8) + KV_THREADS - 1) / KV_THREADS;
+        if (blocks > 0x7fffffffL) return hipErrorInvalidValue;
+        const hipError_t e = launch_paged_varlen_plan(p.pv_cu, p.pv_n_seqs, p.pv_total_q, 1, p.pv_plan, s);
+        if (e != hipSuccess) return e;
+        const dim3 grid((unsigned)blocks), block(KV_THREADS);
+        if (p.kv_type == 0) hipLaunchKernelGGL((kv_append_rows_varlen_kernel<float>), grid, block, 0, s, p);
+        else if (p.kv_type == 1) hipLaunchKernelGGL((kv_append_rows_varlen_kernel<__bf16>), grid, block, 0, s, p);
+        else if (p.kv_type == 2) hipLaunchKernelGGL((kv_append_rows_varlen_kernel<_Float16>), grid, block, 0, s, p);
+        else hipLaunchKernelGGL((kv_append_rows_varlen_kernel<kv_e4m3>), grid, block, 0, s, p);
+        if (p.kv_lens_out) hipLaunchKernelGGL(kv_append_lens_varlen_kernel, dim3(1), block, 0, s, p);
+        return hipGetLastError();
+    }
     if (!(p.head_dim == 32 || p.head_dim == 64 || p.head_dim == 128) || p.batch < 1 || p.kv_heads < 1 || p.seq_new < 1 || p.seq_new > 65536 ||
         p.kv_type < 0 || p.kv_type > FA_KV_FP8 || (p.kv_type != FA_KV_FP8 && (p.k_scale || p.v_scale)) || !p.k_new || !p.v_new || !p.k_pages || !p.v_pages || !p.block_table || !p.kv_lens || p.page_log2 < 4 ||
         p.page_log2 > 8 || p.n_pages < 1 || p.max_pages < 1 || ((long)p.n_pages << p.page_log2) > 0x7fffffffL || cap > 0x7fffffffL || p.cap != cap ||

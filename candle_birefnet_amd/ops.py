@@ -583,6 +583,123 @@ def _kv_cache_append(k_new, v_new, k_pages, v_pages, block_table, kv_lens, kv_dt
     return out
 
 
+_POOL_TYPE = {None: _ffi.BRN_POOL_F32, "bf16": _ffi.BRN_POOL_BF16, "f16": _ffi.BRN_POOL_F16, "e4m3": _ffi.BRN_POOL_E4M3}
+_POOL_DTYPE = {None: "f32", "bf16": "bf16", "f16": "f16", "e4m3": "fp8"}          # what _pool_arg calls the storage
+
+
+def flash_attention_paged_varlen_plan(total_q, n_seqs, max_kv_len, heads, kv_heads, head_dim, kv_splits=0):
+    """brn_flash_attention_paged_varlen_plan: (S, tiles_per_split, workspace_floats, plan_ints) a packed paged call with these integers
+    will use; needs no device."""
+    import ctypes as C
+    S, tps, nws, npl = C.c_int(0), C.c_int(0), C.c_size_t(0), C.c_size_t(0)
+    _ffi.check(_ffi.lib.brn_flash_attention_paged_varlen_plan(int(total_q), int(n_seqs), int(max_kv_len), int(heads), int(kv_heads), int(head_dim), int(kv_splits),
+                                                              C.byref(S), C.byref(tps), C.byref(nws), C.byref(npl)))
+    return S.value, tps.value, nws.value, npl.value
+
+
+def _int_buffer_like(keep, n):
+    """n int32 beside `keep` (a device tensor, or anything on the host)"""
+    if T._is_torch(keep):
+        import torch
+        return torch.empty(n, dtype=torch.int32, device=keep.device)
+    return np.empty(n, np.int32)
+
+
+def _packed_pool_args(kv_dtype, k_pages, v_pages, pool_shape, k_scale, v_scale, kv_heads):
+    if kv_dtype not in _POOL_TYPE:
+        raise ValueError(f"kv_dtype {kv_dtype!r} unknown (None, 'bf16', 'f16' or 'e4m3')")
+    if kv_dtype != "e4m3" and (k_scale is not None or v_scale is not None):
+        raise ValueError("k_scale and v_scale exist for kv_dtype 'e4m3' alone")
+    pk, kloc, kkeep = _pool_arg(k_pages, pool_shape, _POOL_DTYPE[kv_dtype], "k_pages")
+    pv, vloc, vkeep = _pool_arg(v_pages, pool_shape, _POOL_DTYPE[kv_dtype], "v_pages")
+    (pks, ksloc, kskeep), (pvs, vsloc, vskeep) = (_scale_arg(a, kv_heads, n) for a, n in zip((k_scale, v_scale), ("k_scale", "v_scale")))
+    return (pk, pv, pks, pvs), [kloc, vloc] + [sl for sl in (ksloc, vsloc) if sl is not None], (kkeep, vkeep, kskeep, vskeep)
+
+
+def flash_attention_paged_varlen(q, k_pages, v_pages, block_table, kv_lens, cu_seqlens_q, max_kv_len=None, causal=False, scale=None, kv_splits=0,
+                                 return_lse=False, return_partials=False, device=0, kv_dtype=None, k_scale=None, v_scale=None, out=None, lse_out=None,
+                                 workspace=None, plan_workspace=None):
+    """brn_flash_attention_paged_varlen_forward: flash_attention_paged over a PACKED batch of new tokens, one call for a mixed prefill /
+    decode step.  q [total_q, heads, head_dim] fp32; cu_seqlens_q [n_seqs + 1] int32: sequence b owns tokens cu[b] .. cu[b + 1] - 1 (the
+    library clamps it: running maximum of the values clamped to 0 .. total_q); tokens outside cu[0] .. cu[n_seqs] are padding and their
+    rows of y, lse and the partials are not written.  block_table [n_seqs, max_pages] int32, kv_lens [n_seqs] int32 (the lengths AFTER the
+    new keys were appended); the pool as flash_attention_paged takes it, STORED as kv_dtype says: None float32, "bf16", "f16", or "e4m3"
+    (with k_scale, v_scale [kv_heads] fp32 or None).  All on q's side; nothing is read back or checked here.
+    out / lse_out / workspace / plan_workspace: buffers to use instead of fresh ones (y [total_q, heads, head_dim]; lse [heads, total_q];
+    workspace >= the plan's workspace_floats fp32; plan_workspace >= the plan's plan_ints int32).
+    Returns as flash_attention_paged: y, with return_lse (y, lse [heads, total_q]), with return_partials additionally
+    (O_part [S, heads * total_q, head_dim], lse2_part [S, heads * total_q]) or (None, None) when S == 1."""
+    total_q, heads, hd = (int(s) for s in q.shape)
+    n_pages, page_size, kv_heads = (int(s) for s in k_pages.shape[:3])
+    if len(block_table.shape) != 2:
+        raise ValueError("block_table must be [n_seqs, max_pages]")
+    n_seqs, max_pages = int(block_table.shape[0]), int(block_table.shape[1])
+    if max_kv_len is None:
+        max_kv_len = min(max_pages * page_size, 65536)
+    max_kv_len = int(max_kv_len)
+    pq, loc, keep, _ = T.as_arg(q)
+    (pk, pv, pks, pvs), locs, pkeep = _packed_pool_args(kv_dtype, k_pages, v_pages, (n_pages, page_size, kv_heads, hd), k_scale, v_scale, kv_heads)
+    pt, tloc, tkeep, _ = _int32_arg(block_table, (n_seqs, max_pages), "block_table")
+    pl, lloc, lkeep, _ = _int32_arg(kv_lens, (n_seqs,), "kv_lens")
+    pc, cloc, ckeep, _ = _int32_arg(cu_seqlens_q, (n_seqs + 1,), "cu_seqlens_q")
+    if any(l != loc for l in locs + [tloc, lloc, cloc]):
+        raise ValueError("q, the pool, the scales, block_table, kv_lens and cu_seqlens_q must live on the same side")
+    S, _tps, nws, npl = flash_attention_paged_varlen_plan(total_q, n_seqs, max_kv_len, heads, kv_heads, hd, kv_splits)
+    R = heads * total_q
+    y = out if out is not None else T.alloc_like(keep, (total_q, heads, hd))
+    lse = lse_out if lse_out is not None else (T.alloc_like(keep, (heads, total_q)) if return_lse else None)
+    ws = workspace if workspace is not None else (T.alloc_like(keep, (nws,)) if S > 1 else None)
+    plan = plan_workspace if plan_workspace is not None else _int_buffer_like(keep, npl)
+    _ffi.check(_ffi.lib.brn_flash_attention_paged_varlen_forward(
+        pq, pk, pv, _POOL_TYPE[kv_dtype], pks, pvs, pt, pl, pc, total_q, n_seqs, max_kv_len, heads, kv_heads, hd, n_pages, page_size, max_pages, int(bool(causal)),
+        float(scale) if scale is not None else 0.0, int(kv_splits), T.ptr_of(y), T.ptr_of(lse) if lse is not None else None, T.ptr_of(ws) if ws is not None else None,
+        int(ws.numel() if T._is_torch(ws) else ws.size) if ws is not None else 0, T.ptr_of(plan), int(plan.numel() if T._is_torch(plan) else plan.size), loc,
+        T.device_of(keep, device), T.stream_of(keep)))
+    res = (y,) + ((lse,) if return_lse else ())
+    if return_partials:
+        res += ((ws[:S * R * hd].reshape(S, R, hd), ws[S * R * hd:S * R * (hd + 1)].reshape(S, R)) if S > 1 else (None, None),)
+    return res[0] if len(res) == 1 else res
+
+
+def kv_cache_append_varlen(k_new, v_new, cu_seqlens_q, k_pages, v_pages, block_table, kv_lens, kv_dtype=None, k_scale=None, v_scale=None, update_lens=True,
+                           plan_workspace=None, device=0):
+    """brn_kv_cache_append_varlen: kv_cache_append for a PACKED batch.  k_new, v_new [total_q, kv_heads, head_dim] fp32; cu_seqlens_q
+    [n_seqs + 1] int32, clamped by the library as in flash_attention_paged_varlen; token t of sequence b becomes key L_b + t by
+    kv_cache_append's rule, padding tokens write nothing.  The pool is written IN PLACE and taken as it is (kv_dtype None float32, "bf16",
+    "f16", "e4m3" with k_scale / v_scale).  update_lens as in kv_cache_append: True writes kv_lens in place, False returns new lengths,
+    None writes none.  Nothing is read back or checked here.  The rope recipe: rope(q, positions=...) and rope(k_new, positions=...) with
+    batch = total_q, seq = 1 and a per-token positions array, then this call."""
+    total_q, kv_heads, hd = (int(s) for s in k_new.shape)
+    n_pages, page_size = int(k_pages.shape[0]), int(k_pages.shape[1])
+    if len(block_table.shape) != 2:
+        raise ValueError("block_table must be [n_seqs, max_pages]")
+    n_seqs, max_pages = int(block_table.shape[0]), int(block_table.shape[1])
+    pk, loc, keep, _ = T.as_arg(k_new)
+    pv, vloc, vkeep, _ = T.as_arg(v_new, (total_q, kv_heads, hd))
+    (ppk, ppv, pks, pvs), locs, pkeep = _packed_pool_args(kv_dtype, k_pages, v_pages, (n_pages, page_size, kv_heads, hd), k_scale, v_scale, kv_heads)
+    pt, tloc, tkeep, _ = _int32_arg(block_table, (n_seqs, max_pages), "block_table")
+    pl, lloc, lkeep, _ = _int32_arg(kv_lens, (n_seqs,), "kv_lens")
+    pc, cloc, ckeep, _ = _int32_arg(cu_seqlens_q, (n_seqs + 1,), "cu_seqlens_q")
+    if any(l != loc for l in locs + [vloc, tloc, lloc, cloc]):
+        raise ValueError("k_new, v_new, the pool, the scales, block_table, kv_lens and cu_seqlens_q must live on the same side")
+    if update_lens is None:
+        out, po = None, None
+    elif update_lens:
+        if lkeep is not kv_lens and not (T._is_torch(kv_lens) and lkeep.data_ptr() == kv_lens.data_ptr()):
+            raise TypeError("update_lens=True needs kv_lens as a contiguous int32 tensor or array (it is written in place)")
+        out, po = kv_lens, pl
+    else:
+        out = _int_buffer_like(lkeep, n_seqs)
+        po = T.ptr_of(out)
+    # plan_ints depends on n_seqs alone: asked for at the smallest pack, so that no attention-side limit (T_max * kv_heads * S) refuses an append
+    npl = flash_attention_paged_varlen_plan(1, n_seqs, 1, 1, 1, 32)[3]
+    plan = plan_workspace if plan_workspace is not None else _int_buffer_like(keep, npl)
+    _ffi.check(_ffi.lib.brn_kv_cache_append_varlen(pk, pv, pc, total_q, n_seqs, kv_heads, hd, ppk, ppv, _POOL_TYPE[kv_dtype], pks, pvs, pt, pl, po, n_pages, page_size,
+                                                   max_pages, T.ptr_of(plan), int(plan.numel() if T._is_torch(plan) else plan.size), loc, T.device_of(keep, device),
+                                                   T.stream_of(keep)))
+    return out
+
+
 def patch_merging(x, H, W, norm_g, norm_b, reduction_w, device=0):
     """PatchMerging::forward (swin.rs:491-527): x [B,H*W,C] -> [B, ceil(H/2)*ceil(W/2), 2C]."""
     B, L, Cc = (int(v) for v in x.shape)

@@ -653,6 +653,89 @@ brn_status brn_kv_cache_append_rope_fp8(const float* k_new, const float* v_new, 
                                         const int* block_table, const int* kv_lens, int* kv_lens_out,
                                         int n_pages, int page_size, int max_pages,
                                         brn_mem loc, int device_ordinal, void* stream);
+/* The storage type of a K / V pool for the packed paged entries below: the three of brn_kv_type and the e4m3fn pool of the fp8 entries
+ * in one argument.  (The older entries keep brn_kv_type and refuse 3.) */
+typedef enum { BRN_POOL_F32 = 0, BRN_POOL_BF16 = 1, BRN_POOL_F16 = 2, BRN_POOL_E4M3 = 3 } brn_pool_type;
+/* What brn_flash_attention_paged_varlen_forward and brn_kv_cache_append_varlen will use: host-only, a pure function of its integers,
+ * like brn_flash_attention_splitkv_plan.  total_q is the CAPACITY of the pack in tokens, n_seqs its number of sequence slots.
+ * With G = heads / kv_heads, T_max = (G * total_q + 63 * min(n_seqs, total_q)) / 64 bounds the row tiles of 64 packed rows of ANY pack of
+ * at most total_q tokens in n_seqs sequences (sum_b ceil(G * n_b / 64) <= T_max: each of the at most min(n_seqs, total_q) sequences that
+ * are not empty rounds up by less than one tile); the grid is sized by it.  nkt = ceil(max_kv_len / 64);
+ * ask = kv_splits ? kv_splits : the automatic rule of brn_flash_attention_splitkv_plan on a base grid of kv_heads * T_max workgroups;
+ * tps = ceil(nkt / ask), S = ceil(nkt / tps): tps depends on max_kv_len and kv_splits alone when kv_splits is given.
+ * workspace_floats = S * R * (head_dim + 1), R = heads * total_q (not needed and not touched when S == 1).  plan_ints: the int32 count of
+ * plan_workspace, the device-side plan both entries write before they use it; its inner layout is not part of the contract.  The
+ * append entry needs the same plan_ints (it depends on n_seqs alone).  Any out pointer may be NULL.
+ * Limits: those of brn_flash_attention_paged_varlen_forward that concern these integers, under its prefix. */
+brn_status brn_flash_attention_paged_varlen_plan(int total_q, int n_seqs, int max_kv_len, int heads, int kv_heads, int head_dim, int kv_splits,
+                                                 int* splits_out, int* tiles_per_split_out, size_t* workspace_floats_out, size_t* plan_ints_out);
+/* Paged attention over a PACKED batch of new tokens: one call for a serving step that mixes decode sequences (one new token), prefill
+ * chunks (hundreds, over a prefix already in the cache) and idle slots, with every per-sequence number on the device.
+ * q, y: [total_q, heads, head_dim] fp32, packed like brn_flash_attention_varlen_forward's.  lse: [heads, total_q] fp32 or NULL, heads-major.
+ * The pool, block_table [n_seqs, max_pages], kv_lens [n_seqs] and the scales are exactly those of brn_flash_attention_paged_kv_forward /
+ * brn_flash_attention_paged_fp8_forward, pool_type (a brn_pool_type) naming the storage; k_scale and v_scale must be NULL unless
+ * pool_type is BRN_POOL_E4M3.  The pairing of pool and compute mode is the kv entry's (a 16-bit mode reads a 16-bit pool of its own
+ * type; every mode reads an fp32 or an e4m3 pool).
+ * total_q is a capacity.  cu_seqlens_q: [n_seqs + 1] int32 where `loc` says, device data like the table and the lengths: never read by
+ * the host for BRN_MEM_DEVICE, and made harmless instead of validated.  The clamp rule: with c_i = min(max(cu_seqlens_q[i], 0), total_q),
+ * s_b is the running maximum of c_i over i <= b; sequence b owns tokens s_b .. s_{b+1} - 1, n_b = s_{b+1} - s_b.  The sequences are
+ * therefore disjoint and ordered whatever the array holds.  The padding rule: tokens outside [s_0, s_{n_seqs}) are padding; their rows
+ * of y, lse and the partials are not written by any kernel of the call, the combine included.
+ * Sequence b, with len_b = min(max(kv_lens[b], 0), max_kv_len) (the length AFTER its new keys were appended): its rows are those of the
+ * paged entry with seq_q = n_b.  causal 0: a row sees keys 0 .. len_b - 1.  causal 1: key j is visible to the sequence's query i exactly
+ * when j <= i + len_b - n_b.  A row with no visible key gets y = 0 (exact zeros) and lse = -inf.  A sequence with n_b == 0 costs nothing,
+ * and no table entry of it is read.
+ * The split is that of brn_flash_attention_paged_varlen_plan.  Partials sit at row r = h * total_q + token of O_part[s] / lse2_part[s]:
+ * the split entry's layout at batch 1, seq_q = total_q.  S == 1 touches no float workspace.  No atomics; the combine order is s = 0 .. S - 1.
+ * The promise: a sequence's rows carry the bits of brn_flash_attention_paged_forward / _kv_forward / _fp8_forward in the same compute
+ * mode, for y, lse and the partials of the splits that call has, where that call is made with batch = 1, seq_q = n_b, that sequence's
+ * table row and length, the same max_kv_len and the same explicit kv_splits.  The bits depend on none of the other sequences, neither
+ * on n_seqs nor on total_q, on no physical page and on no old workspace content.  With BRN_MEM_DEVICE the call allocates nothing, does
+ * not synchronise the stream and may be captured; changing cu_seqlens_q, kv_lens, the table and the pool between replays is the
+ * intended use.  (BRN_MEM_HOST, a test convenience, stages y, lse and the workspace up as well as down, so padding rows come back as they went.)
+ * Limits (each violation is BRN_ERR_INVALID_ARG with the prefix "flash attention paged varlen:" and a message naming the limit, checked
+ * before the device): no NULL but lse, the scales and (S == 1) workspace; pool_type one of the four, the scales and the pairing above;
+ * head_dim 32, 64 or 128; heads >= 1, 1 <= kv_heads <= heads, heads % kv_heads == 0; 1 <= n_seqs <= 65536; total_q >= 1;
+ * G * total_q < 2^31; T_max * kv_heads * S < 2^31; page_size 16, 32, 64, 128 or 256; n_pages >= 1, max_pages >= 1, n_pages * page_size
+ * < 2^31; 1 <= max_kv_len <= min(65536, max_pages * page_size); 0 <= kv_splits <= 1024; causal 0 or 1; scale finite and >= 0; the
+ * workspace large enough when S > 1; plan_workspace present, 4-byte aligned and of at least plan_ints ints (the message names the count);
+ * y, lse, workspace and plan_workspace overlap neither each other nor any input, sizes in bytes; BRN_MEM_DEVICE float pointers and
+ * pools 16-byte aligned, int and scale arrays 4-byte aligned.
+ * Not provided: a window or a bias; fused rope (the recipe is below); the BHSD layout; 16-bit q / y; copy-on-write of shared pages. */
+brn_status brn_flash_attention_paged_varlen_forward(const float* q, const void* k_pages, const void* v_pages, int pool_type,
+                                                    const float* k_scale, const float* v_scale,
+                                                    const int* block_table, const int* kv_lens, const int* cu_seqlens_q,
+                                                    int total_q, int n_seqs, int max_kv_len, int heads, int kv_heads, int head_dim,
+                                                    int n_pages, int page_size, int max_pages,
+                                                    int causal, float scale, int kv_splits,
+                                                    float* y, float* lse, float* workspace, size_t workspace_floats,
+                                                    int* plan_workspace, size_t plan_ints,
+                                                    brn_mem loc, int device_ordinal, void* stream);
+/* brn_kv_cache_append / brn_kv_cache_append_fp8 for a packed batch: every sequence brings its own number of new tokens, known on the
+ * device alone.  k_new, v_new: [total_q, kv_heads, head_dim] fp32.  cu_seqlens_q is read through the clamp rule above (running maximum
+ * of the values clamped to 0 .. total_q).  Token t of sequence b (packed token s_b + t) becomes key L_b + t by the position rule of
+ * brn_kv_cache_append: L_b = min(max(kv_lens[b], 0), cap), cap = max_pages * page_size, positions at or past cap dropped, the page
+ * number clamped.  kv_lens_out[b] = min(L_b + n_b, cap), written by a later launch, so kv_lens_out may be kv_lens itself; NULL = not
+ * wanted.  Padding tokens write nothing.  Conversion per pool_type is that of brn_kv_cache_append / brn_kv_cache_append_fp8 (scales NULL
+ * unless BRN_POOL_E4M3).  plan_workspace / plan_ints: as above, from brn_flash_attention_paged_varlen_plan.
+ * The promise: the pool and kv_lens_out carry the bits of the existing append entry of that pool type called per sequence with
+ * batch = 1, seq_new = n_b.  With BRN_MEM_DEVICE the call allocates nothing, does not synchronise and may be captured.
+ * No rope is fused.  The recipe: call brn_rope_forward with batch = total_q, seq = 1 and a per-token positions array (the position each
+ * token takes in its sequence) on q and on k_new, then this append: the pool then holds the bits of brn_kv_cache_append_rope per sequence.
+ * Limits (BRN_ERR_INVALID_ARG, prefix "kv cache append varlen:", checked before the device): no NULL but kv_lens_out and the scales;
+ * pool_type one of the four, scales with BRN_POOL_E4M3 alone; head_dim 32, 64 or 128; kv_heads >= 1; 1 <= n_seqs <= 65536; total_q >= 1;
+ * page_size 16, 32, 64, 128 or 256; n_pages >= 1, max_pages >= 1, n_pages * page_size < 2^31, max_pages * page_size < 2^31; plan_workspace
+ * present, 4-byte aligned and of at least plan_ints ints; no input and not plan_workspace overlaps the pool, k_pages and v_pages not each
+ * other, kv_lens_out nothing but (wholly) kv_lens, plan_workspace nothing, sizes in bytes; BRN_MEM_DEVICE k_new, v_new, k_pages, v_pages
+ * 16-byte aligned, int and scale arrays 4-byte aligned.
+ * Not provided: a window or a bias; fused rope; the BHSD layout; 16-bit k_new / v_new; copy-on-write of shared pages. */
+brn_status brn_kv_cache_append_varlen(const float* k_new, const float* v_new, const int* cu_seqlens_q, int total_q, int n_seqs,
+                                      int kv_heads, int head_dim, void* k_pages, void* v_pages, int pool_type,
+                                      const float* k_scale, const float* v_scale,
+                                      const int* block_table, const int* kv_lens, int* kv_lens_out,
+                                      int n_pages, int page_size, int max_pages,
+                                      int* plan_workspace, size_t plan_ints,
+                                      brn_mem loc, int device_ordinal, void* stream);
 /* PatchMerging::forward (swin.rs:491-527): x [B,H*W,C] -> [B, ceil(H/2)*ceil(W/2), 2C]. */
 brn_status brn_patch_merging_forward(const float* x, int B, int H, int W, int C, const float* norm_g,
                                      const float* norm_b, const float* reduction_w, float* y, brn_mem loc,

@@ -185,6 +185,23 @@ extern "C" {
                                         k_pages: *mut c_void, v_pages: *mut c_void, k_scale: *const c_float, v_scale: *const c_float,
                                         block_table: *const c_int, kv_lens: *const c_int, kv_lens_out: *mut c_int, n_pages: c_int, page_size: c_int,
                                         max_pages: c_int, loc: c_int, device_ordinal: c_int, stream: *mut c_void) -> c_int;
+    // pool_type: brn_pool_type, 0 = f32, 1 = bf16, 2 = f16, 3 = e4m3
+    pub fn brn_flash_attention_paged_varlen_plan(total_q: c_int, n_seqs: c_int, max_kv_len: c_int, heads: c_int, kv_heads: c_int, head_dim: c_int,
+                                                 kv_splits: c_int, splits_out: *mut c_int, tiles_per_split_out: *mut c_int,
+                                                 workspace_floats_out: *mut usize, plan_ints_out: *mut usize) -> c_int;
+    pub fn brn_flash_attention_paged_varlen_forward(q: *const c_float, k_pages: *const c_void, v_pages: *const c_void, pool_type: c_int,
+                                                    k_scale: *const c_float, v_scale: *const c_float, block_table: *const c_int,
+                                                    kv_lens: *const c_int, cu_seqlens_q: *const c_int, total_q: c_int, n_seqs: c_int,
+                                                    max_kv_len: c_int, heads: c_int, kv_heads: c_int, head_dim: c_int, n_pages: c_int,
+                                                    page_size: c_int, max_pages: c_int, causal: c_int, scale: c_float, kv_splits: c_int,
+                                                    y: *mut c_float, lse: *mut c_float, workspace: *mut c_float, workspace_floats: usize,
+                                                    plan_workspace: *mut c_int, plan_ints: usize, loc: c_int, device_ordinal: c_int,
+                                                    stream: *mut c_void) -> c_int;
+    pub fn brn_kv_cache_append_varlen(k_new: *const c_float, v_new: *const c_float, cu_seqlens_q: *const c_int, total_q: c_int, n_seqs: c_int,
+                                      kv_heads: c_int, head_dim: c_int, k_pages: *mut c_void, v_pages: *mut c_void, pool_type: c_int,
+                                      k_scale: *const c_float, v_scale: *const c_float, block_table: *const c_int, kv_lens: *const c_int,
+                                      kv_lens_out: *mut c_int, n_pages: c_int, page_size: c_int, max_pages: c_int, plan_workspace: *mut c_int,
+                                      plan_ints: usize, loc: c_int, device_ordinal: c_int, stream: *mut c_void) -> c_int;
     pub fn brn_patch_merging_forward(x: *const c_float, b: c_int, h: c_int, w: c_int, c: c_int, norm_g: *const c_float,
                                      norm_b: *const c_float, reduction_w: *const c_float, y: *mut c_float, loc: c_int,
                                      device_ordinal: c_int, stream: *mut c_void) -> c_int;

@@ -64,8 +64,13 @@ Written to profiles/flash_attention_paged_fp8_bench.json.
 brn_kv_cache_append_rope (HALF, rot_dim = head_dim), brn_kv_cache_append alone, the two-call form (brn_rope_forward on k_new into a
 buffer at positions = kv_lens, then brn_kv_cache_append of it) and a device-to-device copy of the bytes written.  Written to
 profiles/flash_attention_rope_bench.json.
+--paged-varlen times brn_flash_attention_paged_varlen_forward on a packed batch (a mixed step of 31 decode sequences and one 512-token
+chunk; a pure decode step of 32 sequences; heads 32 / 8 x 128, page 64, bf16 pool and compute, causal, every length 4096) beside
+brn_flash_attention_paged_kv_forward (the yardstick: the parent's kernels) called once per group of sequences with the same number of
+new tokens, at kv_splits 0, 0, 1, 2, 4, 4: a row printed twice must repeat its result checksum.  Same protocol.  Written to
+profiles/flash_attention_paged_varlen_bench.json.
 
-  python tools/bench_flash_attention.py [--bias | --gqa | --varlen | --splitkv | --paged | --paged-kv16 | --paged-fp8 | --rope] [--row N] [--mode f32|bf16|f16] [--json PATH]"""
+  python tools/bench_flash_attention.py [--bias | --gqa | --varlen | --splitkv | --paged | --paged-kv16 | --paged-fp8 | --rope | --paged-varlen] [--row N] [--mode f32|bf16|f16] [--json PATH]"""
 import argparse
 import json
 import os
@@ -102,6 +107,11 @@ KV_APPEND_TYPES = ["bf16", "f16", "f32"]
 PAGED_KV16_JSON = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "flash_attention_paged_kv16_bench.json")
 PAGED_FP8_JSON = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "flash_attention_paged_fp8_bench.json")
 ROPE_JSON = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "flash_attention_rope_bench.json")
+PAGED_VARLEN_JSON = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "flash_attention_paged_varlen_bench.json")
+# brn_flash_attention_paged_varlen_forward: (name, [(n_b, len_b)], the existing calls that do the same work as (batch, seq_q) groups of the pack in order)
+PAGED_VARLEN_ROWS = [("mixed: 31 decode + one 512-token chunk", [(1, 4096)] * 31 + [(512, 4096)], [(31, 1), (1, 512)]),
+                     ("decode: 32 sequences", [(1, 4096)] * 32, [(32, 1)])]
+PAGED_VARLEN_SHAPE = (32, 8, 128, 64)            # heads, kv_heads, head_dim, page
 PAGED_JSON = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "flash_attention_paged_bench.json")
 HBM_BYTES_PER_S = 8.0e12
 MODES = ["f32", "bf16", "f16"]
@@ -758,6 +768,76 @@ def bench_rope(row, kv):
     return [rec]
 
 
+def bench_paged_varlen(row, kv_splits=0):
+    """brn_flash_attention_paged_varlen_forward on a packed batch beside the existing entry (brn_flash_attention_paged_kv_forward, the
+    parent's kernels) on the same work: one call per group of sequences with the same number of new tokens.  bf16 pool, bf16 compute,
+    causal, page 64, shuffled table; every record also says whether the packed rows equal the existing entry's, bit for bit"""
+    import torch
+    import candle_birefnet_amd as cb
+    from candle_birefnet_amd import ops
+    lib = cb._ffi.lib
+    name, pack, groups = row
+    heads, kv_heads, hd, page = PAGED_VARLEN_SHAPE
+    n_seqs, total_q, max_kv = len(pack), sum(n for n, _ in pack), max(L for _, L in pack)
+    max_pages = (max_kv + page - 1) // page
+    n_pages = n_seqs * max_pages
+    g = torch.Generator(device="cuda").manual_seed(1)
+    q = torch.randn(total_q, heads, hd, device="cuda", generator=g)
+    pools = [torch.randn(n_pages, page, kv_heads, hd, device="cuda", generator=g).to(torch.bfloat16) for _ in range(2)]
+    table = torch.randperm(n_pages, device="cuda", generator=g).to(torch.int32).view(n_seqs, max_pages).contiguous()
+    lens = torch.tensor([L for _, L in pack], dtype=torch.int32, device="cuda")
+    cu_h = [0]
+    for n, _ in pack:
+        cu_h.append(cu_h[-1] + n)
+    cu = torch.tensor(cu_h, dtype=torch.int32, device="cuda")
+    stream = torch.cuda.current_stream().cuda_stream
+    S, tps, need, npl = ops.flash_attention_paged_varlen_plan(total_q, n_seqs, max_kv, heads, kv_heads, hd, kv_splits)
+    y, lse, ws, plan = torch.empty_like(q), torch.empty(heads * total_q, device="cuda"), torch.empty(max(need, 4), device="cuda"), torch.empty(npl, dtype=torch.int32, device="cuda")
+
+    def packed():
+        cb._ffi.check(lib.brn_flash_attention_paged_varlen_forward(q.data_ptr(), pools[0].data_ptr(), pools[1].data_ptr(), cb._ffi.BRN_POOL_BF16, None, None, table.data_ptr(),
+                                                                   lens.data_ptr(), cu.data_ptr(), total_q, n_seqs, max_kv, heads, kv_heads, hd, n_pages, page, max_pages, 1, 0.0,
+                                                                   kv_splits, y.data_ptr(), lse.data_ptr(), ws.data_ptr(), need, plan.data_ptr(), npl, 1, 0, stream))
+        return y
+
+    # the existing entry: the groups' rows of q, table and lens are contiguous slices of the pack's
+    calls, at, seq_at = [], 0, 0
+    for batch, seq_q in groups:
+        assert all(n == seq_q for n, _ in pack[seq_at:seq_at + batch])
+        gS, _, gneed = ops.flash_attention_splitkv_plan(batch, seq_q, max_kv, heads, kv_heads, hd, kv_splits)
+        gy = torch.empty(batch, seq_q, heads, hd, device="cuda")
+        calls.append((q[at:at + batch * seq_q], table[seq_at:seq_at + batch], lens[seq_at:seq_at + batch], batch, seq_q, gy, torch.empty(batch * heads * seq_q, device="cuda"),
+                      torch.empty(max(gneed, 4), device="cuda"), gneed, gS))
+        at += batch * seq_q
+        seq_at += batch
+
+    def existing():
+        for gq, gt, gl, batch, seq_q, gy, glse, gws, gneed, _ in calls:
+            cb._ffi.check(lib.brn_flash_attention_paged_kv_forward(gq.data_ptr(), pools[0].data_ptr(), pools[1].data_ptr(), cb._ffi.BRN_KV_BF16, gt.data_ptr(), gl.data_ptr(), batch,
+                                                                   seq_q, max_kv, heads, kv_heads, hd, n_pages, page, max_pages, 0, 1, 0.0, kv_splits, gy.data_ptr(), glse.data_ptr(),
+                                                                   gws.data_ptr(), gneed, 1, 0, stream))
+        return torch.cat([c[5].reshape(-1, heads, hd) for c in calls])
+
+    ops.set_compute("bf16")
+    try:
+        te, tp = _time_alternating([existing, packed])
+        same = bool(torch.equal(te[4], tp[4])) if all(c[9] == S for c in calls) or kv_splits else None      # the bits are promised at the same explicit kv_splits
+        keys = sum(L for _, L in pack) * kv_heads * hd
+        rec = {"row": name, "total_q": total_q, "n_seqs": n_seqs, "max_kv_len": max_kv, "heads": heads, "kv_heads": kv_heads, "head_dim": hd, "mode": "bf16", "pool": "bf16",
+               "page_size": page, "table": "shuffled", "causal": 1, "kv_splits": kv_splits, "S": S, "tiles_per_split": tps, "existing_calls": [(c[3], c[4], c[9]) for c in calls],
+               "packed_over_existing": round(tp[0] / te[0], 4), "packed_below_highest_existing_round_median": bool(tp[0] < te[3]), "same_bits": same,
+               "kv_bytes": 2 * 2 * keys, "packed_y_sha1": __import__("hashlib").sha1(tp[4].cpu().numpy().tobytes()).hexdigest()[:16]}
+        rec.update(_side("existing", te))
+        rec.update(_side("packed", tp))
+        print(f"{name}, kv_splits {kv_splits}: existing {len(calls)} call(s) (S {[c[9] for c in calls]}) {te[0]:8.4f} ms [{te[2]:.4f} .. {te[3]:.4f}] | packed (S {S}) {tp[0]:8.4f} ms "
+              f"[{tp[2]:.4f} .. {tp[3]:.4f}] x{rec['packed_over_existing']:.3f} bits {same} y {rec['packed_y_sha1']}", flush=True)
+    finally:
+        ops.set_compute("f32")
+    del q, pools, calls
+    torch.cuda.empty_cache()
+    return [rec]
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--bias", action="store_true", help="time brn_flash_attention_bias_forward beside the bias-free call and torch + bias")
@@ -768,6 +848,7 @@ if __name__ == "__main__":
     ap.add_argument("--paged-kv16", action="store_true", help="time brn_flash_attention_paged_kv_forward on 16-bit pools beside the fp32-pool entry, and brn_kv_cache_append beside a copy")
     ap.add_argument("--paged-fp8", action="store_true", help="time brn_flash_attention_paged_fp8_forward on an e4m3 pool beside the 16-bit-pool and fp32-pool entries, and brn_kv_cache_append_fp8 beside a copy")
     ap.add_argument("--rope", action="store_true", help="time brn_kv_cache_append_rope beside the plain append, rope + append in two calls, and a copy")
+    ap.add_argument("--paged-varlen", action="store_true", help="time brn_flash_attention_paged_varlen_forward (a mixed prefill / decode step, a pure decode step) beside the existing paged entry called per group; every row is printed twice")
     ap.add_argument("--row", type=int, choices=range(len(BIAS_ROWS)))
     ap.add_argument("--mode", choices=MODES)
     ap.add_argument("--json", help="write the records to this file")
@@ -776,8 +857,16 @@ if __name__ == "__main__":
     if cb.device_count() < 1:
         sys.exit("no HIP device: nothing is measured")
     recs = []
-    if a.bias + a.gqa + a.varlen + a.splitkv + a.paged + a.paged_kv16 + a.paged_fp8 + a.rope > 1:
-        sys.exit("--bias, --gqa, --varlen, --splitkv, --paged, --paged-kv16, --paged-fp8 and --rope are separate tables: one at a time")
+    if a.bias + a.gqa + a.varlen + a.splitkv + a.paged + a.paged_kv16 + a.paged_fp8 + a.rope + a.paged_varlen > 1:
+        sys.exit("--bias, --gqa, --varlen, --splitkv, --paged, --paged-kv16, --paged-fp8, --rope and --paged-varlen are separate tables: one at a time")
+    if a.paged_varlen:
+        for row in (PAGED_VARLEN_ROWS if a.row is None else [PAGED_VARLEN_ROWS[a.row]] if a.row < len(PAGED_VARLEN_ROWS) else sys.exit(f"--row {a.row}: only {len(PAGED_VARLEN_ROWS)} rows in this table")):
+            for ks in (0, 0, 1, 2, 4, 4):            # the automatic rule and kv_splits 4 twice: a repeated row must repeat its result
+                recs += bench_paged_varlen(row, ks)
+        with open(a.json or PAGED_VARLEN_JSON, "w") as f:
+            json.dump({"tool": "tools/bench_flash_attention.py --paged-varlen", "warmup": GQA_WARMUP, "timed": GQA_ROUNDS * GQA_TIMED, "rows": recs}, f, indent=1)
+            f.write("\n")
+        sys.exit(0)
     if a.rope:
         for row in (KV_APPEND_ROWS if a.row is None else [KV_APPEND_ROWS[a.row]] if a.row < len(KV_APPEND_ROWS) else sys.exit(f"--row {a.row}: only {len(KV_APPEND_ROWS)} rows in this table")):
             for kv in KV_APPEND_TYPES + ["fp8"]:
